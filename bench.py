@@ -16,10 +16,15 @@ Two multi-GPU modes (`config.workload` names the one that ran):
           total frames / time.  --emulate-world K runs rank 0's shard of a K-rank split on ONE GPU (no collective).
 There is no data-path collective; `config.gather_bytes_per_step` says what each GPU receives per step.
 
-Prints ONE JSON line on rank 0 (driver contract), including
+Prints ONE JSON line on rank 0 (driver contract).  A plain run (`--gpus 1 --steps N --warmup W`) does only what the headline
+needs -- set-up, W warm-up steps, the N timed steps, the result line -- and its line carries
   roofline      dominant kernel: algorithmic bytes per launch / HIP-event duration vs 8 TB/s, plus the instruction
-                side (`issue`: priced at the clock MEASURED in this run) and the PMC traffic / VALU-busy share of the committed
-                profile of the SAME sources (`profiles_head`)
+                side (`issue`: priced at the clock `sustained` MEASURED, else at 2.4 GHz) and the PMC traffic / VALU-busy share of the committed
+                profile of the SAME sources (`profiles_head`); from the stage events of the timed steps themselves
+  matcher       map points/s and brute-force-equivalent Hamming pairs/s of the SearchByProjection stage (same events).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs).  --full adds everything else,
+each block after the timed steps and still switchable on its own (--sustained-seconds 0, --no-verify, --no-host-io,
+--no-latency, --no-cpu-baseline):
   sustained     a second timed region behind the driver's K steps: the same step loop for >= 5 s, every step's duration from HIP
                 events (p50 / p99 / max), the first and the last 100 steps, and the shader clock the chip held meanwhile, read in
                 the kernel (s_memtime over s_memrealtime, orbfe_debug_clock_probe) on a stream beside the workload
@@ -29,8 +34,7 @@ Prints ONE JSON line on rank 0 (driver contract), including
   latency       the reference's own call shape -- ONE host frame per call (src/Frame.cc:178-189): orbfe_extract from
                 pageable and pinned memory, orbfe_match_projection (2000 map points), orbfe_prepare_and_extract, each
                 the median of >= 200 calls, next to the single-thread oracle on the same call
-  value_host_io frames/s with host pointers in and out through the pipelined ring (orbfe_stream_*)
-  matcher       map points/s and brute-force-equivalent Hamming pairs/s of the SearchByProjection stage.
+  value_host_io frames/s with host pointers in and out through the pipelined ring (orbfe_stream_*).
 --images DIR runs the same step on grey-converted image files (PGM / PNG / JPEG via PIL, centre-cropped or resized to
 the workload geometry) for BASELINE configs 2/3/5 where EuRoC / TUM-VI data exists; the default is synthetic.
 """
@@ -598,6 +602,46 @@ def verify_last_step(runner, frames_host, state, B, cap, M, cfg, n_frames=8):
     return out
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: all files together (the limit is 64 MB)
+KP_FIELDS = ("x", "y", "size", "angle", "response", "octave")
+
+
+def dump_sample(B, cap, n_levels):
+    """frames of the batch whose keypoints / descriptors / match indices --dump-outputs writes: all of them while they fit in
+    DUMP_BUDGET_BYTES, else a fixed, seeded sample (sorted).  Depends on the arguments only, never on the results."""
+    per_frame = cap * (len(KP_FIELDS) + 32 + 1) * 4
+    k = min(B, max(1, (DUMP_BUDGET_BYTES - B * (n_levels + 2) * 8) // per_frame))
+    return np.arange(B) if k == B else np.sort(np.random.default_rng(0).choice(B, k, replace=False))
+
+
+def dump_outputs(path, runner, B, cap, n_levels, M):
+    """--dump-outputs DIR: what the LAST timed step computed, the arrays a caller of the step receives, as DIR/<name>.npy
+    (integers exactly, in float32 / float64), so that two builds can be compared output for output.  Whole batch:
+    n_keypoints [B], keypoints_per_level [B, levels], n_matches [B] (float64).  The frames of dump_sample(): keypoints
+    [F, cap, 6] (x, y, size, angle, response, octave), descriptors [F, cap, 32] (one byte per value), matches [F, cap] (map point
+    index or -1) in float32; slots past a frame's keypoint count are 0 (matches -1), whatever the buffers held there."""
+    import orbfe
+    b, _ = runner.last
+    if runner.cuda:
+        torch.cuda.synchronize(b["n"].device)
+    idx = dump_sample(B, cap, n_levels)
+    sel = torch.from_numpy(idx).to(b["n"].device)
+    n_all = b["n"][:B].cpu().numpy()
+    out = {"n_keypoints": n_all.astype(np.float64), "keypoints_per_level": b["per"][:B].cpu().numpy().astype(np.float64)}
+    valid = np.arange(cap)[None, :] < n_all[idx][:, None]
+    kp = b["kp"][sel].cpu().numpy().reshape(len(idx), cap * 24).view(orbfe.KP_DTYPE).reshape(len(idx), cap)
+    out["keypoints"] = np.stack([kp[f].astype(np.float32) for f in KP_FIELDS], axis=2)
+    out["descriptors"] = b["desc"][sel].cpu().numpy().astype(np.float32)
+    out["keypoints"][~valid] = 0
+    out["descriptors"][~valid] = 0
+    if M:
+        out["n_matches"] = b["nmatch"][:B].cpu().numpy().astype(np.float64)
+        out["matches"] = np.where(valid, b["match"][sel].cpu().numpy(), -1).astype(np.float32)
+    os.makedirs(path, exist_ok=True)
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
 def launch_ranks(n, argv):
     """`bench.py --gpus N` started as ONE process: start N ranks (one per GPU) through torch.distributed.run on
     127.0.0.1 and relay rank 0's JSON line.  The parent never initialises the GPU (no torch.cuda call, no HIP call): the
@@ -1007,9 +1051,17 @@ def main():
     ap.add_argument("--no-match", action="store_true", help="extract only")
     ap.add_argument("--no-overlap", action="store_true", help="match on the extraction stream (no 2-stream pipelining)")
     ap.add_argument("--lib", default=None, help="load this build of liborbfe instead (tools/: the timing-only ablation build)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the sustained region, the oracle check (`verified`, `gather_verified`; exit 4 "
+                         "on a mismatch), value_host_io, the latency block and the CPU baselines; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (rank 0) to DIR/<name>.npy, float32 / float64, at most 64 MB: "
+                         "counts of the whole batch, keypoints / descriptors / match indices of a fixed sample of its frames")
     a = ap.parse_args()
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started as one process: become the launcher of N ranks BEFORE anything touches the GPU
         sys.exit(launch_ranks(a.gpus, sys.argv[1:]))
@@ -1181,15 +1233,17 @@ def main():
 
     dt, stage_ms, ncalls = timed_run(a.steps, a.warmup)
     ex.device_status()  # device-side guard flags of the last chain (raises if any is set); outside the timed region
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, runner, B, cap, ex.nlevels, M)
 
     # ---- the second timed region: the same loop for >= 5 s, per-step durations and the clock (the headline above is untouched) ----
     sustained = None
-    if a.sustained_seconds > 0:
+    if a.full and a.sustained_seconds > 0:
         sustained = sustained_run(runner, ex, dev, dist, frames_total, a.sustained_seconds, rank, world, a.sustained_dump)
         ex.device_status()
     # ---- the line checks itself: 8 frames of the last step that ran against the oracle; the gathered bytes against the packed ones ----
     verified, gather_verified, all_ok = None, None, True
-    if not a.no_verify:
+    if a.full and not a.no_verify:
         torch.cuda.synchronize(dev)
         verified = verify_last_step(runner, frames_sets, state, B, cap, M, cfg)
         ok = verified["kp_desc_equal"] and verified.get("match_equal", True)
@@ -1307,7 +1361,7 @@ def main():
                               # search evaluates a small fraction of them, this is the rate a brute-force matcher would need
                               "pairs_per_s_bruteforce_equivalent": B * M * n_kp_mean / (mm * 1e-3),
                               "note": "stage time on its own stream while the next step's extraction runs beside it"}
-        if not a.no_host_io and world == 1 and scaling == "weak":
+        if a.full and not a.no_host_io and world == 1 and scaling == "weak":
             slot = min(256, B)
             try:
                 # long enough (>= 0.1 s) that filling and draining the three-slot ring is a few per cent of the timed region
@@ -1343,12 +1397,12 @@ def main():
                                "mean_keypoints_per_frame": float(runner.bufs[0]["n"][:B].float().mean().item()),
                                "fast_ms": st_ms["fast_nms_blur"] / max(1, nc)}
             out["texture_sweep"] = sweep
-        if not a.no_latency and world == 1 and not emu:
+        if a.full and not a.no_latency and world == 1 and not emu:
             try:
                 out["latency"] = latency_block(cfg, local_rank, frames_sets[0], a.latency_calls, a.latency_tail_calls)
             except orbfe.OrbfeError as e:
                 out["latency"] = {"error": str(e)}
-        if not a.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
+        if a.full and not a.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
             sample = frames_sets[0][:64]
             fps, n = cpu_baseline(cfg, sample, a.cpu_seconds, bool(M), orbfe.MP_DTYPE, pin_core=0)
             out["cpu_baseline"] = {"value": fps, "unit": "frames/s", "cores": 1, "kind": "port",

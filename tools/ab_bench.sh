@@ -1,8 +1,8 @@
 #!/bin/bash
 # A/B on ONE box: bench.py with every library under tools/ab/ (earlier builds) and with the shipped one, alternating, the
-# headline steps plus a 3 s sustained region each.  Usage: tools/ab_bench.sh <out-prefix> <rounds> [bench args...]
+# headline steps plus a 3 s sustained region each (--full).  Usage: tools/ab_bench.sh <out-prefix> <rounds> [bench args...]
 out=${1:?prefix}; rounds=${2:-3}; shift; shift || true
-args="${@:---steps 20 --warmup 5 --no-cpu-baseline --no-host-io --no-latency --sustained-seconds 3}"
+args="${@:---full --steps 20 --warmup 5 --no-cpu-baseline --no-host-io --no-latency --sustained-seconds 3}"
 for i in $(seq 1 $rounds); do
   for lib in tools/ab/*.so shipped; do
     name=$(basename $lib .so); name=${name#liborbfe_}
