@@ -673,18 +673,19 @@ __global__ __launch_bounds__(256) void proj_topk_wave_kernel(ProjArgs A, int mpw
     else topk_wave_body<WIDE, false>(A, S, sList, f, lane, wv, nMine, i, w, cs, tabStride, rec, descS, segBase);
 }
 
-// One persistent block per frame, one THREAD per map point, chunks of 1024 map points in index order.
-// The frame's keypoints (cell, octave, x, y) and descriptors, in rank order, are staged in LDS once (frames
-// up to kResN keypoints), so sweeps and the exact rescans of starved map points never touch global memory.
+// One persistent block per frame, one THREAD per map point, chunks of THREADS map points in index order.
+// The 1024-thread form stages the frame's keypoints (cell, octave, x, y) and, up to kResNDesc keypoints, descriptors
+// in LDS once (frames up to kResN keypoints), so its sweeps and exact rescans never touch global memory.  The batched
+// form (IMG = false, see proj_resolve_kernel) keeps only the claim and column tables in LDS and reads the rest through L2.
 constexpr int kResN = 2048;
 
 constexpr int kResNDesc = 1280;  // frames up to this many keypoints also keep their descriptors in LDS (77 KB per block)
 
-template <int N, bool DESC>
+template <int N, bool DESC, bool IMG>
 struct ResolveLdsT {
     int claim[3][N];                      // by rank; three rotating tables (final / this sweep / next sweep)
-    uint8_t oct[N];                       // by rank
-    int4 rec[N];                          // by storage slot: {rank, octave | cell y << 8, x bits, y bits}
+    uint8_t oct[IMG ? N : 1];             // by rank
+    int4 rec[IMG ? N : 1];                // by storage slot: {rank, octave | cell y << 8, x bits, y bits}
     // descriptors by storage slot: the exact rescans of starved map points (hundreds per frame when many map points
     // compete for look-alike keypoints) then never wait on global memory
     unsigned long long desc[DESC ? N * 4 : 4];
@@ -704,7 +705,7 @@ __device__ __forceinline__ void wave_top2_u32(uint32_t& k1, uint32_t& k2)
 // exact rescan for a map point whose stored top-K ran dry: one WAVE scans the contiguous rank range of the
 // window's grid columns (lane-strided) and reduces the two smallest free keys; all lanes get the result.
 // The claim test goes first: a starved map point sits in a region where nearly everything is taken.
-template <bool LDS, bool DESC, typename SLds>
+template <bool IMG, bool DESC, typename SLds>
 __device__ __forceinline__ void full_scan_top2_wave(const ProjArgs& A, int f, int i, const MpWindow& w,
                                                     const unsigned long long (&d4)[4], const int* cs, const int* claim,
                                                     const SLds* S, int lane, uint32_t& k1, uint32_t& k2)
@@ -720,7 +721,7 @@ __device__ __forceinline__ void full_scan_top2_wave(const ProjArgs& A, int f, in
             const int plo = csl[w.minCX], phi = csl[w.maxCX + 1];  // all rows of the window's columns
             for (int p = plo + lane; p < phi; p += 64) {
                 int4 q;
-                if constexpr (LDS) q = S->rec[p];
+                if constexpr (IMG) q = S->rec[p];
                 else q = rec[p];
                 if (claim[q.x] < i) continue;
                 const int cy = q.y >> 8;
@@ -733,8 +734,10 @@ __device__ __forceinline__ void full_scan_top2_wave(const ProjArgs& A, int f, in
                 else dist = hamming256(reinterpret_cast<const uint2*>(descS + (size_t)p * 4), d4);
                 if (dist >= A.dCut) continue;
                 const uint32_t key = make_key32(dist, q.x);
-                if (key < k1) { k2 = k1; k1 = key; }
-                else if (key < k2) k2 = key;
+                // running (min, second) without a branch: k1 <= k2 (a branch that picks which of the two to
+                // overwrite made the compiler keep the pair in scratch memory)
+                k2 = umed3(k1, key, k2);
+                k1 = min(k1, key);
             }
         }
     }
@@ -745,21 +748,27 @@ __device__ __forceinline__ void full_scan_top2_wave(const ProjArgs& A, int f, in
 // them) instead of being fetched by the rescanning wave, one after the other
 constexpr int kFbLds = 192;
 constexpr int kResTabLds = 1024;  // column-start tables up to this many entries are kept in LDS too
+constexpr int kFbBatched = 32;    // parking area of the batched form
 
-// THREADS: 1024 for small launches (fewest ordered chunks: shortest call); 256 when the chip is full anyway -- a 1024-thread
-// block with its register and LDS footprint keeps a whole CU to itself while it mostly waits on barriers.
-template <bool LDS, int THREADS, int N = kResN, bool DESC = false>
+// THREADS: 1024 for small launches (fewest ordered chunks: shortest call).  LDS: claim tables in LDS (else claimG).
+// IMG: the frame's records and octaves are staged in LDS too (else read through L2).  FB: parked starved map points.
+// The batched form <LDS, 256, kResN, false, false, kFbBatched> (proj_launch, B >= kResolveBatchedMinFrames) is sized to
+// fit beside seven blocks of the FAST kernel on one CU: <= 120 VGPRs, no scratch, 34 KB of LDS (claim tables, column
+// tables, parking area; records, octaves and descriptors come through L2).  The 1024-thread form keeps a whole CU to
+// itself and can only start on an empty one.  Chunks of 256 map points are exact by the same induction as chunks of 1024.
+template <bool LDS, int THREADS, int N = kResN, bool DESC = false, bool IMG = LDS, int FB = kFbLds>
 __global__ __launch_bounds__(THREADS) void proj_resolve_kernel(ProjArgs A)
 {
-    __shared__ ResolveLdsT<N, DESC> S;
+    static_assert(LDS || !IMG, "the LDS image goes with LDS claim tables");
+    __shared__ ResolveLdsT<N, DESC, IMG> S;
     __shared__ int sChanged[2];
     __shared__ int sGaveUp[2];                           // a claim HOLDER moved away in this sweep (by sweep parity): ranks came free
     __shared__ int sCount;
     __shared__ int sFbCount[2];                          // starved map points of the current sweep (by sweep parity, like sChanged)
     __shared__ int sFbMp[THREADS];
     __shared__ uint32_t sFbK1[THREADS], sFbK2[THREADS];
-    __shared__ MpWindow sFbWin[kFbLds];
-    __shared__ unsigned long long sFbDesc[kFbLds][4];
+    __shared__ MpWindow sFbWin[FB];
+    __shared__ unsigned long long sFbDesc[FB][4];
     __shared__ int sTab[LDS ? kResTabLds : 1];
     const int f = blockIdx.x;
     const int tid = threadIdx.x;
@@ -767,14 +776,14 @@ __global__ __launch_bounds__(THREADS) void proj_resolve_kernel(ProjArgs A)
     const int M = A.M;
     // Claim tables (by rank): value = -1 if the slot holds a map point with observations on entry (:77-79), else the
     // smallest accepted map point (with observations) whose best match is that keypoint, else kClaimFree.
-    // Three tables rotate so that a sweep needs TWO block barriers instead of five: T[fin] holds the final claims of
-    // the earlier chunks; T[cur] = T[fin] + the tentative claims of this sweep (written by atomicMin in phase 1, read
-    // in phase 2); T[nxt] is refilled with a copy of T[fin] during phase 2 for the next sweep.  A chunk that has
-    // converged promotes T[cur] to final.
-    int* T[3];
-#pragma unroll
-    for (int q = 0; q < 3; q++) T[q] = LDS ? S.claim[q] : A.claimG + ((size_t)f * 3 + q) * A.kpStride;
-    int fin = 0, cur = 1, nxt = 2;
+    // Three tables rotate so that a sweep needs TWO block barriers instead of five: Tfin holds the final claims of
+    // the earlier chunks; Tcur = Tfin + the tentative claims of this sweep (written by atomicMin in phase 1, read
+    // in phase 2); Tnxt is refilled with a copy of Tfin during phase 2 for the next sweep.  A chunk that has
+    // converged promotes Tcur to final.
+    // (rotated as pointers: an index into a pointer array would live in scratch memory)
+    int* Tfin = LDS ? S.claim[0] : A.claimG + ((size_t)f * 3 + 0) * A.kpStride;
+    int* Tcur = LDS ? S.claim[1] : A.claimG + ((size_t)f * 3 + 1) * A.kpStride;
+    int* Tnxt = LDS ? S.claim[2] : A.claimG + ((size_t)f * 3 + 2) * A.kpStride;
     const orbfe_map_point* mps = A.mps + (size_t)f * M;
     const int* order = A.order + (size_t)f * A.kpStride;
     const int4* rec = A.rec + (size_t)f * A.kpStride;
@@ -782,11 +791,11 @@ __global__ __launch_bounds__(THREADS) void proj_resolve_kernel(ProjArgs A)
 
     for (int r = tid; r < n; r += THREADS) {
         const int v = (initObs && initObs[order[r]] > 0) ? -1 : kClaimFree;
-        T[fin][r] = v;
-        T[cur][r] = v;
+        Tfin[r] = v;
+        Tcur[r] = v;
     }
     const uint8_t* octByRank = A.octByRank + (size_t)f * A.kpStride;
-    if constexpr (LDS) {
+    if constexpr (IMG) {
         for (int r = tid; r < n; r += THREADS) {
             S.rec[r] = rec[r];
             S.oct[r] = octByRank[r];
@@ -829,18 +838,18 @@ __global__ __launch_bounds__(THREADS) void proj_resolve_kernel(ProjArgs A)
         // the pair the verdict was made from survives the sweep: a later sweep looks again only if it has to
         uint32_t k1 = kKey32None, k2 = kKey32None;
         bool k2StandIn = false;  // k2 is the K-th key standing in for an unseen second best: taken itself, nothing to watch
-        // (T[cur] == T[fin] here: initialised above / refilled at the end of the previous chunk)
+        // (Tcur == Tfin here: initialised above / refilled at the end of the previous chunk)
         for (int iter = 0; iter <= THREADS + 1; iter++) {
             // ---- phase 1: this sweep's tentative claims on top of the final ones ----
             if (tid == 0) { sChanged[iter & 1] = 0; sFbCount[iter & 1] = 0; sGaveUp[iter & 1] = 0; }  // last read two barriers ago
-            if (res >= 0 && obs > 0) atomicMin(&T[cur][res], i);
+            if (res >= 0 && obs > 0) atomicMin(&Tcur[res], i);
             __syncthreads();
             // ---- phase 2: the map points whose verdict may have moved look for their two best free candidates ----
-            // T[cur] is rebuilt every sweep from the final claims + every lane's current verdict.  Unless a claim HOLDER
+            // Tcur is rebuilt every sweep from the final claims + every lane's current verdict.  Unless a claim HOLDER
             // moved away in the previous sweep (sGaveUp), every entry of it is <= the previous sweep's: what was taken
             // stays taken, so a lane whose best and second best are still free would find the same pair again -- it keeps
             // its verdict without looking (2 lookups instead of kTopK; a wave whose lanes all keep theirs skips the rest).
-            const int* claim = T[cur];
+            const int* claim = Tcur;
             bool look = iter == 0 || sGaveUp[(iter & 1) ^ 1] != 0;
             if (!look && c > 0) {
                 const int c1 = k1 != kKey32None ? claim[(int)(k1 & kRankMask)] : kClaimFree;
@@ -884,7 +893,7 @@ __global__ __launch_bounds__(THREADS) void proj_resolve_kernel(ProjArgs A)
                     if (!decided) {  // exact rescan, done cooperatively below
                         slot = atomicAdd(&sFbCount[iter & 1], 1);
                         sFbMp[slot] = i;
-                        if (slot < kFbLds) {
+                        if (slot < FB) {
                             sFbWin[slot] = mp_window(A, mps[i]);
                             const unsigned long long* dp = reinterpret_cast<const unsigned long long*>(A.mpDesc + ((size_t)f * M + i) * 32);
 #pragma unroll
@@ -892,24 +901,25 @@ __global__ __launch_bounds__(THREADS) void proj_resolve_kernel(ProjArgs A)
                         }
 #ifdef ORBFE_DIAG
                         atomicAdd(&A.dbg[f * 4 + 1], 1);  // diagnostics build only: exact rescans of this frame
+                        if (slot >= FB) atomicAdd(&A.dbg[f * 4 + 2], 1);  // ... of which not parked (window + descriptor from global memory)
 #endif
                     }
                 }
             }
-            // the table of the next sweep starts as a copy of the final claims (nobody reads or writes T[nxt] in this phase)
-            for (int k = tid; k < n; k += THREADS) T[nxt][k] = T[fin][k];
+            // the table of the next sweep starts as a copy of the final claims (nobody reads or writes Tnxt in this phase)
+            for (int k = tid; k < n; k += THREADS) Tnxt[k] = Tfin[k];
             auto verdict = [&]() {
                 int result = -1;
                 if (k1 != kKey32None) {
                     const int bestDist = (int)(k1 >> kRankBits), bestRank = (int)(k1 & kRankMask);
                     int bestLevel;
-                    if constexpr (LDS) bestLevel = S.oct[bestRank];
+                    if constexpr (IMG) bestLevel = S.oct[bestRank];
                     else bestLevel = octByRank[bestRank];
                     int bestDist2 = 256, bestLevel2 = -1;
                     if (k2 != kKey32None) {
                         bestDist2 = (int)(k2 >> kRankBits);
                         const int r2 = (int)(k2 & kRankMask);
-                        if constexpr (LDS) bestLevel2 = S.oct[r2];
+                        if constexpr (IMG) bestLevel2 = S.oct[r2];
                         else bestLevel2 = octByRank[r2];
                     }
                     if (bestDist <= ORBFE_TH_HIGH) {  // :108-117
@@ -938,7 +948,7 @@ __global__ __launch_bounds__(THREADS) void proj_resolve_kernel(ProjArgs A)
                     const int mp = sFbMp[q];
                     MpWindow w;
                     unsigned long long d4[4];
-                    if (q < kFbLds) {
+                    if (q < FB) {
                         w = sFbWin[q];
 #pragma unroll
                         for (int t = 0; t < 4; t++) d4[t] = sFbDesc[q][t];
@@ -948,7 +958,7 @@ __global__ __launch_bounds__(THREADS) void proj_resolve_kernel(ProjArgs A)
 #pragma unroll
                         for (int t = 0; t < 4; t++) d4[t] = dp[t];
                     }
-                    full_scan_top2_wave<LDS, DESC>(A, f, mp, w, d4, cs, claim, &S, tid & 63, a1, a2);
+                    full_scan_top2_wave<IMG, DESC>(A, f, mp, w, d4, cs, claim, &S, tid & 63, a1, a2);
                     if ((tid & 63) == 0) { sFbK1[q] = a1; sFbK2[q] = a2; }
                 }
                 __syncthreads();
@@ -962,20 +972,20 @@ __global__ __launch_bounds__(THREADS) void proj_resolve_kernel(ProjArgs A)
 #ifdef ORBFE_DIAG
             if (tid == 0) atomicAdd(&A.dbg[f * 4 + 0], 1);  // diagnostics build only: sweeps of this frame
 #endif
-            if (!sChanged[iter & 1]) break;  // fixed point: T[cur] = final claims + this chunk's
+            if (!sChanged[iter & 1]) break;  // fixed point: Tcur = final claims + this chunk's
             // next sweep writes its claims into the fresh copy
-            const int tq = cur;
-            cur = nxt;
-            nxt = tq;
+            int* const tq = Tcur;
+            Tcur = Tnxt;
+            Tnxt = tq;
         }
         // the converged table becomes the final one; the next chunk starts from a copy of it
         {
-            const int tq = fin;
-            fin = cur;
-            cur = tq;
+            int* const tq = Tfin;
+            Tfin = Tcur;
+            Tcur = tq;
         }
         if (chunk + THREADS < M) {
-            for (int k = tid; k < n; k += THREADS) T[cur][k] = T[fin][k];
+            for (int k = tid; k < n; k += THREADS) Tcur[k] = Tfin[k];
             __syncthreads();
         }
         // F->mvpMapPoints[bestIdx] = pMP in map-point order: the last writer wins; nmatches counts accepts
@@ -1099,13 +1109,28 @@ int proj_launch(hipStream_t s, ProjArgs& A, std::string& err)
     // Block shape of the resolve pass: a frame is a dependent chain of sweeps, so the call is shortest with the fewest
     // chunks (1024 threads).  Frames of up to kResNDesc keypoints also stage their descriptors in LDS: the exact rescans
     // of starved map points (one wave each, ~250 per frame on the bench stream) then run out of LDS on all 16 waves.
+    // Large launches take the batched form: a block that fits next to seven FAST blocks starts as soon as one retires, where
+    // a 1024-thread block waits for an empty CU and then holds it mostly on barriers.  Threshold (kResolveBatchedMinFrames)
+    // from a launch-size sweep, both forms forced, bench step at --batch B (profiles/r06_resolve_launch_sweep.json):
+    //   beside the next batch's extraction, ms/step 1024-thread -> batched: B 128 0.720 -> 0.696, 256 1.308 -> 1.253,
+    //     384 1.870 -> 1.809, 512 2.490 -> 2.399 (the batched form wins at every size);
+    //   alone (--no-overlap), resolve stage ms: B 128 0.285 -> 0.312, 256 0.365 -> 0.392, 384 0.486 -> 0.482,
+    //     512 0.612 -> 0.575 (the 1024-thread form wins up to 256 frames: four times fewer ordered chunks per frame).
+    // Launches below 384 frames -- single frames, the host ring's slots of <= 256 frames, whose matcher runs after the
+    // slot's own extraction on one stream, i.e. alone -- keep the 1024-thread form; from 384 on the batched form is no
+    // slower alone and faster beside other work.
+    const bool batched = A.B >= kResolveBatchedMinFrames;
 #ifdef ORBFE_DIAG
-    static const int envT = getenv("ORBFE_RESOLVE_THREADS") ? atoi(getenv("ORBFE_RESOLVE_THREADS")) : 0;  // tuning experiments
-    const int rt = envT ? envT : kResolveThreads;
+    // tuning experiments: ORBFE_RESOLVE_THREADS=0 forces the batched form, 1024 the whole-CU form, 256 the 256-thread whole-frame-image form
+    static const int envT = getenv("ORBFE_RESOLVE_THREADS") ? atoi(getenv("ORBFE_RESOLVE_THREADS")) : -1;
+    const int rt = envT >= 0 ? envT : (batched ? 0 : kResolveThreads);
 #else
-    const int rt = kResolveThreads;  // the shipped library reads no environment variable here (liborbfe_diag.so does)
+    const int rt = batched ? 0 : kResolveThreads;  // the shipped library reads no environment variable here (liborbfe_diag.so does)
 #endif
-    if (lds && A.kpStride <= kResNDesc && rt == kResolveThreads) {
+    if (rt == 0) {
+        if (lds) hipLaunchKernelGGL((proj_resolve_kernel<true, 256, kResN, false, false, kFbBatched>), dim3(A.B), dim3(256), 0, s, A);
+        else hipLaunchKernelGGL((proj_resolve_kernel<false, 256, kResN, false, false, kFbBatched>), dim3(A.B), dim3(256), 0, s, A);
+    } else if (lds && A.kpStride <= kResNDesc && rt == kResolveThreads) {
         hipLaunchKernelGGL((proj_resolve_kernel<true, kResolveThreads, kResNDesc, true>), dim3(A.B), dim3(kResolveThreads), 0, s, A);
     } else if (rt == 256) {
         if (lds) hipLaunchKernelGGL((proj_resolve_kernel<true, 256>), dim3(A.B), dim3(256), 0, s, A);
@@ -1192,7 +1217,8 @@ int match_projection_run(MatchScratch& m, hipStream_t s, const orbfe_frame_view*
     if (getenv("ORBFE_DEBUG_MATCH")) {  // liborbfe_diag.so only (tools/diag_match.py, tools/resolve_stats.py)
         int dbg[4] = {0, 0, 0, 0};
         (void)copy_sync(dbg, A.dbg, sizeof dbg, hipMemcpyDeviceToHost, s);
-        fprintf(stderr, "[orbfe] match_projection: n=%d M=%d sweeps=%d cooperative_rescans=%d\n", n, M, dbg[0], dbg[1]);
+        fprintf(stderr, "[orbfe] match_projection: n=%d M=%d sweeps=%d cooperative_rescans=%d unparked_rescans=%d\n", n, M, dbg[0], dbg[1],
+                dbg[2]);
     }
 #endif
     memcpy(matchOut, hMatch, (size_t)n * sizeof(int));

@@ -10,6 +10,7 @@ namespace proj {
 
 constexpr int kClaimFree = 0x7fffffff;
 constexpr int kResolveThreads = 1024;
+constexpr int kResolveBatchedMinFrames = 384;  // launches of at least this many frames take the batched resolve form (proj_launch: measured)
 constexpr int kTopK = 24;         // stored candidates per map point
 constexpr uint32_t kKey32None = 0xffffffffu;
 constexpr int kRankBits = 20;
@@ -51,7 +52,7 @@ struct ProjArgs {
     uint32_t* topk;               // [B][M][kTopK] sorted smallest keys (contiguous per map point)
     int* claimG;                  // [B][kpStride] fallback claim table (frames that do not fit the LDS image)
     int* perm;                    // [B][M] map points ordered by (level, tile): work assignment of the top-K pass
-    int* dbg;                     // [B][4] diagnostics: sweeps, cooperative rescans, -, -
+    int* dbg;                     // [B][4] diagnostics: sweeps, cooperative rescans, rescans beyond the parking area, -
     int* matchOut;                // [B][kpStride]
     int* nMatches;                // [B]
 };
