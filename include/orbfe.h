@@ -672,7 +672,10 @@ int orbfe_bow_transform(orbfe_handle *h, orbfe_vocab *v, const uint8_t *desc, in
  * host in between.  A frame feature whose word has weight 0 (a stopped word) is in no node of mFeatVec
  * (TemplatedVocabulary.h:1168-1172,1196-1200) and takes no part in the matching, although its word_id_out / node_id_out /
  * weight_out (== 0) are still returned.  Results are byte-identical to orbfe_extract -> orbfe_bow_transform ->
- * orbfe_match_bow with the FeatureVectors of both sides (features with weight > 0 only).  HOST pointers; gray may be pinned (read in place) or pageable. */
+ * orbfe_match_bow with the FeatureVectors of both sides (features with weight > 0 only), at every extractor configuration
+ * orbfe_track_frame accepts (per-frame keypoint capacity below 2^20): frames of up to 7168 keypoints are matched from LDS,
+ * larger ones from per-node lists built in device memory, in the same graph.  HOST pointers; gray may be pinned (read in
+ * place) or pageable. */
 int orbfe_track_reference_keyframe(orbfe_handle *h, const uint8_t *gray, int pitch, const orbfe_vocab *vocab, int levelsup,
                                    const orbfe_keyframe *kf, const uint8_t *kf_has_mp, float nn_ratio,
                                    int check_orientation, orbfe_keypoint *kp_out, uint8_t *desc_out, int *n_out,

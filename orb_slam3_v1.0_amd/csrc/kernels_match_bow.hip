@@ -4,6 +4,8 @@
 // a node sequentially and scans the node's frame features in parallel (top-2 under the total order
 // (distance, position in the node's list)); a single block then applies the rotation histogram.
 #include <algorithm>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 
 #include "keyframe.h"
@@ -35,8 +37,10 @@ struct BowArgs {
 // One vocabulary node shared by key frame and frame (:166-300): the key-frame features kfIdx[k0 .. k1e) of the node in
 // DBoW2 order, sequentially (later ones skip frame features matched by earlier ones, :188); the node's frame features
 // fList[0 .. fCount) scanned by the wave.  IdxT: the frame-side list lives in HBM (CSR from the host) or in LDS (built by
-// the wave from the per-feature node ids); AngKF / AngF: orientation of a key-frame / frame feature.
-template <typename IdxT, typename AngKF, typename AngF>
+// the wave from the per-feature node ids); AngKF / AngF: orientation of a key-frame / frame feature.  kByIndex: ties of
+// the top-2 are broken by the feature index instead of the position in fList -- the same order for a list in ascending
+// index, and independent of the list's order otherwise (the device-built lists of bow_track_csr_kernel).
+template <bool kByIndex, typename IdxT, typename AngKF, typename AngF>
 __device__ __forceinline__ void bow_walk_node(const int* __restrict__ kfIdx, int k0, int k1e, const IdxT* fList, int fCount,
                                               const uint8_t* __restrict__ kfDesc, const uint8_t* __restrict__ kfHasMP,
                                               const uint8_t* __restrict__ fDesc, int nLeftArg, float nnRatio, int checkOrientation,
@@ -59,7 +63,7 @@ __device__ __forceinline__ void bow_walk_node(const int* __restrict__ kfIdx, int
             if (matchOut[realIdxF] >= 0) continue;
             const int dist = hamming256(reinterpret_cast<const uint2*>(fDesc + (size_t)realIdxF * 32), d4);
             if (dist >= 256) continue;
-            const unsigned long long key = ((unsigned long long)dist << 32) | (unsigned)iF;
+            const unsigned long long key = ((unsigned long long)dist << 32) | (unsigned)(kByIndex ? realIdxF : iF);
             if (realIdxF < nLeft) {
                 if (key < k1) { k2 = k1; k1 = key; }
                 else if (key < k2) k2 = key;
@@ -76,7 +80,7 @@ __device__ __forceinline__ void bow_walk_node(const int* __restrict__ kfIdx, int
         if (bestDist1 <= ORBFE_TH_LOW) {  // :237
             bool wrote = false;
             if ((float)bestDist1 < nnRatio * (float)bestDist2) {  // :239
-                const int bestIdxF = (int)fList[(int)(k1 & 0xffffffffu)];
+                const int bestIdxF = kByIndex ? (int)(k1 & 0xffffffffu) : (int)fList[(int)(k1 & 0xffffffffu)];
                 if (lane == 0) {
                     matchOut[bestIdxF] = realIdxKF;
                     if (checkOrientation) {
@@ -91,7 +95,7 @@ __device__ __forceinline__ void bow_walk_node(const int* __restrict__ kfIdx, int
             }
             // right camera (:263-286): accepted whenever its best distance passes TH_LOW (the ratio test is "|| true")
             if (r1 != kKeyNone && (int)(r1 >> 32) <= ORBFE_TH_LOW) {
-                const int bestIdxFR = (int)fList[(int)(r1 & 0xffffffffu)];
+                const int bestIdxFR = kByIndex ? (int)(r1 & 0xffffffffu) : (int)fList[(int)(r1 & 0xffffffffu)];
                 if (lane == 0) {
                     matchOut[bestIdxFR] = realIdxKF;
                     if (checkOrientation) {
@@ -115,7 +119,7 @@ __global__ __launch_bounds__(256) void bow_match_kernel(BowArgs A)
     const int lane = threadIdx.x & 63;
     if (g >= A.G) return;
     const int f0 = A.fOff[g];
-    bow_walk_node(A.kfIdx, A.kfOff[g], A.kfOff[g + 1], A.fIdx + f0, A.fOff[g + 1] - f0, A.kfDesc, A.kfHasMP, A.fDesc, A.nLeft,
+    bow_walk_node<false>(A.kfIdx, A.kfOff[g], A.kfOff[g + 1], A.fIdx + f0, A.fOff[g + 1] - f0, A.kfDesc, A.kfHasMP, A.fDesc, A.nLeft,
                   A.nnRatio, A.checkOrientation, A.matchOut, A.binOf, [&](int i) { return A.kfAngle[i]; },
                   [&](int i) { return A.fAngle[i]; }, lane);
 }
@@ -326,10 +330,88 @@ __global__ __launch_bounds__(64) void bow_track_kernel(BowTrackArgs A)
                 }
             }
         } else {
-            bow_walk_node(R.order, k0, k0 + cntK, list, cnt, R.desc, A.kfHasMP, A.fDesc, -1, A.nnRatio, A.checkOrientation,
+            bow_walk_node<false>(R.order, k0, k0 + cntK, list, cnt, R.desc, A.kfHasMP, A.fDesc, -1, A.nnRatio, A.checkOrientation,
                           A.matchOut, A.binOf, [&](int i) { return R.kp[i].angle; }, [&](int i) { return A.fKp[i].angle; }, lane);
         }
         __builtin_amdgcn_wave_barrier();  // the LDS arrays are rewritten for the block's next node
+    }
+}
+
+// Frames of more than kBowLdsCap features (the node ids and a 16-bit list of the frame no longer fit in LDS): the frame side
+// of every key-frame node as a CSR in HBM, built on the device -- the group of every feature (binary search of its node in
+// the key frame's ascending nodeList), a count per group, an exclusive scan, a scatter -- and walked one wave per group as
+// bow_match_kernel walks the host's CSR.  The scatter's atomics leave a group's list in no particular order; the walk breaks
+// ties by feature index, which is what the position in DBoW2's ascending list amounts to.
+constexpr int kBowLdsCap = 7168;
+
+__global__ __launch_bounds__(256) void bow_csr_count_kernel(BowTrackArgs A)
+{
+    const BowKfRef R = *A.ref;
+    const int nF = min(*A.nF, A.cap);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nF; i += gridDim.x * blockDim.x) {
+        int g = -1;
+        if (A.weight[A.fLeaf[i]] > 0.0) {  // stopped words are in no node (as sNode of bow_track_kernel)
+            const int nid = A.fBow[2 * i + 1];
+            int lo = 0, hi = R.G;  // first entry >= nid
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (R.nodeList[mid] < nid) lo = mid + 1;
+                else hi = mid;
+            }
+            if (lo < R.G && R.nodeList[lo] == nid) g = lo;
+        }
+        A.fGrp[i] = g;
+        if (g >= 0) atomicAdd(&A.fCnt[g], 1);
+    }
+}
+
+// fOff[0 .. G] = exclusive scan of the counts; the counts become the scatter's cursors (fCnt[g] = fOff[g]).  One block,
+// each thread a contiguous run of groups.
+__global__ __launch_bounds__(1024) void bow_csr_scan_kernel(BowTrackArgs A)
+{
+    __shared__ int sSum[1024];
+    const int G = A.ref->G;
+    const int t = threadIdx.x, per = (G + 1023) / 1024;
+    const int b = min(G, t * per), e = min(G, b + per);
+    int sum = 0;
+    for (int g = b; g < e; g++) sum += A.fCnt[g];
+    sSum[t] = sum;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+        const int v = t >= d ? sSum[t - d] : 0;
+        __syncthreads();
+        sSum[t] += v;
+        __syncthreads();
+    }
+    int off = sSum[t] - sum;
+    for (int g = b; g < e; g++) {
+        const int c = A.fCnt[g];
+        A.fOff[g] = off;
+        A.fCnt[g] = off;
+        off += c;
+    }
+    if (t == 1023) A.fOff[G] = sSum[1023];
+}
+
+__global__ __launch_bounds__(256) void bow_csr_scatter_kernel(BowTrackArgs A)
+{
+    const int nF = min(*A.nF, A.cap);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nF; i += gridDim.x * blockDim.x) {
+        const int g = A.fGrp[i];
+        if (g >= 0) A.fIdx[atomicAdd(&A.fCnt[g], 1)] = i;
+    }
+}
+
+__global__ __launch_bounds__(256) void bow_track_csr_kernel(BowTrackArgs A)
+{
+    const BowKfRef R = *A.ref;
+    const int lane = threadIdx.x & 63;
+    for (int g = blockIdx.x * 4 + (threadIdx.x >> 6); g < R.G; g += gridDim.x * 4) {  // wave-uniform
+        const int f0 = A.fOff[g], cnt = A.fOff[g + 1] - f0;
+        if (cnt == 0) continue;
+        bow_walk_node<true>(R.order, R.nodeOff[g], R.nodeOff[g + 1], A.fIdx + f0, cnt, R.desc, A.kfHasMP, A.fDesc, -1, A.nnRatio,
+                            A.checkOrientation, A.matchOut, A.binOf, [&](int i) { return R.kp[i].angle; },
+                            [&](int i) { return A.fKp[i].angle; }, lane);
     }
 }
 
@@ -422,14 +504,28 @@ int match_bow_run(MatchScratch& m, hipStream_t s, int G, const int* kfOff, const
 
 int bow_track_launch(hipStream_t s, const BowTrackArgs& A, std::string& err)
 {
-    if (A.cap <= 0 || A.cap > 7168) {  // 16-bit list entries; node ids + one list of cap entries in LDS (<= 61 KB)
-        err = "bow_track_launch: frame capacity outside (0, 7168]";
+    if (A.cap <= 0 || A.cap >= (1 << 20) || A.capGroups < 0) {
+        err = "bow_track_launch: frame capacity outside (0, 2^20)";
         return ORBFE_ERR_UNSUPPORTED;
     }
     const dim3 blk(256);
     // (A.matchOut arrives filled with -1: the vocabulary descent that runs before this wrote it)
-    const size_t lds = (size_t)kBowNodeCap * (2 * sizeof(uint4) + sizeof(float)) + (size_t)A.cap * (sizeof(int) + sizeof(uint16_t));
-    hipLaunchKernelGGL(bow_track_kernel, dim3(512), dim3(64), lds, s, A);
+    bool csr = A.cap > kBowLdsCap;
+#ifdef ORBFE_DIAG
+    if (getenv("ORBFE_BOW_CSR")) csr = true;  // liborbfe_diag.so only: the HBM lists on frames that fit in LDS
+    if (csr) fprintf(stderr, "orbfe diag: bow_track_launch: node lists in HBM (cap %d, key-frame node capacity %d)\n", A.cap, A.capGroups);
+#endif
+    if (!csr) {  // 16-bit list entries; node ids + one list of cap entries in LDS (<= 61 KB)
+        const size_t lds = (size_t)kBowNodeCap * (2 * sizeof(uint4) + sizeof(float)) + (size_t)A.cap * (sizeof(int) + sizeof(uint16_t));
+        hipLaunchKernelGGL(bow_track_kernel, dim3(512), dim3(64), lds, s, A);
+    } else {
+        const dim3 grid((A.cap + 255) / 256);
+        hipLaunchKernelGGL(fill_kernel, dim3((A.capGroups + 255) / 256), blk, 0, s, A.fCnt, 0, (size_t)A.capGroups);
+        hipLaunchKernelGGL(bow_csr_count_kernel, grid, blk, 0, s, A);
+        hipLaunchKernelGGL(bow_csr_scan_kernel, dim3(1), dim3(1024), 0, s, A);
+        hipLaunchKernelGGL(bow_csr_scatter_kernel, grid, blk, 0, s, A);
+        hipLaunchKernelGGL(bow_track_csr_kernel, dim3(512), blk, 0, s, A);
+    }
     hipLaunchKernelGGL(bow_track_finalize_kernel, dim3(1), blk, 0, s, A);
     MCHK(hipGetLastError());
     return ORBFE_OK;

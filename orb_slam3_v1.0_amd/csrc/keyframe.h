@@ -83,6 +83,12 @@ struct BowTrackArgs {
     int* matchOut;              // [cap] key-frame feature matched to frame feature i, -1 = none
     int* binOf;                 // [cap] scratch
     int* nMatches;
+    // scratch of frames above 7168 features (the per-node frame lists in HBM, bow_track_launch)
+    int* fGrp;                  // [cap] group (index into ref->nodeList) of every frame feature, -1 = none
+    int* fIdx;                  // [cap] the frame features of every group
+    int* fCnt;                  // [capGroups] features per group, then the scatter's cursors
+    int* fOff;                  // [capGroups + 1] ranges of fIdx
+    int capGroups;              // >= ref->G
 };
 int bow_track_launch(hipStream_t s, const BowTrackArgs& A, std::string& err);
 

@@ -2569,7 +2569,7 @@ namespace {
 
 struct RefLayout {
     size_t inFrame, oRef, oFlags, inBytes;
-    size_t oPer, oKp, oDesc, oMatch, oBow, oLeaf, outBytes /* what is downloaded */, oBin, devBytes;
+    size_t oPer, oKp, oDesc, oMatch, oBow, oLeaf, outBytes /* what is downloaded */, oBin, oGrp, oFIdx, oFCnt, oFOff, devBytes;
 };
 
 RefLayout ref_layout(const orbfe_handle* h, int capFlags)
@@ -2590,6 +2590,11 @@ RefLayout ref_layout(const orbfe_handle* h, int capFlags)
     L.oLeaf = take(cap * sizeof(int));
     L.outBytes = off;
     L.oBin = take(cap * sizeof(int));
+    // the per-node frame lists of frames above 7168 features (bow_track_launch): a key frame has at most capFlags nodes
+    L.oGrp = take(cap * sizeof(int));
+    L.oFIdx = take(cap * sizeof(int));
+    L.oFCnt = take((size_t)capFlags * sizeof(int));
+    L.oFOff = take(((size_t)capFlags + 1) * sizeof(int));
     L.devBytes = off;
     return L;
 }
@@ -2653,6 +2658,11 @@ int ref_enqueue(orbfe_handle* h, const RefLayout& L, int inPitch, const orbfe::V
         A.matchOut = reinterpret_cast<int*>(h->dRefOut + L.oMatch);
         A.binOf = reinterpret_cast<int*>(h->dRefOut + L.oBin);
         A.nMatches = dHead + 2;
+        A.fGrp = reinterpret_cast<int*>(h->dRefOut + L.oGrp);
+        A.fIdx = reinterpret_cast<int*>(h->dRefOut + L.oFIdx);
+        A.fCnt = reinterpret_cast<int*>(h->dRefOut + L.oFCnt);
+        A.fOff = reinterpret_cast<int*>(h->dRefOut + L.oFOff);
+        A.capGroups = h->refCapFlags;
         rc = bow_track_launch(s, A, err);
     }
     if (rc != ORBFE_OK) {
@@ -2678,7 +2688,7 @@ extern "C" int orbfe_track_reference_keyframe(orbfe_handle* h, const uint8_t* gr
     const KeyFrameDev* K = kf->k;
     if (K->n > 0 && !kf_has_mp) return ORBFE_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
-    if (h->P.kpCapFrame > 7168) return ORBFE_ERR_UNSUPPORTED;  // the matcher's per-frame LDS arrays (bow_track_launch)
+    if (h->P.kpCapFrame >= (1 << 20)) return ORBFE_ERR_UNSUPPORTED;
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     const int W = h->prm.image_width, H = h->prm.image_height, nL = h->nLevels;

@@ -112,7 +112,9 @@ def test_oracle_fuse_matches_restatement(built):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("M,th,stereo,seed,kb8", [(2000, 3.0, False, 1, False), (1500, 3.0, True, 2, False), (700, 8.0, True, 3, False),
-                                                  (1, 3.0, False, 4, False), (1500, 4.0, False, 5, True)])
+                                                  (1, 3.0, False, 4, False), (1500, 4.0, False, 5, True),
+                                                  # th = 10: the radius LocalMapping::SearchInNeighbors passes (src/LocalMapping.cc:822,852)
+                                                  (2000, 10.0, False, 6, False), (1500, 10.0, True, 7, False)])
 def test_gpu_fuse_search_matches_oracle(built, M, th, stereo, seed, kb8):
     import orbfe
     from orbfe import synth
@@ -166,7 +168,8 @@ def test_oracle_fuse_right_matches_restatement(built):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("M,th,stereo,seed,kb8,short", [(1500, 3.0, False, 1, False, 0), (1200, 4.0, True, 2, True, 150), (600, 8.0, False, 3, True, 700)])
+@pytest.mark.parametrize("M,th,stereo,seed,kb8,short", [(1500, 3.0, False, 1, False, 0), (1200, 4.0, True, 2, True, 150), (600, 8.0, False, 3, True, 700),
+                                                        (1500, 10.0, True, 4, False, 100)])
 def test_gpu_fuse_search_right_matches_oracle(built, M, th, stereo, seed, kb8, short):
     import orbfe
     from orbfe import synth

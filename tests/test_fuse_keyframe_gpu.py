@@ -31,7 +31,9 @@ def ids_of(pts, base=0):
 
 
 @pytest.mark.parametrize("M,th,stereo,seed,kb8", [(2000, 3.0, False, 1, False), (1500, 3.0, True, 2, False), (700, 8.0, True, 3, False),
-                                                  (1, 3.0, False, 4, False), (1500, 4.0, False, 5, True)])
+                                                  (1, 3.0, False, 4, False), (1500, 4.0, False, 5, True),
+                                                  # th = 10: the radius LocalMapping::SearchInNeighbors passes (src/LocalMapping.cc:822,852)
+                                                  (2000, 10.0, False, 6, False), (1500, 10.0, True, 7, False)])
 def test_resident_fuse_search_matches_oracle(built, M, th, stereo, seed, kb8):
     import orbfe
     from orbfe import synth
@@ -70,7 +72,8 @@ def test_resident_fuse_search_matches_oracle(built, M, th, stereo, seed, kb8):
     kf.close()
 
 
-def test_search_in_neighbors_sequence(built):
+@pytest.mark.parametrize("th", [3.0, 10.0])  # 10: the radius of src/LocalMapping.cc:822,852
+def test_search_in_neighbors_sequence(built, th):
     """LocalMapping::SearchInNeighbors: the current key frame's map points are fused into K = 20 neighbours one after the other;
     between two calls the caller edits the map (Fuse :829-849: a matched point is REPLACED by the neighbour's -- its descriptor
     and position change -- or added to the key frame -- it is skipped from then on where IsInKeyFrame holds).  Resident key
@@ -113,8 +116,8 @@ def test_search_in_neighbors_sequence(built):
         call_pts["skip"] = in_kf
         ids = np.where(in_kf, ~np.arange(M, dtype=np.int32), np.arange(M, dtype=np.int32)).astype(np.int32)
         fvo = O.make_frame_view(nb["kp"], nb["desc"], 64, 48, 0.0, 0.0, float(W), float(H), eo.scaleFactors)
-        bi_r, bd_r = O.fuse_search(fvo, nb["is2"], nb["ur"], nb["Fo"], 3.0, call_pts, mpd)
-        bi, bd = m.Fuse_search_keyframe(nb["kf"], mp, ids, nb["Fp"], 3.0)
+        bi_r, bd_r = O.fuse_search(fvo, nb["is2"], nb["ur"], nb["Fo"], th, call_pts, mpd)
+        bi, bd = m.Fuse_search_keyframe(nb["kf"], mp, ids, nb["Fp"], th)
         assert np.array_equal(bi, bi_r) and np.array_equal(bd, bd_r), "neighbour %d" % k
         hit = np.flatnonzero(bd_r <= orbfe.ORBmatcher.TH_LOW)
         total += len(hit)

@@ -3,6 +3,10 @@ ExtractORB -> the per-feature part of Frame::ComputeBoW -> ORBmatcher::SearchByB
 (Tracking::TrackReferenceKeyFrame, src/Tracking.cc:825-835; every frame while the IMU is not initialised, :454-458) -- as
 ONE submission against a key frame resident in HBM, compared bit for bit with the oracle's chain
 O.Extractor.extract -> O.vocab_transform -> (merge-walk of the two FeatureVectors) -> O.search_by_bow."""
+import os
+import re
+import sys
+
 import numpy as np
 import pytest
 
@@ -60,7 +64,10 @@ def make_kf(eo, t, levelsup, img):
     return dict(kp=kp, desc=desc, node=np.where(weight > 0, node, -1).astype(np.int32))
 
 
-@pytest.mark.parametrize("k,L,levelsup", [(10, 5, 3), (10, 6, 4), (6, 4, 1), (6, 4, 4)])
+STREAM_CASES = [(10, 5, 3), (10, 6, 4), (6, 4, 1), (6, 4, 4)]
+
+
+@pytest.mark.parametrize("k,L,levelsup", STREAM_CASES)
 def test_chain_equals_oracle_on_a_stream(built, k, L, levelsup):
     """consecutive frames of one stream against a reference key frame that changes twice on the way (the graph of the chain
     does not depend on the key frame), flags that change from frame to frame, pageable / pinned / padded sources, both
@@ -216,3 +223,30 @@ def test_edge_cases(built):
         ex._chk(ex.L.orbfe_track_reference_keyframe(ex.h, None, W, voc.v, 2, res.h, None, 0.75, 1, None, None, None, None, None, None,
                                                     None, None, None), "orbfe_track_reference_keyframe")
     voc.close()
+
+
+def test_device_built_node_lists_forced_on_small_frames(built):
+    """The matcher of frames above 7168 keypoints (per-node frame lists built on the device in HBM instead of LDS) on the
+    C1 stream of the four vocabularies above and on the edge cases.  The switch that forces it (ORBFE_BOW_CSR) exists only
+    in the diagnostics build liborbfe_diag.so (`make diag`, -DORBFE_DIAG) -- the shipped library reads no such variable --
+    so this runs once in a child process that loads that build.  The build reports every launch of the HBM-list path on
+    stderr: the child must have taken it."""
+    import subprocess
+    import __graft_entry__ as g
+    g.build_variant("diag")
+    env = dict(os.environ, ORBFE_BOW_CSR="1", ORBFE_TEST_LIB="liborbfe_diag.so")
+    p = subprocess.run([sys.executable, os.path.abspath(__file__)], env=env, capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0 and "device-built node lists: 4 streams + edge cases exact" in p.stdout, p.stdout[-1000:] + p.stderr[-2000:]
+    caps = [int(c) for c in re.findall(r"bow_track_launch: node lists in HBM \(cap (\d+),", p.stderr)]
+    assert caps and max(caps) <= 7168, p.stderr[-2000:]  # frames that fit in LDS went through the HBM lists
+
+
+if __name__ == "__main__":  # child of test_device_built_node_lists_forced_on_small_frames
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "orb_slam3_v1.0_amd", "python"))
+    import orbfe
+    orbfe.LIB_PATH = os.path.join(orbfe.CSRC, os.environ["ORBFE_TEST_LIB"])
+    assert os.environ.get("ORBFE_BOW_CSR") == "1"
+    for case in STREAM_CASES:
+        test_chain_equals_oracle_on_a_stream(True, *case)
+    test_edge_cases(True)
+    print("device-built node lists: 4 streams + edge cases exact")

@@ -20,9 +20,10 @@ def nodes_of(kp):
     return ((kp["y"] // 40).astype(np.int32) * 8 + kp["octave"]).astype(np.int32)
 
 
-def neighbour(kp, desc, seed, consistent, stereo):
+def neighbour(kp, desc, seed, consistent, stereo, width=W, cx=367.215, cy=248.375, nodes=None):
     """a neighbour key frame of (kp, desc): most features re-observed (shifted, noisy, a few bits flipped), some strangers,
-    shuffled; vocabulary nodes follow the position, 5 % stray, 3 % of the features are in no node at all"""
+    shuffled; vocabulary nodes follow the position (nodes_of, or the caller's `nodes` of kp), 5 % stray, 3 % of the
+    features are in no node at all.  width / (cx, cy): image width and principal point of the camera (752 x 480 default)"""
     rng = np.random.default_rng(seed)
     n1 = len(kp)
     src = np.flatnonzero(rng.random(n1) < 0.8)
@@ -33,22 +34,22 @@ def neighbour(kp, desc, seed, consistent, stereo):
     d2 = np.stack([S.flip_bits(desc[s], int(rng.integers(0, 36)), rng) for s in src])
     extra = rng.integers(0, n1, n1 // 5)
     kpe = kp[extra].copy()
-    kpe["x"] = rng.uniform(10, W - 10, len(extra))
+    kpe["x"] = rng.uniform(10, width - 10, len(extra))
     kp2 = np.concatenate([kp2, kpe])
     d2 = np.concatenate([d2, rng.integers(0, 256, (len(extra), 32), dtype=np.uint8)])
     perm = rng.permutation(len(kp2))
     kp2, d2 = kp2[perm], d2[perm]
-    node1 = nodes_of(kp)
+    node1 = nodes_of(kp) if nodes is None else nodes
     node2 = np.concatenate([node1[src], rng.integers(0, node1.max() + 1, len(extra))])[perm].astype(np.int32)
     node2 = np.where(rng.random(len(node2)) < 0.05, rng.integers(0, node1.max() + 1, len(node2)), node2).astype(np.int32)
     node2[rng.random(len(node2)) < 0.03] = -1
     has2 = (rng.random(len(kp2)) < 0.3).astype(np.uint8)
     s2 = (rng.random(len(kp2)) < 0.4).astype(np.uint8) if stereo else None
     if consistent:
-        Kc = np.array([[458.654, 0, 367.215], [0, 457.296, 248.375], [0, 0, 1]])
+        Kc = np.array([[458.654, 0, cx], [0, 457.296, cy], [0, 0, 1]])
         tx = np.array([[0, 0, 0], [0, 0, -0.11], [0, 0.11, 0]])
         F12 = (np.linalg.inv(Kc).T @ tx @ np.linalg.inv(Kc)).astype(np.float32)
-        ep = (-5000.0, 248.0)
+        ep = (-5000.0, float(int(cy)))
     else:
         F12 = rng.normal(0, 1e-3, (3, 3)).astype(np.float32)
         F12[2, 2] = 0.3

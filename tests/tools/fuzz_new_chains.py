@@ -88,7 +88,7 @@ def one_fuse(rng, k):
     v = FS.fill_frustum(Fo, ON, seed=300 + k, kb8=kb8)
     FS.fill_frustum(Fp, PN, seed=300 + k, kb8=kb8)
     M = int(rng.choice([1, 50, 700, 2000, 5000]))
-    th = float(rng.choice([2.5, 3.0, 4.0, 8.0]))
+    th = float(rng.choice([2.5, 3.0, 4.0, 8.0, 10.0]))
     pts, mpd, u_right, inv_s2 = TF.scenario(kp, desc, e.scaleFactors, v, M, k, stereo)
     cols, rows = int(rng.integers(8, 200)), int(rng.integers(6, 120))
     fvo = O.make_frame_view(kp, desc, cols, rows, 0.0, 0.0, float(W), float(H), e.scaleFactors)
