@@ -712,6 +712,74 @@ int orbfe_track_initialization(orbfe_handle *h, const uint8_t *gray, int pitch, 
                                int *matches12_out, int *n_matches);
 
 /* -------------------------------------------------------------------------------------------
+ * Multi-device pool: the batched many-frame mode with host frames, sharded over several GPUs
+ * ---------------------------------------------------------------------------------------- */
+/* A pool owns N members.  Member k is a handle made from *params with device_id = devices[k] (params->device_id is ignored),
+ * plus one ring (orbfe_stream_*) of `slots` x `slot_frames`.  A device may appear more than once: two members on one GPU are
+ * two handles with two rings.  Each MI355X has its own host link, so host frames go faster only with more devices; the
+ * members' results travel down their own links straight into the caller's arrays, nothing is gathered through one device.
+ * Sharding: frame i belongs to the member k whose orbfe_shard_range block holds i.  Each member pushes its block through its
+ * own ring in chunks of slot_frames, on a worker thread of its own (one per member, made at create, joined at destroy):
+ * it submits until the ring is full, then collects the oldest submission into the caller's arrays at the frames' absolute
+ * offsets.  All members run at the same time; the calling thread sleeps until the last one is done.  A member whose block
+ * is empty does nothing.
+ * Outputs: exactly orbfe_extract_batch's layout with cap = orbfe_max_keypoints(orbfe_pool_member(p, 0)): frame i at
+ * kp_out + i*cap, desc_out + i*cap*32, n_out[i], per_level_counts + i*n_levels (per_level_counts may be NULL) and, for
+ * orbfe_pool_track, match_out + i*cap and n_matches[i].  Only the first n_out[i] entries of a frame are written.
+ * Results are byte-identical to the single-handle calls whatever the member count and whether or not devices repeat.
+ * Errors: argument errors are found on the calling thread before any member starts: ORBFE_ERR_INVALID_ARG, no output
+ * written, no GPU work done.  A runtime failure (a HIP error, device guard flags at collect) lets every member first wait
+ * for and drop what it submitted; the call then returns the status of the lowest-numbered failing member and
+ * orbfe_pool_last_error() reads "member k (device d): <orbfe_last_error of that member>".  The pool stays usable.
+ * Threading: one caller at a time per pool, as for a handle.  The calls are synchronous: source frames may be reused once
+ * a call has returned.  Sources as for the ring: pinned frames are read in place by DMA, pageable ones go through a pool of
+ * copy threads (max(1, 7 / n_devices) per member, so a pool takes no more threads than one ring). */
+typedef struct orbfe_pool orbfe_pool;
+
+/* host-only: the contiguous block [*lo, *hi) of n_frames that member k of n_members owns -- ceil(n_frames / n_members)
+ * frames each, the first members take the remainder and the last ones may be empty; the same arithmetic as shard_range()
+ * in python/orbfe/shard.py.  n_frames >= 0, 1 <= n_members, 0 <= k < n_members. */
+int orbfe_shard_range(int n_frames, int k, int n_members, int *lo, int *hi);
+
+/* 1 <= n_devices <= 16, 2 <= slots <= 64, 1 <= slot_frames <= params->max_batch.  A NULL pointer or a count or ordinal that
+ * is negative or out of range gives ORBFE_ERR_INVALID_ARG before any HIP call; no GPU at all gives ORBFE_ERR_NO_DEVICE; an
+ * ordinal >= the device count gives ORBFE_ERR_INVALID_ARG.  If a member fails to create, everything created so far is
+ * released and that member's status is returned. */
+int orbfe_pool_create(const orbfe_params *params, const int *devices, int n_devices, int slots, int slot_frames,
+                      orbfe_pool **out);
+/* joins the workers, then releases every member's ring, map and handle.  NULL is a no-op. */
+void orbfe_pool_destroy(orbfe_pool *p);
+int orbfe_pool_size(const orbfe_pool *p);
+/* member k's handle, borrowed: for the getters (orbfe_max_keypoints, scale tables, level info, orbfe_last_error).  Other
+ * calls on it only while the pool is idle; never orbfe_destroy it. */
+orbfe_handle *orbfe_pool_member(const orbfe_pool *p, int k);
+/* frames member k has processed since create */
+long long orbfe_pool_member_frames(const orbfe_pool *p, int k);
+/* message of the pool's last failing call ("" if none) */
+const char *orbfe_pool_last_error(const orbfe_pool *p);
+
+/* orbfe_extract_batch over n_frames (>= 1) host frames `pitch` bytes per row, any number of them (no max_batch limit). */
+int orbfe_pool_extract(orbfe_pool *p, const uint8_t *const *grays, int pitch, int n_frames,
+                       orbfe_keypoint *kp_out, uint8_t *desc_out, int *n_out, int *per_level_counts);
+
+/* one orbfe_map of map_capacity per member, and orbfe_stream_enable_track(max_points) on every ring.  Once per pool: a
+ * second call (or one while a pool call runs) gives ORBFE_ERR_INVALID_ARG.  Out of memory on any member releases what this
+ * call made and leaves the pool as it was; the call may be repeated. */
+int orbfe_pool_enable_track(orbfe_pool *p, int map_capacity, int max_points);
+/* orbfe_map_update of the same entries on every member's map, the members in parallel; returns when all of them are
+ * updated, so it is ordered before the next orbfe_pool_track.  ORBFE_ERR_INVALID_ARG before orbfe_pool_enable_track. */
+int orbfe_pool_map_update(orbfe_pool *p, int n, const int *ids, const orbfe_world_point *points, const uint8_t *desc);
+/* per frame i, what orbfe_track_frame_map(h, grays[i], pitch, &frusta[i], tp, map, n_points, ids + i*n_points, ...) gives
+ * on one handle whose map holds the same entries: frusta[i] is frame i's pose, ids[i*n_points ..] its local map points
+ * (id >= 0, ~id = skipped, outside the map = no point, as orbfe_stream_submit_track); n_points <= max_points.  Outputs as
+ * orbfe_pool_extract plus match_out + i*cap / n_matches[i] as orbfe_stream_collect_track.  ORBFE_ERR_INVALID_ARG before
+ * orbfe_pool_enable_track. */
+int orbfe_pool_track(orbfe_pool *p, const uint8_t *const *grays, int pitch, int n_frames, const orbfe_track_params *tp,
+                     const orbfe_frustum *frusta, int n_points, const int *ids,
+                     orbfe_keypoint *kp_out, uint8_t *desc_out, int *n_out, int *per_level_counts,
+                     int *match_out, int *n_matches);
+
+/* -------------------------------------------------------------------------------------------
  * Misc
  * ---------------------------------------------------------------------------------------- */
 const char *orbfe_status_string(int status);

@@ -638,6 +638,90 @@ private:
     orbfe_map* m_ = nullptr;
 };
 
+// The batched many-frame mode over several GPUs (orbfe_pool_*): member k is an extractor on devices[k] with a ring of
+// slots x slotFrames; the frames of a call are sharded in contiguous blocks (orbfe_shard_range) and the members run at the
+// same time.  Outputs are frame-major with the stride Cap(): frame i at kp[i*Cap()], desc[i*Cap()*32], n[i],
+// perLevel[i*Levels()], match[i*Cap()], nMatches[i]; the vectors are grown to fit.  Every frame of a call shares one pitch.
+class FramePool {
+public:
+    FramePool(const orbfe_params& params, const std::vector<int>& devices, int slots = 3, int slotFrames = 0)
+    {
+        const int rc = orbfe_pool_create(&params, devices.data(), (int)devices.size(), slots, slotFrames > 0 ? slotFrames : params.max_batch,
+                                         &p_);
+        check(rc, "orbfe_pool_create");
+        cap_ = orbfe_max_keypoints(orbfe_pool_member(p_, 0));
+        levels_ = orbfe_get_levels(orbfe_pool_member(p_, 0));
+    }
+    ~FramePool() { orbfe_pool_destroy(p_); }
+    FramePool(const FramePool&) = delete;
+    FramePool& operator=(const FramePool&) = delete;
+
+    int Size() const { return orbfe_pool_size(p_); }
+    int Cap() const { return cap_; }
+    int Levels() const { return levels_; }
+    const orbfe_handle* Member(int k) const { return orbfe_pool_member(p_, k); }
+    long long MemberFrames(int k) const { return orbfe_pool_member_frames(p_, k); }
+
+    void Extract(const std::vector<GrayImageView>& frames, std::vector<orbfe_keypoint>& kp, std::vector<uint8_t>& desc, std::vector<int>& n,
+                 std::vector<int>* perLevel = nullptr)
+    {
+        const std::vector<const uint8_t*> ptrs = pointers(frames);
+        size_outputs(ptrs.size(), kp, desc, n, perLevel);
+        check(orbfe_pool_extract(p_, ptrs.data(), frames[0].pitch, (int)ptrs.size(), kp.data(), desc.data(), n.data(),
+                                 perLevel ? perLevel->data() : nullptr),
+              "orbfe_pool_extract");
+    }
+
+    void EnableTrack(int mapCapacity, int maxPoints) { check(orbfe_pool_enable_track(p_, mapCapacity, maxPoints), "orbfe_pool_enable_track"); }
+    void MapUpdate(const std::vector<int>& ids, const std::vector<orbfe_world_point>& points, const std::vector<uint8_t>& desc)
+    {
+        if (points.size() < ids.size() || desc.size() < ids.size() * 32) throw std::invalid_argument("FramePool::MapUpdate: short arrays");
+        check(orbfe_pool_map_update(p_, (int)ids.size(), ids.data(), points.data(), desc.data()), "orbfe_pool_map_update");
+    }
+
+    // frusta[i]: frame i's pose; ids[i*nPoints ..]: its local map points by id (id >= 0, ~id = skipped, outside the map = none)
+    void Track(const std::vector<GrayImageView>& frames, const orbfe_track_params& tp, const std::vector<orbfe_frustum>& frusta, int nPoints,
+               const std::vector<int>& ids, std::vector<orbfe_keypoint>& kp, std::vector<uint8_t>& desc, std::vector<int>& n,
+               std::vector<int>& match, std::vector<int>& nMatches, std::vector<int>* perLevel = nullptr)
+    {
+        const std::vector<const uint8_t*> ptrs = pointers(frames);
+        const size_t N = ptrs.size();
+        if (frusta.size() < N || nPoints < 0 || ids.size() < N * (size_t)nPoints) throw std::invalid_argument("FramePool::Track: short arrays");
+        size_outputs(N, kp, desc, n, perLevel);
+        if (match.size() < N * cap_) match.resize(N * cap_);
+        if (nMatches.size() < N) nMatches.resize(N);
+        check(orbfe_pool_track(p_, ptrs.data(), frames[0].pitch, (int)N, &tp, frusta.data(), nPoints, ids.data(), kp.data(), desc.data(),
+                               n.data(), perLevel ? perLevel->data() : nullptr, match.data(), nMatches.data()),
+              "orbfe_pool_track");
+    }
+
+private:
+    void check(int rc, const char* where) const
+    {
+        if (rc != ORBFE_OK)
+            throw std::runtime_error(std::string(where) + ": " + orbfe_status_string(rc) + " " + (p_ ? orbfe_pool_last_error(p_) : ""));
+    }
+    static std::vector<const uint8_t*> pointers(const std::vector<GrayImageView>& frames)
+    {
+        if (frames.empty()) throw std::invalid_argument("FramePool: no frames");
+        std::vector<const uint8_t*> ptrs(frames.size());
+        for (size_t i = 0; i < frames.size(); i++) {
+            if (frames[i].pitch != frames[0].pitch) throw std::invalid_argument("FramePool: the frames of one call share one pitch");
+            ptrs[i] = frames[i].data;
+        }
+        return ptrs;
+    }
+    void size_outputs(size_t N, std::vector<orbfe_keypoint>& kp, std::vector<uint8_t>& desc, std::vector<int>& n, std::vector<int>* perLevel) const
+    {
+        if (kp.size() < N * cap_) kp.resize(N * cap_);
+        if (desc.size() < N * cap_ * 32) desc.resize(N * cap_ * 32);
+        if (n.size() < N) n.resize(N);
+        if (perLevel && perLevel->size() < N * levels_) perLevel->resize(N * levels_);
+    }
+    orbfe_pool* p_ = nullptr;
+    size_t cap_ = 0, levels_ = 0;
+};
+
 // ORBmatcher::Fuse(pKF, vpMapPoints, th) (src/ORBmatcher.cc:678-851) for LocalMapping::SearchInNeighbors
 // (src/LocalMapping.cc:764-860, calls at :822,:852) on RESIDENT data: the target key frame is a ResidentKeyFrame with SetGrid
 // done, the map points are entries of a ResidentMap (ids[i] = the entry of vpMapPoints[i]); a frustum and 4 bytes per map point

@@ -1333,6 +1333,13 @@ void orbfe_stream_destroy(orbfe_stream* st)
 
 int orbfe_stream_create(orbfe_handle* h, int slots, int slot_frames, orbfe_stream** out)
 {
+    return orbfe_stream_create_copy_threads(h, slots, slot_frames, 0, out);
+}
+
+}  // extern "C"
+
+int orbfe_stream_create_copy_threads(orbfe_handle* h, int slots, int slot_frames, int copy_threads, orbfe_stream** out)
+{
     if (!h || !out || slots < 2 || slots > 64 || slot_frames < 1 || slot_frames > h->maxBatch) return ORBFE_ERR_INVALID_ARG;
     *out = nullptr;
     std::lock_guard<std::mutex> lk(h->mu);
@@ -1372,11 +1379,45 @@ int orbfe_stream_create(orbfe_handle* h, int slots, int slot_frames, orbfe_strea
         return ORBFE_ERR_OUT_OF_MEMORY;
     }
     const unsigned hw = std::thread::hardware_concurrency();
-    st->pool = new RowCopyPool((int)std::min<unsigned>(7u, hw > 2 ? hw / 2 : 1));
+    st->pool = new RowCopyPool(copy_threads > 0 ? copy_threads : (int)std::min<unsigned>(7u, hw > 2 ? hw / 2 : 1));
     h->rings.push_back(st);
     *out = st;
     return ORBFE_OK;
 }
+
+// the slots' extract-and-match blocks and the map of orbfe_stream_enable_track: the ring is idle and serves plain submissions
+// again, and a later enable_track starts from empty slots
+void orbfe_stream_release_track(orbfe_stream* st)
+{
+    if (!st || !st->h) return;
+    orbfe_handle* h = st->h;
+    std::lock_guard<std::mutex> lk(h->mu);
+    (void)hipSetDevice(h->device);
+    for (auto& sl : st->slots) {
+        if (sl.hTrkIn) (void)hipHostFree(sl.hTrkIn);
+        if (sl.dTrkIn) (void)hipFree(sl.dTrkIn);
+        if (sl.dTrkWork) (void)hipFree(sl.dTrkWork);
+        if (sl.dTrkOut) (void)hipFree(sl.dTrkOut);
+        if (sl.hTrkOut) (void)hipHostFree(sl.hTrkOut);
+        sl.hTrkIn = sl.dTrkIn = sl.dTrkWork = sl.dTrkOut = sl.hTrkOut = nullptr;
+    }
+    st->map = nullptr;
+    st->maxPoints = 0;
+}
+
+// waits for everything the ring has in flight (errors ignored) and drops it uncollected
+void orbfe_stream_drain(orbfe_stream* st)
+{
+    if (!st || !st->h) return;
+    orbfe_handle* h = st->h;
+    (void)hipSetDevice(h->device);
+    for (hipStream_t s : {st->sIn, h->stream, st->sOut})
+        if (s) (void)hipStreamSynchronize(s);
+    (void)hipGetLastError();
+    st->collected.store(st->submitted.load(std::memory_order_acquire), std::memory_order_release);
+}
+
+extern "C" {
 
 int orbfe_stream_in_flight(const orbfe_stream* st)
 {

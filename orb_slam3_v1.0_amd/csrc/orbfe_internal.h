@@ -24,6 +24,14 @@ inline hipError_t memset_sync(void* dst, int value, size_t bytes, hipStream_t s)
     return e != hipSuccess ? e : hipStreamSynchronize(s);
 }
 
+// Host-side hooks of the ring (orbfe_host.cpp) for the multi-device pool (orbfe_pool.cpp).
+// orbfe_stream_create with `copy_threads` re-pitch threads (<= 0: the default of orbfe_stream_create).
+int orbfe_stream_create_copy_threads(orbfe_handle* h, int slots, int slot_frames, int copy_threads, orbfe_stream** out);
+// undoes orbfe_stream_enable_track on an idle ring (its slots' track blocks are freed, the map is detached)
+void orbfe_stream_release_track(orbfe_stream* st);
+// waits for every submission in flight and drops it uncollected (after a failed submit / collect)
+void orbfe_stream_drain(orbfe_stream* st);
+
 namespace orbfe {
 
 constexpr int kMaxLevels = ORBFE_MAX_LEVELS;

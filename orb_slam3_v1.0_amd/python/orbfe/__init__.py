@@ -122,6 +122,9 @@ SYMBOLS = [
     "orbfe_debug_clock_probe", "orbfe_keyframe_set_grid", "orbfe_fuse_search_keyframe",
     "orbfe_init_frame_create", "orbfe_init_frame_destroy", "orbfe_init_frame_size", "orbfe_track_initialization",
     "orbfe_set_stream_priority",
+    "orbfe_shard_range", "orbfe_pool_create", "orbfe_pool_destroy", "orbfe_pool_size", "orbfe_pool_member",
+    "orbfe_pool_member_frames", "orbfe_pool_last_error", "orbfe_pool_extract", "orbfe_pool_enable_track",
+    "orbfe_pool_map_update", "orbfe_pool_track",
 ]
 
 _lib = None
@@ -242,6 +245,21 @@ def lib():
     L.orbfe_last_error.argtypes = [vp]
     L.orbfe_last_error.restype = C.c_char_p
     L.orbfe_version.restype = C.c_char_p
+    L.orbfe_shard_range.argtypes = [ci, ci, ci, vp, vp]
+    L.orbfe_pool_create.argtypes = [C.POINTER(Params), vp, ci, ci, ci, C.POINTER(vp)]
+    L.orbfe_pool_destroy.argtypes = [vp]
+    L.orbfe_pool_destroy.restype = None
+    L.orbfe_pool_size.argtypes = [vp]
+    L.orbfe_pool_member.argtypes = [vp, ci]
+    L.orbfe_pool_member.restype = vp
+    L.orbfe_pool_member_frames.argtypes = [vp, ci]
+    L.orbfe_pool_member_frames.restype = C.c_longlong
+    L.orbfe_pool_last_error.argtypes = [vp]
+    L.orbfe_pool_last_error.restype = C.c_char_p
+    L.orbfe_pool_extract.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp]
+    L.orbfe_pool_enable_track.argtypes = [vp, ci, ci]
+    L.orbfe_pool_map_update.argtypes = [vp, ci, vp, vp, vp]
+    L.orbfe_pool_track.argtypes = [vp, vp, ci, ci, C.POINTER(TrackParams), vp, ci, vp, vp, vp, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -546,6 +564,119 @@ class ExtractStream:
 
         return (nf.value, view(kp, sf * cap * 24, KP_DTYPE, (sf, cap)), view(desc, sf * cap * 32, np.uint8, (sf, cap, 32)),
                 view(n, sf * 4, np.int32, (sf,)), view(per, sf * nl * 4, np.int32, (sf, nl)))
+
+
+def shard_range(n_frames, k, n_members):
+    """orbfe_shard_range: the block [lo, hi) of n_frames that member k of n_members owns (host only)."""
+    lo, hi = C.c_int(), C.c_int()
+    rc = lib().orbfe_shard_range(int(n_frames), int(k), int(n_members), C.byref(lo), C.byref(hi))
+    if rc != 0:
+        raise OrbfeError(rc, "orbfe_shard_range")
+    return lo.value, hi.value
+
+
+def _frame_ptrs(frames):
+    """[n][H][W] host frames (numpy, or a list of [H][W] arrays) -> (ctypes array of n row-0 addresses, row pitch)"""
+    if isinstance(frames, np.ndarray):
+        base, stride = frames.ctypes.data, frames.strides[0]
+        return (C.c_void_p * len(frames))(*[base + b * stride for b in range(len(frames))]), frames.strides[1]
+    return (C.c_void_p * len(frames))(*[f.ctypes.data for f in frames]), frames[0].strides[0]
+
+
+class Pool:
+    """orbfe_pool_*: the batched many-frame mode over several GPUs.  Member k is a handle on devices[k] (a device may repeat)
+    with a ring of `slots` x `slot_frames`; the frames of a call are sharded over the members in contiguous blocks
+    (shard_range) and every member runs its block through its own ring on a worker thread of its own.  Results are those of
+    one ORBextractor's extract_batch / one FrameTracker's TrackFrameMap, frame by frame."""
+
+    def __init__(self, args, devices, slots=3, slot_frames=None, max_batch=None):
+        self.L = lib()
+        self.h = None
+        max_batch = int(max_batch or slot_frames or 64)
+        self.slot_frames = int(slot_frames or max_batch)
+        self.W, self.H = int(args[6]), int(args[7])
+        prm = Params(*args, 0, max_batch)
+        devs = (C.c_int * len(devices))(*[int(d) for d in devices])
+        h = C.c_void_p()
+        rc = self.L.orbfe_pool_create(C.byref(prm), devs, len(devices), int(slots), self.slot_frames, C.byref(h))
+        if rc != 0:
+            raise OrbfeError(rc, "orbfe_pool_create")
+        self.h = h
+        self.size = self.L.orbfe_pool_size(self.h)
+        m0 = self.L.orbfe_pool_member(self.h, 0)
+        self.cap = self.L.orbfe_max_keypoints(m0)
+        self.nlevels = self.L.orbfe_get_levels(m0)
+        self._grid = None
+
+    def _chk(self, rc, where):
+        if rc != 0:
+            raise OrbfeError(rc, where, self.L.orbfe_pool_last_error(self.h).decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.orbfe_pool_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def member_frames(self):
+        return [self.L.orbfe_pool_member_frames(self.h, k) for k in range(self.size)]
+
+    def extract_raw(self, frames, pitch=None, out=None):
+        """orbfe_pool_extract into frame-major arrays (kp[n][cap], desc[n][cap][32], n[n], per[n][levels]); `out` reuses them"""
+        ptrs, p = _frame_ptrs(frames)
+        n = len(frames)
+        kp, desc, cnt, per = out if out is not None else (np.zeros((n, self.cap), KP_DTYPE), np.zeros((n, self.cap, 32), np.uint8),
+                                                          np.zeros(n, np.int32), np.zeros((n, self.nlevels), np.int32))
+        self._chk(self.L.orbfe_pool_extract(self.h, ptrs, int(pitch or p), n, _p(kp), _p(desc), _p(cnt), _p(per)), "orbfe_pool_extract")
+        return kp, desc, cnt, per
+
+    def extract(self, frames, pitch=None):
+        """per frame (kp, desc, per_level) as ORBextractor.extract_batch"""
+        kp, desc, n, per = self.extract_raw(frames, pitch)
+        return [(kp[b, :n[b]].copy(), desc[b, :n[b]].copy(), per[b].copy()) for b in range(len(n))]
+
+    def enable_track(self, capacity, max_points, gridCols, gridRows, minX, minY, maxX, maxY):
+        """one resident map of `capacity` entries per member; every ring takes up to max_points map points per frame"""
+        self._chk(self.L.orbfe_pool_enable_track(self.h, int(capacity), int(max_points)), "orbfe_pool_enable_track")
+        self._grid = (int(gridCols), int(gridRows), float(minX), float(minY),
+                      float(np.float32(gridCols) / np.float32(np.float32(maxX) - np.float32(minX))),
+                      float(np.float32(gridRows) / np.float32(np.float32(maxY) - np.float32(minY))))
+
+    def map_update(self, ids, points, desc):
+        ids = np.ascontiguousarray(ids, np.int32)
+        points = np.ascontiguousarray(points, WP_DTYPE)
+        desc = np.ascontiguousarray(desc, np.uint8)
+        assert len(ids) == len(points) == len(desc)
+        self._chk(self.L.orbfe_pool_map_update(self.h, len(ids), _p(ids), _p(points), _p(desc)), "orbfe_pool_map_update")
+
+    def track_params(self, th, nnRatio, bFarPoints=False, thFarPoints=0.0):
+        tp = TrackParams()
+        if self._grid is not None:
+            (tp.grid_cols, tp.grid_rows, tp.min_x, tp.min_y, tp.grid_inv_w, tp.grid_inv_h) = self._grid
+        tp.th, tp.nn_ratio, tp.far_points, tp.th_far_points = th, nnRatio, int(bFarPoints), thFarPoints
+        return tp
+
+    def track_raw(self, frames, frusta, ids, tp, pitch=None, out=None):
+        """orbfe_pool_track into frame-major arrays (kp, desc, n, per, match[n][cap], nmatch[n])"""
+        ptrs, p = _frame_ptrs(frames)
+        n = len(frames)
+        if not isinstance(frusta, C.Array):
+            frusta = (Frustum * n)(*frusta)
+        ids = np.ascontiguousarray(ids, np.int32)
+        assert ids.ndim == 2 and ids.shape[0] == n
+        kp, desc, cnt, per, match, nm = out if out is not None else (
+            np.zeros((n, self.cap), KP_DTYPE), np.zeros((n, self.cap, 32), np.uint8), np.zeros(n, np.int32),
+            np.zeros((n, self.nlevels), np.int32), np.full((n, self.cap), -1, np.int32), np.zeros(n, np.int32))
+        self._chk(self.L.orbfe_pool_track(self.h, ptrs, int(pitch or p), n, C.byref(tp), frusta, ids.shape[1], _p(ids), _p(kp), _p(desc),
+                                          _p(cnt), _p(per), _p(match), _p(nm)), "orbfe_pool_track")
+        return kp, desc, cnt, per, match, nm
+
+    def track(self, frames, frusta, ids, th, nnRatio, bFarPoints=False, thFarPoints=0.0, pitch=None):
+        """per frame (kp, desc, per_level, match, n_matches) as ExtractStream.collect_track; frusta: one Frustum per frame,
+        ids: [n][n_points] int32 (id >= 0, ~id = skipped, outside the map = no point)"""
+        kp, desc, n, per, match, nm = self.track_raw(frames, frusta, ids, self.track_params(th, nnRatio, bFarPoints, thFarPoints), pitch)
+        return [(kp[b, :n[b]].copy(), desc[b, :n[b]].copy(), per[b].copy(), match[b, :n[b]].copy(), int(nm[b])) for b in range(len(n))]
 
 
 class ORBmatcher:
