@@ -508,6 +508,62 @@ int orbfe_match_triangulation_batch(orbfe_handle *h, const orbfe_keyframe *kf1, 
 int orbfe_triangulation_select(int n1, const int *raw_match12, const uint8_t *raw_bin, const uint8_t *has_mp1_now,
                                int check_orientation, int *matches12_out, int *n_matches);
 
+/* -------------------------------------------------------------------------------------------
+ * The second loop of LocalMapping::CreateNewMapPoints: "triangulate each match" (src/LocalMapping.cc:501-705)
+ * ---------------------------------------------------------------------------------------- */
+/* verdict of one pair, in the order of the reference's gates (SPEC DECISION S11) */
+#define ORBFE_NEWPT_ACCEPTED        0   /* a new map point at x3d */
+#define ORBFE_NEWPT_LOW_PARALLAX    1   /* cosParallaxRays <= 0 or >= 0.9998 (0.9996 inertial), :596,:615-618; no point */
+#define ORBFE_NEWPT_AT_INFINITY     2   /* x3Dh(3) == 0, src/GeometricTools.cc:59; no point */
+#define ORBFE_NEWPT_BEHIND_1        3   /* z1 <= 0, :627-629 */
+#define ORBFE_NEWPT_BEHIND_2        4   /* z2 <= 0, :631-633 */
+#define ORBFE_NEWPT_REPROJECTION_1  5   /* reprojection error in key frame 1 above 5.991 sigma^2, :643-648 */
+#define ORBFE_NEWPT_REPROJECTION_2  6   /* ... in key frame 2, :670-674 */
+#define ORBFE_NEWPT_ZERO_DISTANCE   7   /* dist1 == 0 || dist2 == 0, :695 */
+#define ORBFE_NEWPT_FAR             8   /* mbFarPoints && (dist1 >= mThFarPoints || dist2 >= mThFarPoints), :698 */
+#define ORBFE_NEWPT_SCALE           9   /* scale consistency, :701-705 */
+#define ORBFE_NEWPT_NO_PARTNER      255 /* the batch search found no partner for this feature; no point */
+
+/* what the triangulation loop reads besides the two key frames' keypoints and scale factors, for ONE pair (key frame 1,
+ * neighbour).  Monocular key frames only (mvuRight < 0, NLeft == -1, no mpCamera2: bStereo1 == bStereo2 == bRight2 == false).
+ * Versioned by struct_size like orbfe_tri_params. */
+typedef struct orbfe_newpoint_params {
+    int struct_size;         /* sizeof(orbfe_newpoint_params) at the caller's compile time */
+    float tcw1[12];          /* GetPose().matrix3x4() of key frame 1, row-major 3 x 4 (eigTcw1, :432-436) */
+    float tcw2[12];          /* ... of the neighbour (eigTcw2, :490-494) */
+    float twc1[3], twc2[3];  /* GetTranslationInverse() of the two key frames (:440,:464): taken as given, not recomputed */
+    int camera_model1;       /* ORBFE_CAMERA_* of pKF1->mpCamera / pKF2->mpCamera */
+    int camera_model2;
+    float cam1[8], cam2[8];  /* fx fy cx cy k1 k2 k3 k4 */
+    float kb_precision;      /* KannalaBrandt8::precision */
+    float level_sigma2_1[ORBFE_MAX_LEVELS]; /* mpCurrentKeyFrame->mvLevelSigma2 */
+    float level_sigma2_2[ORBFE_MAX_LEVELS]; /* pKF2->mvLevelSigma2 */
+    float ratio_factor;      /* 1.5f * mpCurrentKeyFrame->mfScaleFactor (:447) */
+    int inertial;            /* mbInertial: parallax limit 0.9996 instead of 0.9998 (:597) */
+    int far_points;          /* mbFarPoints */
+    float th_far_points;     /* mThFarPoints */
+} orbfe_newpoint_params;
+#define ORBFE_NEWPOINT_PARAMS_INIT {(int)sizeof(orbfe_newpoint_params)}
+
+/* orbfe_match_triangulation_batch + the geometry of src/LocalMapping.cc:571-705 for EVERY raw partner, in the same
+ * submission (one upload, two launches back to back, one download, one synchronisation).  Arguments up to raw_bin as
+ * orbfe_match_triangulation_batch (same bytes come back); np_params[k] describes the pair (kf1, kf2[k]).
+ * verdict_out[k * n1 + i1] = ORBFE_NEWPT_* of the pair (i1, raw_match12[k * n1 + i1]); x3d_out[(k * n1 + i1) * 3 ..] = x3D of
+ * that pair (three zeros where no point exists: verdicts 1, 2 and 255).  The verdict and the point of a pair depend only on
+ * the two keypoints, the two poses and the two cameras, so the caller walks the neighbours in order, takes
+ * orbfe_triangulation_select's matches with the flags as they stand and looks the verdict up: exactly the reference's loop.
+ * A key frame created with stereo flags -> ORBFE_ERR_UNSUPPORTED (the stereo branches are not built).  HOST pointers
+ * except the key frames. */
+int orbfe_create_new_points_batch(orbfe_handle *h, const orbfe_keyframe *kf1, const uint8_t *has_mp1, int K,
+                                  const orbfe_keyframe *const *kf2, const uint8_t *const *has_mp2,
+                                  const orbfe_tri_params *tri_params, const orbfe_newpoint_params *np_params,
+                                  int *raw_match12, uint8_t *raw_bin, float *x3d_out, uint8_t *verdict_out);
+/* the geometry alone for n_pairs explicit pairs (idx1[p] in kf1, idx2[p] in kf2) of two resident key frames:
+ * x3d_out[3 * p ..], verdict_out[p].  An index out of range -> ORBFE_ERR_INVALID_ARG.  HOST pointers. */
+int orbfe_triangulate_pairs(orbfe_handle *h, const orbfe_keyframe *kf1, const orbfe_keyframe *kf2,
+                            const orbfe_newpoint_params *np_params, int n_pairs, const int *idx1, const int *idx2,
+                            float *x3d_out, uint8_t *verdict_out);
+
 /* replaces the search part of ORBmatcher::Fuse(pKF, vpMapPoints, th, bRight = false)
  * (src/ORBmatcher.cc:678-836; callers src/LocalMapping.cc:822,852): per map point the projection into the
  * key frame, KeyFrame::IsInImage, PredictScale, KeyFrame::GetFeaturesInArea (src/KeyFrame.cc:790-833), the

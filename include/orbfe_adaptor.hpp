@@ -818,6 +818,82 @@ private:
     std::vector<uint8_t> bin_;
 };
 
+// The whole neighbour loop of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:453-725) with ONE submission: the K
+// SearchForTriangulation calls (:488) AND "triangulate each match" (:501-705) for every raw partner of every neighbour
+// (orbfe_create_new_points_batch, SPEC DECISION S11; monocular key frames).  Construct it before the loop -- prm[k] as for
+// TriangulationBatch, geo[k] = the poses, cameras, sigma tables and the three LocalMapping settings of the pair (pKF1,
+// neighbour k), see orbfe_newpoint_params -- and inside the loop, in place of :488-705, call Points(k, pKF1, out): the
+// (idx1, idx2, x3D) of the map points the reference would create for neighbour k, in the order it creates them (ascending
+// idx1), given the map points pKF1 has NOW.  The caller keeps what touches the map: make_shared<MapPoint>(x3D, ...),
+// AddObservation / AddMapPoint / ComputeDistinctiveDescriptors / UpdateDepth / AddMapPoint (:708-723) -- pKF1->AddMapPoint
+// BEFORE the next Points call, that is what the later neighbours see --, the baseline test (:463-482: skip the Points call
+// for that neighbour) and CheckNewKeyFrames() (:455).
+struct NewPoint {
+    size_t idx1, idx2;
+    float x3D[3];
+};
+
+class NewMapPointsBatch {
+public:
+    template <class KeyFramePtr>
+    NewMapPointsBatch(orbfe_handle* h, KeyFramePtr pKF1, const ResidentKeyFrame& r1, const std::vector<KeyFramePtr>& vpNeighKFs,
+                      const std::vector<const ResidentKeyFrame*>& r2, const std::vector<orbfe_tri_params>& prm,
+                      const std::vector<orbfe_newpoint_params>& geo)
+        : n1_(pKF1->N), check_(prm.empty() ? 1 : prm[0].check_orientation)
+    {
+        const int K = (int)vpNeighKFs.size();
+        std::vector<uint8_t> has1(n1_ > 0 ? n1_ : 1);
+        for (int i = 0; i < n1_; i++) has1[i] = pKF1->GetMapPoint(i) ? 1 : 0;
+        std::vector<std::vector<uint8_t>> has2(K);
+        std::vector<const uint8_t*> has2p(K);
+        std::vector<const orbfe_keyframe*> kf2(K);
+        for (int k = 0; k < K; k++) {
+            const int n2 = vpNeighKFs[k]->N;
+            has2[k].resize(n2 > 0 ? n2 : 1);
+            for (int i = 0; i < n2; i++) has2[k][i] = vpNeighKFs[k]->GetMapPoint(i) ? 1 : 0;
+            has2p[k] = has2[k].data();
+            kf2[k] = r2[k]->get();
+        }
+        const size_t cells = (size_t)(K > 0 ? K : 1) * (n1_ > 0 ? n1_ : 1);
+        raw_.assign(cells, -1);
+        bin_.assign(cells, 0);
+        verdict_.assign(cells, ORBFE_NEWPT_NO_PARTNER);
+        x3d_.assign(cells * 3, 0.0f);
+        orbfe_detail::check(orbfe_create_new_points_batch(h, r1.get(), has1.data(), K, kf2.data(), has2p.data(), prm.data(), geo.data(),
+                                                          raw_.data(), bin_.data(), x3d_.data(), verdict_.data()), h,
+                            "orbfe_create_new_points_batch");
+    }
+
+    // the new map points of neighbour k; returns how many matches the k-th SearchForTriangulation call had (nmatches, :502)
+    template <class KeyFramePtr>
+    int Points(int k, KeyFramePtr pKF1, std::vector<NewPoint>& out) const
+    {
+        std::vector<uint8_t> now(n1_ > 0 ? n1_ : 1);
+        for (int i = 0; i < n1_; i++) now[i] = pKF1->GetMapPoint(i) ? 1 : 0;
+        std::vector<int> m12(n1_ > 0 ? n1_ : 1);
+        int nmatches = 0;
+        const size_t base = (size_t)k * n1_;
+        orbfe_detail::check(orbfe_triangulation_select(n1_, raw_.data() + base, bin_.data() + base, now.data(), check_, m12.data(), &nmatches),
+                            nullptr, "orbfe_triangulation_select");
+        out.clear();
+        for (int i = 0; i < n1_; i++) {
+            if (m12[i] < 0 || verdict_[base + i] != ORBFE_NEWPT_ACCEPTED) continue;
+            const float* x = &x3d_[(base + i) * 3];
+            out.push_back(NewPoint{(size_t)i, (size_t)m12[i], {x[0], x[1], x[2]}});
+        }
+        return nmatches;
+    }
+
+    // ORBFE_NEWPT_* of (neighbour k, feature idx1 of key frame 1) -- why a match did not become a point
+    int Verdict(int k, size_t idx1) const { return verdict_[(size_t)k * n1_ + idx1]; }
+
+private:
+    int n1_, check_;
+    std::vector<int> raw_;
+    std::vector<uint8_t> bin_, verdict_;
+    std::vector<float> x3d_;
+};
+
 // The isInFrustum loop of Tracking::SearchLocalPoints (src/Tracking.cc:1059-1077) for all local map points in one
 // launch.  `frustum` carries what Frame::isInFrustum reads from the frame (GetRcw / GetTcw / GetTwc, image bounds,
 // pinhole intrinsics, mbf, mfLogScaleFactor, mnScaleLevels); `MapPoint` needs GetWorldPos() (indexable [0..2]),

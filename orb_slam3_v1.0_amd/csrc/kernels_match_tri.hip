@@ -127,10 +127,15 @@ __device__ inline void sym4_min_eigenvector(double (&M)[4][4], double (&vOut)[4]
                 }
             }
     }
-    int m = 0;
-    for (int i = 1; i < 4; i++)
-        if (M[i][i] < M[m][m]) m = i;
-    for (int k = 0; k < 4; k++) vOut[k] = V[k][m];
+    // column of the smallest diagonal entry, lowest index on ties (selects instead of a run-time column index: the arrays
+    // stay in registers)
+    double best = M[0][0];
+    for (int k = 0; k < 4; k++) vOut[k] = V[k][0];
+    for (int i = 1; i < 4; i++) {
+        const bool less = M[i][i] < best;
+        best = less ? M[i][i] : best;
+        for (int k = 0; k < 4; k++) vOut[k] = less ? V[k][i] : vOut[k];
+    }
 }
 
 __device__ inline bool kb8_epipolar(const CamP& C1, const CamP& C2, float precision, float u1, float v1, float u2, float v2,
@@ -412,6 +417,148 @@ __global__ __launch_bounds__(256) void tri_batch_kernel(const TriNeighbour* __re
     rawBin[(size_t)k * n1 + idx1] = (uint8_t)bin;
 }
 
+// ---------------------------------------------------------------------------------------------
+// "Triangulate each match" of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:571-705) for monocular key frames
+// (bStereo1 == bStereo2 == bRight2 == false: the stereo branches :583-586,603-614,651-661,676-686 are unreachable), and
+// GeometricTools::Triangulate (src/GeometricTools.cc:47-66).  SPEC DECISION S11: binary32, one operation per line, left to
+// right, no contraction; comparisons against the reference's double literals in binary64 on the promoted float; the null
+// vector of A by the S10 sequence (sym4_min_eigenvector on A^T A in binary64).  The verdict and the point of a pair depend
+// only on the two keypoints, the two poses and the two cameras, so every raw partner of every neighbour is evaluated at
+// once and orbfe_triangulation_select's replay only looks the result up.
+// ---------------------------------------------------------------------------------------------
+struct NewPtNeighbour {  // device-side geometry block of one (key frame 1, neighbour) pair
+    const orbfe_keypoint* kp2;
+    const float* sf2;
+    float tcw1[12], tcw2[12];  // row-major 3 x 4
+    float twc1[3], twc2[3];
+    int model1, model2;
+    float cam1[8], cam2[8], kbPrecision;
+    float sigma2_1[kMaxLevels], sigma2_2[kMaxLevels];
+    float ratioFactor;
+    int inertial, farPoints;
+    float thFar;
+};
+
+__device__ inline int newpoint_eval(const NewPtNeighbour& G, const orbfe_keypoint& k1, const orbfe_keypoint& k2,
+                                    const float* __restrict__ sf1, float& X, float& Y, float& Z)
+{
+    const float (&T1)[12] = G.tcw1;
+    const float (&T2)[12] = G.tcw2;
+    const CamP C1 = cam_of(G.cam1, G.model1), C2 = cam_of(G.cam2, G.model2);
+    X = 0.0f; Y = 0.0f; Z = 0.0f;
+    float x1, y1, x2, y2;
+    cam_unproject(C1, G.kbPrecision, k1.x, k1.y, x1, y1);  // xn = (x, y, 1), :572-573
+    cam_unproject(C2, G.kbPrecision, k2.x, k2.y, x2, y2);
+    // ray = Rwc xn with Rwc = Rcw^T (:575-576)
+    const float r1x = (T1[0] * x1 + T1[4] * y1) + T1[8] * 1.0f;
+    const float r1y = (T1[1] * x1 + T1[5] * y1) + T1[9] * 1.0f;
+    const float r1z = (T1[2] * x1 + T1[6] * y1) + T1[10] * 1.0f;
+    const float r2x = (T2[0] * x2 + T2[4] * y2) + T2[8] * 1.0f;
+    const float r2y = (T2[1] * x2 + T2[5] * y2) + T2[9] * 1.0f;
+    const float r2z = (T2[2] * x2 + T2[6] * y2) + T2[10] * 1.0f;
+    const float dot = (r1x * r2x + r1y * r2y) + r1z * r2z;
+    const float n1 = sqrtf((r1x * r1x + r1y * r1y) + r1z * r1z);
+    const float n2 = sqrtf((r2x * r2x + r2y * r2y) + r2z * r2z);
+    const float cosParallax = dot / (n1 * n2);  // :577
+    const double limit = G.inertial ? 0.9996 : 0.9998;
+    if (!(cosParallax > 0.0f && (double)cosParallax < limit)) return ORBFE_NEWPT_LOW_PARALLAX;  // :596-597, :615-618
+    // GeometricTools::Triangulate (src/GeometricTools.cc:49-53)
+    float A[4][4];
+    for (int j = 0; j < 4; j++) {
+        A[0][j] = x1 * T1[8 + j] - T1[j];
+        A[1][j] = y1 * T1[8 + j] - T1[4 + j];
+        A[2][j] = x2 * T2[8 + j] - T2[j];
+        A[3][j] = y2 * T2[8 + j] - T2[4 + j];
+    }
+    double M[4][4], vv[4];
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) {
+            double acc = 0.0;
+            for (int k = 0; k < 4; k++) acc = acc + (double)A[k][i] * (double)A[k][j];
+            M[i][j] = acc;
+        }
+    sym4_min_eigenvector(M, vv);
+    if (vv[3] == 0.0) return ORBFE_NEWPT_AT_INFINITY;  // :59
+    X = (float)(vv[0] / vv[3]);
+    Y = (float)(vv[1] / vv[3]);
+    Z = (float)(vv[2] / vv[3]);
+    const float z1 = ((T1[8] * X + T1[9] * Y) + T1[10] * Z) + T1[11];  // :627
+    if (!(z1 > 0.0f)) return ORBFE_NEWPT_BEHIND_1;  // NaN fails (S10)
+    const float z2 = ((T2[8] * X + T2[9] * Y) + T2[10] * Z) + T2[11];  // :631
+    if (!(z2 > 0.0f)) return ORBFE_NEWPT_BEHIND_2;
+    const float xc1 = ((T1[0] * X + T1[1] * Y) + T1[2] * Z) + T1[3];  // :637-638
+    const float yc1 = ((T1[4] * X + T1[5] * Y) + T1[6] * Z) + T1[7];
+    float pu, pv;
+    camera_project(C1, xc1, yc1, z1, pu, pv);  // :643
+    const float e1x = pu - k1.x, e1y = pv - k1.y;
+    if ((double)(e1x * e1x + e1y * e1y) > 5.991 * (double)G.sigma2_1[k1.octave]) return ORBFE_NEWPT_REPROJECTION_1;  // :647
+    const float xc2 = ((T2[0] * X + T2[1] * Y) + T2[2] * Z) + T2[3];  // :665-666
+    const float yc2 = ((T2[4] * X + T2[5] * Y) + T2[6] * Z) + T2[7];
+    camera_project(C2, xc2, yc2, z2, pu, pv);  // :670
+    const float e2x = pu - k2.x, e2y = pv - k2.y;
+    if ((double)(e2x * e2x + e2y * e2y) > 5.991 * (double)G.sigma2_2[k2.octave]) return ORBFE_NEWPT_REPROJECTION_2;  // :673
+    // scale consistency (:689-705)
+    const float d1x = X - G.twc1[0], d1y = Y - G.twc1[1], d1z = Z - G.twc1[2];
+    const float dist1 = sqrtf((d1x * d1x + d1y * d1y) + d1z * d1z);
+    const float d2x = X - G.twc2[0], d2y = Y - G.twc2[1], d2z = Z - G.twc2[2];
+    const float dist2 = sqrtf((d2x * d2x + d2y * d2y) + d2z * d2z);
+    if (dist1 == 0.0f || dist2 == 0.0f) return ORBFE_NEWPT_ZERO_DISTANCE;  // :695
+    if (G.farPoints && (dist1 >= G.thFar || dist2 >= G.thFar)) return ORBFE_NEWPT_FAR;  // :698
+    const float ratioDist = dist2 / dist1;
+    const float ratioOctave = sf1[k1.octave] / G.sf2[k2.octave];
+    if (ratioDist * G.ratioFactor < ratioOctave || ratioDist > ratioOctave * G.ratioFactor) return ORBFE_NEWPT_SCALE;  // :704
+    return ORBFE_NEWPT_ACCEPTED;
+}
+
+// One thread per (neighbour blockIdx.y, entry): entry = feature i1 of key frame 1 with partner[k * n + i1] (the raw matches of
+// tri_batch_kernel, launched behind it on the same stream), or, with idx1List, pair p = (idx1List[p], partner[p]) of an
+// explicit list.  The chain is ~48 dependent binary64 Jacobi rotations: latency, not throughput, so blocks are one wave wide
+// to spread the entries with a partner over as many CUs as there are.
+__global__ __launch_bounds__(64) void newpoints_kernel(const NewPtNeighbour* __restrict__ nbs, int n,
+                                                       const orbfe_keypoint* __restrict__ kp1, const float* __restrict__ sf1,
+                                                       const int* __restrict__ idx1List, const int* __restrict__ partner,
+                                                       float* __restrict__ x3d, uint8_t* __restrict__ verdict)
+{
+    const int k = blockIdx.y;
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    if (e >= n) return;
+    const NewPtNeighbour& G = nbs[k];
+    const size_t o = (size_t)k * n + e;
+    const int i2 = partner[o];
+    float X = 0.0f, Y = 0.0f, Z = 0.0f;
+    int v = ORBFE_NEWPT_NO_PARTNER;
+    if (i2 >= 0) {
+        const int i1 = idx1List ? idx1List[e] : e;
+        const orbfe_keypoint k1 = kp1[i1];
+        const orbfe_keypoint k2 = G.kp2[i2];
+        v = newpoint_eval(G, k1, k2, sf1, X, Y, Z);  // (0, 0, 0) where no point exists
+    }
+    x3d[3 * o] = X;
+    x3d[3 * o + 1] = Y;
+    x3d[3 * o + 2] = Z;
+    verdict[o] = (uint8_t)v;
+}
+
+void fill_newpt(NewPtNeighbour& G, const KeyFrameDev* F2, const orbfe_newpoint_params& Q)
+{
+    G.kp2 = F2->kp;
+    G.sf2 = F2->sf;
+    for (int i = 0; i < 12; i++) { G.tcw1[i] = Q.tcw1[i]; G.tcw2[i] = Q.tcw2[i]; }
+    for (int i = 0; i < 3; i++) { G.twc1[i] = Q.twc1[i]; G.twc2[i] = Q.twc2[i]; }
+    G.model1 = Q.camera_model1;
+    G.model2 = Q.camera_model2;
+    for (int i = 0; i < 8; i++) { G.cam1[i] = Q.cam1[i]; G.cam2[i] = Q.cam2[i]; }
+    G.kbPrecision = Q.kb_precision;
+    for (int i = 0; i < kMaxLevels; i++) { G.sigma2_1[i] = Q.level_sigma2_1[i]; G.sigma2_2[i] = Q.level_sigma2_2[i]; }
+    G.ratioFactor = Q.ratio_factor;
+    G.inertial = Q.inertial;
+    G.farPoints = Q.far_points;
+    G.thFar = Q.th_far_points;
+}
+
+const char* const kNewPtSizeErr =
+    "orbfe_newpoint_params.struct_size does not match this library (rebuild the caller against include/orbfe.h)";
+
 }  // namespace
 
 int match_triangulation_run(MatchScratch& m, hipStream_t s, int G, const int* off1, const int* idx1, const int* off2,
@@ -615,27 +762,40 @@ void keyframe_destroy(KeyFrameDev* K)
 
 int match_triangulation_batch_run(MatchScratch& m, hipStream_t s, const KeyFrameDev* kf1, const uint8_t* hasMP1, int K,
                                   const KeyFrameDev* const* kf2, const uint8_t* const* hasMP2, const orbfe_tri_params* P,
-                                  int* rawMatch, uint8_t* rawBin, std::string& err)
+                                  int* rawMatch, uint8_t* rawBin, std::string& err, const orbfe_newpoint_params* NP, float* x3d,
+                                  uint8_t* verdict)
 {
     const int n1 = kf1->n;
-    if (K == 0 || n1 == 0) return ORBFE_OK;
+    if (!NP && (K == 0 || n1 == 0)) return ORBFE_OK;
     for (int k = 0; k < K; k++) {
         if (!kf2[k] || (!hasMP2[k] && kf2[k]->n > 0)) return ORBFE_ERR_INVALID_ARG;
         if (P[k].struct_size != (int)sizeof(orbfe_tri_params)) {
             err = "orbfe_tri_params.struct_size does not match this library (rebuild the caller against include/orbfe.h)";
             return ORBFE_ERR_INVALID_ARG;
         }
+        if (NP && NP[k].struct_size != (int)sizeof(orbfe_newpoint_params)) {
+            err = kNewPtSizeErr;
+            return ORBFE_ERR_INVALID_ARG;
+        }
+        if (NP && (kf1->hasStereo || kf2[k]->hasStereo)) {
+            err = "orbfe_create_new_points_batch: monocular key frames only (the stereo branches of CreateNewMapPoints are not built)";
+            return ORBFE_ERR_UNSUPPORTED;
+        }
     }
+    if (K == 0 || n1 == 0) return ORBFE_OK;
     // one pinned block up: [argument blocks | has_mp1 | has_mp2 of every neighbour]; one block down: [raw match | raw bin]
     Carver in;
     const size_t oArgs = in.take((size_t)K * sizeof(TriNeighbour));
     const size_t oH1 = in.take((size_t)n1);
     std::vector<size_t> oH2((size_t)K);
     for (int k = 0; k < K; k++) oH2[(size_t)k] = in.take((size_t)std::max(kf2[k]->n, 1));
+    const size_t oGeo = NP ? in.take((size_t)K * sizeof(NewPtNeighbour)) : 0;
     const size_t inBytes = in.off;
     Carver sc = in;
     const size_t oMatch = sc.take((size_t)K * n1 * sizeof(int));
     const size_t oBin = sc.take((size_t)K * n1);
+    const size_t oVerdict = NP ? sc.take((size_t)K * n1) : 0;
+    const size_t oX3d = NP ? sc.take((size_t)K * n1 * 3 * sizeof(float)) : 0;
     const size_t outBytes = sc.off - oMatch;
     int rc = ensure(m, sc.off, inBytes + outBytes + 256, err);
     if (rc != ORBFE_OK) return rc;
@@ -661,16 +821,69 @@ int match_triangulation_batch_run(MatchScratch& m, hipStream_t s, const KeyFrame
         for (int i = 0; i < 9; i++) A.R12[i] = Q.r12[i];
         for (int i = 0; i < 3; i++) A.t12[i] = Q.t12[i];
         for (int i = 0; i < kMaxLevels; i++) A.sigma2_1[i] = Q.level_sigma2_1[i];
+        if (NP) fill_newpt(reinterpret_cast<NewPtNeighbour*>(hp + oGeo)[k], F, NP[k]);
     }
     MCHK(hipMemcpyAsync(dp, hp, inBytes, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(tri_batch_kernel, dim3((n1 + 255) / 256, K), dim3(256), 0, s, reinterpret_cast<const TriNeighbour*>(dp + oArgs), n1,
                        kf1->kp, kf1->desc, kf1->node, kf1->stereo, dp + oH1, reinterpret_cast<int*>(dp + oMatch), dp + oBin);
+    if (NP)  // every raw partner's geometry, behind the search on the same stream: one submission, one download
+        hipLaunchKernelGGL(newpoints_kernel, dim3((n1 + 63) / 64, K), dim3(64), 0, s, reinterpret_cast<const NewPtNeighbour*>(dp + oGeo), n1,
+                           kf1->kp, kf1->sf, static_cast<const int*>(nullptr), reinterpret_cast<const int*>(dp + oMatch),
+                           reinterpret_cast<float*>(dp + oX3d), dp + oVerdict);
     MCHK(hipGetLastError());
     uint8_t* hOut = hp + inBytes;
     MCHK(hipMemcpyAsync(hOut, dp + oMatch, outBytes, hipMemcpyDeviceToHost, s));
     MCHK(hipStreamSynchronize(s));
     memcpy(rawMatch, hOut, (size_t)K * n1 * sizeof(int));
     memcpy(rawBin, hOut + (oBin - oMatch), (size_t)K * n1);
+    if (NP) {
+        memcpy(verdict, hOut + (oVerdict - oMatch), (size_t)K * n1);
+        memcpy(x3d, hOut + (oX3d - oMatch), (size_t)K * n1 * 3 * sizeof(float));
+    }
+    return ORBFE_OK;
+}
+
+int triangulate_pairs_run(MatchScratch& m, hipStream_t s, const KeyFrameDev* kf1, const KeyFrameDev* kf2,
+                          const orbfe_newpoint_params* NP, int nPairs, const int* idx1, const int* idx2, float* x3d, uint8_t* verdict,
+                          std::string& err)
+{
+    if (NP->struct_size != (int)sizeof(orbfe_newpoint_params)) {
+        err = kNewPtSizeErr;
+        return ORBFE_ERR_INVALID_ARG;
+    }
+    if (kf1->hasStereo || kf2->hasStereo) {
+        err = "orbfe_triangulate_pairs: monocular key frames only (the stereo branches of CreateNewMapPoints are not built)";
+        return ORBFE_ERR_UNSUPPORTED;
+    }
+    for (int p = 0; p < nPairs; p++)
+        if (idx1[p] < 0 || idx1[p] >= kf1->n || idx2[p] < 0 || idx2[p] >= kf2->n) return ORBFE_ERR_INVALID_ARG;
+    if (nPairs == 0) return ORBFE_OK;
+    Carver in;
+    const size_t oGeo = in.take(sizeof(NewPtNeighbour));
+    const size_t oI1 = in.take((size_t)nPairs * sizeof(int));
+    const size_t oI2 = in.take((size_t)nPairs * sizeof(int));
+    const size_t inBytes = in.off;
+    Carver sc = in;
+    const size_t oVerdict = sc.take((size_t)nPairs);
+    const size_t oX3d = sc.take((size_t)nPairs * 3 * sizeof(float));
+    const size_t outBytes = sc.off - oVerdict;
+    const int rc = ensure(m, sc.off, inBytes + outBytes + 256, err);
+    if (rc != ORBFE_OK) return rc;
+    uint8_t* hp = static_cast<uint8_t*>(m.hpin);
+    uint8_t* dp = static_cast<uint8_t*>(m.d);
+    fill_newpt(*reinterpret_cast<NewPtNeighbour*>(hp + oGeo), kf2, *NP);
+    memcpy(hp + oI1, idx1, (size_t)nPairs * sizeof(int));
+    memcpy(hp + oI2, idx2, (size_t)nPairs * sizeof(int));
+    MCHK(hipMemcpyAsync(dp, hp, inBytes, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(newpoints_kernel, dim3((nPairs + 63) / 64, 1), dim3(64), 0, s, reinterpret_cast<const NewPtNeighbour*>(dp + oGeo),
+                       nPairs, kf1->kp, kf1->sf, reinterpret_cast<const int*>(dp + oI1), reinterpret_cast<const int*>(dp + oI2),
+                       reinterpret_cast<float*>(dp + oX3d), dp + oVerdict);
+    MCHK(hipGetLastError());
+    uint8_t* hOut = hp + inBytes;
+    MCHK(hipMemcpyAsync(hOut, dp + oVerdict, outBytes, hipMemcpyDeviceToHost, s));
+    MCHK(hipStreamSynchronize(s));
+    memcpy(verdict, hOut, (size_t)nPairs);
+    memcpy(x3d, hOut + (oX3d - oVerdict), (size_t)nPairs * 3 * sizeof(float));
     return ORBFE_OK;
 }
 

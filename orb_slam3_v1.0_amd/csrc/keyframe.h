@@ -55,7 +55,14 @@ int fuse_search_keyframe_run(MatchScratch& m, hipStream_t s, const KeyFrameDev* 
 // feature of key frame 1); the per-neighbour selection runs on the host (orbfe_triangulation_select)
 int match_triangulation_batch_run(MatchScratch& m, hipStream_t s, const KeyFrameDev* kf1, const uint8_t* hasMP1, int K,
                                   const KeyFrameDev* const* kf2, const uint8_t* const* hasMP2, const orbfe_tri_params* P,
-                                  int* rawMatch, uint8_t* rawBin, std::string& err);
+                                  int* rawMatch, uint8_t* rawBin, std::string& err, const orbfe_newpoint_params* NP = nullptr,
+                                  float* x3d = nullptr, uint8_t* verdict = nullptr);
+// NP != null (orbfe_create_new_points_batch): the geometry of src/LocalMapping.cc:571-705 for every raw partner in the same
+// submission, NP[k] per neighbour: x3d[(k * n1 + i1) * 3 ..], verdict[k * n1 + i1] (ORBFE_NEWPT_*).
+// The geometry alone for an explicit pair list of two resident key frames (orbfe_triangulate_pairs)
+int triangulate_pairs_run(MatchScratch& m, hipStream_t s, const KeyFrameDev* kf1, const KeyFrameDev* kf2,
+                          const orbfe_newpoint_params* NP, int nPairs, const int* idx1, const int* idx2, float* x3d, uint8_t* verdict,
+                          std::string& err);
 
 // SearchByBoW of a frame whose features are still on the device (kernels_match_bow.hip, orbfe_track_reference_keyframe).
 // The key frame is named by a record in device memory, uploaded with the call's inputs, so a captured graph of the chain

@@ -2234,6 +2234,7 @@ int orbfe_match_triangulation(orbfe_handle* h, int n_groups, const int* kf1_off,
 struct orbfe_keyframe {
     orbfe::KeyFrameDev* k;
     int device;
+    const orbfe_handle* owner;  // the handle it was created from (the new-point entry points refuse any other)
 };
 
 int orbfe_keyframe_create(orbfe_handle* h, int n, const orbfe_keypoint* kp, const uint8_t* desc, const int* node_id,
@@ -2250,7 +2251,7 @@ int orbfe_keyframe_create(orbfe_handle* h, int n, const orbfe_keypoint* kp, cons
         h->err = err;
         return rc;
     }
-    *out = new orbfe_keyframe{k, h->device};
+    *out = new orbfe_keyframe{k, h->device, h};
     return ORBFE_OK;
 }
 
@@ -2315,6 +2316,50 @@ int orbfe_match_triangulation_batch(orbfe_handle* h, const orbfe_keyframe* kf1, 
     if (scope_.rc != ORBFE_OK) return scope_.rc;
     const int rc = match_triangulation_batch_run(h->match, h->stream, kf1->k, has_mp1, K, k2.data(), has_mp2, params, raw_match12,
                                                  raw_bin, err);
+    if (rc != ORBFE_OK) h->err = err;
+    return rc;
+}
+
+int orbfe_create_new_points_batch(orbfe_handle* h, const orbfe_keyframe* kf1, const uint8_t* has_mp1, int K,
+                                  const orbfe_keyframe* const* kf2, const uint8_t* const* has_mp2,
+                                  const orbfe_tri_params* tri_params, const orbfe_newpoint_params* np_params, int* raw_match12,
+                                  uint8_t* raw_bin, float* x3d_out, uint8_t* verdict_out)
+{
+    if (!h || !kf1 || K < 0 || K > 4096 || (K > 0 && (!kf2 || !has_mp2 || !tri_params || !np_params)) ||
+        (kf1->k->n > 0 && K > 0 && (!has_mp1 || !raw_match12 || !raw_bin || !x3d_out || !verdict_out)))
+        return ORBFE_ERR_INVALID_ARG;
+    std::vector<const orbfe::KeyFrameDev*> k2((size_t)K);
+    for (int k = 0; k < K; k++) {
+        if (!kf2[k] || kf2[k]->device != h->device || kf2[k]->owner != h) return ORBFE_ERR_INVALID_ARG;
+        if (np_params[k].struct_size != (int)sizeof(orbfe_newpoint_params)) return ORBFE_ERR_INVALID_ARG;
+        k2[(size_t)k] = kf2[k]->k;
+    }
+    if (kf1->device != h->device || kf1->owner != h) return ORBFE_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIPCHK(h, hipSetDevice(h->device));
+    std::string err;
+    MatchScope scope_(h, h->stream);
+    if (scope_.rc != ORBFE_OK) return scope_.rc;
+    const int rc = match_triangulation_batch_run(h->match, h->stream, kf1->k, has_mp1, K, k2.data(), has_mp2, tri_params, raw_match12,
+                                                 raw_bin, err, np_params, x3d_out, verdict_out);
+    if (rc != ORBFE_OK) h->err = err;
+    return rc;
+}
+
+int orbfe_triangulate_pairs(orbfe_handle* h, const orbfe_keyframe* kf1, const orbfe_keyframe* kf2,
+                            const orbfe_newpoint_params* np_params, int n_pairs, const int* idx1, const int* idx2, float* x3d_out,
+                            uint8_t* verdict_out)
+{
+    if (!h || !kf1 || !kf2 || !np_params || n_pairs < 0 || (n_pairs > 0 && (!idx1 || !idx2 || !x3d_out || !verdict_out)))
+        return ORBFE_ERR_INVALID_ARG;
+    if (np_params->struct_size != (int)sizeof(orbfe_newpoint_params)) return ORBFE_ERR_INVALID_ARG;
+    if (kf1->device != h->device || kf2->device != h->device || kf1->owner != h || kf2->owner != h) return ORBFE_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIPCHK(h, hipSetDevice(h->device));
+    std::string err;
+    MatchScope scope_(h, h->stream);
+    if (scope_.rc != ORBFE_OK) return scope_.rc;
+    const int rc = triangulate_pairs_run(h->match, h->stream, kf1->k, kf2->k, np_params, n_pairs, idx1, idx2, x3d_out, verdict_out, err);
     if (rc != ORBFE_OK) h->err = err;
     return rc;
 }

@@ -25,6 +25,7 @@ NUM_STAGES = 5
 
 STATUS = {0: "ORBFE_OK", 1: "ORBFE_ERR_INVALID_ARG", 2: "ORBFE_ERR_UNSUPPORTED", 3: "ORBFE_ERR_NO_DEVICE",
           4: "ORBFE_ERR_HIP", 5: "ORBFE_ERR_OUT_OF_MEMORY", 6: "ORBFE_ERR_INTERNAL", 7: "ORBFE_ERR_BUSY"}
+ERR_INVALID_ARG, ERR_UNSUPPORTED = 1, 2
 ERR_BUSY = 7
 
 
@@ -87,6 +88,44 @@ def fill_tri_cameras(P, cameras):
     P.kf1_has_camera2 = int(cameras.get("kf1HasCamera2", 0))
 
 
+class NewPointParams(C.Structure):
+    """orbfe_newpoint_params: what "triangulate each match" of LocalMapping::CreateNewMapPoints reads for one key-frame pair."""
+    _fields_ = [("struct_size", C.c_int), ("tcw1", C.c_float * 12), ("tcw2", C.c_float * 12), ("twc1", C.c_float * 3),
+                ("twc2", C.c_float * 3), ("camera_model1", C.c_int), ("camera_model2", C.c_int), ("cam1", C.c_float * 8),
+                ("cam2", C.c_float * 8), ("kb_precision", C.c_float), ("level_sigma2_1", C.c_float * 32),
+                ("level_sigma2_2", C.c_float * 32), ("ratio_factor", C.c_float), ("inertial", C.c_int), ("far_points", C.c_int),
+                ("th_far_points", C.c_float)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(NewPointParams)
+
+
+# verdict bytes of orbfe_create_new_points_batch / orbfe_triangulate_pairs (ORBFE_NEWPT_*)
+NEWPT_ACCEPTED, NEWPT_LOW_PARALLAX, NEWPT_AT_INFINITY, NEWPT_BEHIND_1, NEWPT_BEHIND_2 = 0, 1, 2, 3, 4
+NEWPT_REPROJECTION_1, NEWPT_REPROJECTION_2, NEWPT_ZERO_DISTANCE, NEWPT_FAR, NEWPT_SCALE, NEWPT_NO_PARTNER = 5, 6, 7, 8, 9, 255
+
+
+def newpoint_params(Tcw1, Tcw2, twc1, twc2, levelSigma2_1, levelSigma2_2, ratioFactor, model1=0, model2=0, cam1=None, cam2=None,
+                    precision=1e-6, inertial=False, farPoints=False, thFarPoints=0.0):
+    """orbfe_newpoint_params of one pair: Tcw = GetPose().matrix3x4() (3 x 4), twc = GetTranslationInverse(), cam = fx fy cx cy
+    k1 k2 k3 k4, ratioFactor = 1.5f * mfScaleFactor"""
+    P = NewPointParams()
+    for dst, src, n in ((P.tcw1, Tcw1, 12), (P.tcw2, Tcw2, 12), (P.twc1, twc1, 3), (P.twc2, twc2, 3), (P.cam1, cam1, 8),
+                        (P.cam2, cam2, 8), (P.level_sigma2_1, levelSigma2_1, None), (P.level_sigma2_2, levelSigma2_2, None)):
+        if src is None:
+            continue
+        v = np.asarray(src, np.float32).reshape(-1)
+        assert n is None or len(v) == n
+        for i, x in enumerate(v):
+            dst[i] = float(x)
+    P.camera_model1, P.camera_model2 = int(model1), int(model2)
+    P.kb_precision = float(precision)
+    P.ratio_factor = float(np.float32(ratioFactor))
+    P.inertial, P.far_points, P.th_far_points = int(inertial), int(farPoints), float(np.float32(thFarPoints))
+    return P
+
+
 class TrackParams(C.Structure):
     """orbfe_track_params: frame grid statics (src/Frame.cc:101-105) + the call parameters of SearchByProjection."""
     _fields_ = [("struct_size", C.c_int), ("grid_cols", C.c_int), ("grid_rows", C.c_int), ("min_x", C.c_float),
@@ -117,7 +156,7 @@ SYMBOLS = [
     "orbfe_get_device_status", "orbfe_stream_create", "orbfe_stream_destroy", "orbfe_stream_submit", "orbfe_stream_collect",
     "orbfe_stream_collect_view", "orbfe_stream_in_flight", "orbfe_track_frame",
     "orbfe_keyframe_create", "orbfe_keyframe_destroy", "orbfe_keyframe_size", "orbfe_match_triangulation_batch",
-    "orbfe_triangulation_select", "orbfe_map_create", "orbfe_map_destroy", "orbfe_map_update", "orbfe_stream_enable_track",
+    "orbfe_triangulation_select", "orbfe_create_new_points_batch", "orbfe_triangulate_pairs", "orbfe_map_create", "orbfe_map_destroy", "orbfe_map_update", "orbfe_stream_enable_track",
     "orbfe_stream_submit_track", "orbfe_stream_collect_track", "orbfe_track_frame_map", "orbfe_track_reference_keyframe", "orbfe_debug_graph_stats", "orbfe_set_graph_capture",
     "orbfe_debug_clock_probe", "orbfe_keyframe_set_grid", "orbfe_fuse_search_keyframe",
     "orbfe_init_frame_create", "orbfe_init_frame_destroy", "orbfe_init_frame_size", "orbfe_track_initialization",
@@ -235,6 +274,9 @@ def lib():
     L.orbfe_fuse_search_keyframe.argtypes = [vp, vp, vp, ci, vp, C.POINTER(Frustum), cf, vp, vp]
     L.orbfe_match_triangulation_batch.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, vp]
     L.orbfe_triangulation_select.argtypes = [ci, vp, vp, vp, ci, vp, vp]
+    if hasattr(L, "orbfe_create_new_points_batch"):  # an earlier build loaded for an A/B (bench.py --lib tools/ab/...) lacks the two
+        L.orbfe_create_new_points_batch.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.orbfe_triangulate_pairs.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, vp]
     L.orbfe_distinctive_descriptors.argtypes = [vp, ci, vp, vp, vp, vp]
     L.orbfe_vocab_create.argtypes = [vp, ci, vp, vp, vp, vp, vp, ci, C.POINTER(vp)]
     L.orbfe_vocab_destroy.argtypes = [vp]
@@ -963,6 +1005,39 @@ def SearchForTriangulation_batch(extractor, kf1, hasMP1, kf2s, hasMP2s, params):
     extractor._chk(extractor.L.orbfe_match_triangulation_batch(extractor.h, kf1.h, _p(h1), K, kfp, h2p, P, _p(raw), _p(rbin)),
                    "orbfe_match_triangulation_batch")
     return raw[:K, :kf1.n], rbin[:K, :kf1.n]
+
+
+def CreateNewMapPoints_batch(extractor, kf1, hasMP1, kf2s, hasMP2s, params, np_params):
+    """orbfe_create_new_points_batch: SearchForTriangulation_batch + the geometry of src/LocalMapping.cc:571-705 for every raw
+    partner in the same submission -> (raw_match12 [K][n1], raw_bin [K][n1], x3d [K][n1][3], verdict [K][n1]); walk the
+    neighbours in order with triangulation_select and create the points whose verdict is NEWPT_ACCEPTED."""
+    K = len(kf2s)
+    h1 = np.ascontiguousarray(hasMP1, np.uint8)
+    h2 = [np.ascontiguousarray(v, np.uint8) for v in hasMP2s]
+    kfp = (C.c_void_p * max(K, 1))(*[k.h.value for k in kf2s])
+    h2p = (C.c_void_p * max(K, 1))(*[v.ctypes.data for v in h2])
+    P = (TriParams * max(K, 1))(*params)
+    Q = (NewPointParams * max(K, 1))(*np_params)
+    raw = np.full((max(K, 1), max(kf1.n, 1)), -1, np.int32)
+    rbin = np.zeros((max(K, 1), max(kf1.n, 1)), np.uint8)
+    x3d = np.zeros((max(K, 1), max(kf1.n, 1), 3), np.float32)
+    verdict = np.full((max(K, 1), max(kf1.n, 1)), NEWPT_NO_PARTNER, np.uint8)
+    extractor._chk(extractor.L.orbfe_create_new_points_batch(extractor.h, kf1.h, _p(h1), K, kfp, h2p, P, Q, _p(raw), _p(rbin), _p(x3d),
+                                                             _p(verdict)), "orbfe_create_new_points_batch")
+    return raw[:K, :kf1.n], rbin[:K, :kf1.n], x3d[:K, :kf1.n], verdict[:K, :kf1.n]
+
+
+def triangulate_pairs(extractor, kf1, kf2, np_params, idx1, idx2):
+    """orbfe_triangulate_pairs: (x3d [n][3], verdict [n]) of the explicit pairs (idx1[p], idx2[p]) of two resident key frames"""
+    i1 = np.ascontiguousarray(idx1, np.int32)
+    i2 = np.ascontiguousarray(idx2, np.int32)
+    assert len(i1) == len(i2)
+    n = len(i1)
+    x3d = np.zeros((max(n, 1), 3), np.float32)
+    verdict = np.full(max(n, 1), NEWPT_NO_PARTNER, np.uint8)
+    extractor._chk(extractor.L.orbfe_triangulate_pairs(extractor.h, kf1.h, kf2.h, C.byref(np_params), n, _p(i1), _p(i2), _p(x3d),
+                                                       _p(verdict)), "orbfe_triangulate_pairs")
+    return x3d[:n], verdict[:n]
 
 
 def triangulation_select(raw_match12, raw_bin, hasMP1_now, checkOrientation=True):
