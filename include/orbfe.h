@@ -590,15 +590,44 @@ int orbfe_keyframe_set_grid(orbfe_handle *h, orbfe_keyframe *kf, int grid_cols, 
  * frame of orbfe_keyframe_create with orbfe_keyframe_set_grid done, the map points are entries of an orbfe_map named by id:
  * ids[i] >= 0 = the entry; ~id (negative) = the entry with "!pMP || pMP->IsInKeyFrame(pKF)" for this call (skipped,
  * src/ORBmatcher.cc:706-721); an id outside the map = no point.  Up go the frustum and 4 bytes per map point, down come
- * best_idx_out[i] / best_dist_out[i] as orbfe_fuse_search (-1 / 256 when nothing qualified).  The calls of one
- * SearchInNeighbors stay sequential -- between two of them the caller replaces / adds map points (:829-849); descriptor
- * and position changes reach the map through orbfe_map_update, which is ordered in front of the next call.
+ * best_idx_out[i] / best_dist_out[i] as orbfe_fuse_search (-1 / 256 when nothing qualified).  With this call the calls of one
+ * SearchInNeighbors stay sequential (orbfe_fuse_search_keyframes below does all targets at once) -- between two of them the
+ * caller replaces / adds map points (:829-849); descriptor and position changes reach the map through orbfe_map_update,
+ * which is ordered in front of the next call.
  * Same results as orbfe_fuse_search on the same key frame, map points and flags (monocular / stereo left camera; the bRight
  * overload has no resident form). */
 int orbfe_fuse_search_keyframe(orbfe_handle *h, const orbfe_keyframe *kf, const orbfe_map *map, int M, const int *ids,
                                const orbfe_frustum *frustum, float th, int *best_idx_out, int *best_dist_out);
 
-/* the same with bRight = true (src/ORBmatcher.cc:684-688,:820; callers src/LocalMapping.cc:824,854 when the key frame
+/* orbfe_fuse_search_keyframe into ALL targets of one SearchInNeighbors loop (src/LocalMapping.cc:819-824) in one submission.
+ * Everything a search does before it compares descriptors (projection, IsInImage, distance gate, PredictScale,
+ * GetFeaturesInArea, level and chi-square gates, src/ORBmatcher.cc:724-820) reads only what the loop never changes; the skip
+ * conditions only ever turn ON during the loop; the descriptor enters in the strict "<" scan alone (:824-832).  So the call
+ * returns, per pair, the best candidate under the descriptor the map holds NOW and the gated candidates in visit order, and the
+ * caller walks the targets in order: a pair skipped by now is masked on the host, a point whose descriptor changed since the
+ * call (MapPoint::Replace -> ComputeDistinctiveDescriptors) gets its result from orbfe_fuse_select over its list.
+ * rows k = 0..K-1: exactly orbfe_fuse_search_keyframe(h, kfs[k], map, M, ids_k, &frusta[k], th, ...) with
+ * ids_k[i] = skip && skip[k*M+i] ? (ids[i] < 0 ? ids[i] : ~ids[i]) : ids[i]      -- ONE upload, ONE launch, ONE download, ONE sync.
+ * best_idx_out / best_dist_out: K*M ints each (-1 / 256 when nothing qualified).
+ * cand_cap in [0,16]; when > 0: cand_count_out[k*M+i] = number of features that passed every gate of :787-820 for the pair
+ * (the TRUE count, it may exceed cand_cap), cand_idx_out[(k*M+i)*cand_cap + j] = the j-th of them in the reference's
+ * visit order (the order in which the strict "<" of :828 sees them), -1 beyond the count.  HOST pointers except kfs / map.
+ * Validation per target is the single call's (grid set, frusta[k].n_levels within the key frame's levels); K == 0 or M == 0
+ * returns ORBFE_OK and writes nothing; a NULL among the required pointers or cand_cap outside [0,16] is ORBFE_ERR_INVALID_ARG
+ * before anything is enqueued.  Targets may differ in feature count (0 included), grid, camera model and mono / stereo; the
+ * same key frame may appear twice.  The bRight overload has no resident form. */
+int orbfe_fuse_search_keyframes(orbfe_handle *h, int K, const orbfe_keyframe *const *kfs, const orbfe_frustum *frusta,
+                                const orbfe_map *map, int M, const int *ids, const uint8_t *skip, float th,
+                                int *best_idx_out, int *best_dist_out, int cand_cap, int *cand_idx_out, int *cand_count_out);
+
+/* host-only, no handle: the scan of :824-832 for ONE pair over a candidate list of the call above, with a descriptor the
+ * caller supplies (the point's descriptor NOW).  kf_desc = the target's mDescriptors (host, n_kf x 32).  Ties keep the
+ * earlier entry; an empty list gives -1 / 256.  Returns ORBFE_ERR_UNSUPPORTED when cand_count > cand_cap (list truncated:
+ * use orbfe_fuse_search_keyframe for that pair), ORBFE_ERR_INVALID_ARG for an index outside [0, n_kf). */
+int orbfe_fuse_select(const int *cand_idx, int cand_count, int cand_cap, const uint8_t *kf_desc, int n_kf,
+                      const uint8_t *mp_desc, int *best_idx, int *best_dist);
+
+/* orbfe_fuse_search with bRight = true (src/ORBmatcher.cc:684-688,:820; callers src/LocalMapping.cc:824,854 when the key frame
  * has a second camera): frustum carries pKF->GetRightPose() / GetRightTranslationInverse() / mpCamera2; KF_left
  * describes the LEFT features (KF_left->n == pKF->NLeft -- they fill mGrid, and the level and chi-square gates read them,
  * as in the reference) while KF_left->desc is all of pKF->mDescriptors: NLeft + n_right rows.  The compared descriptor

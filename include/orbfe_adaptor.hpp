@@ -764,6 +764,139 @@ struct ResidentFuse {
     }
 };
 
+// The first loop of LocalMapping::SearchInNeighbors (src/LocalMapping.cc:819-824: ORBmatcher::Fuse(pKFi, vpMapPointMatches) for
+// every target key frame) with ONE submission for all targets (orbfe_fuse_search_keyframes).  Construct it before the loop: it
+// evaluates "!pMP || pMP->IsInKeyFrame(pKFk)" for every pair, remembers the 32 descriptor bytes every point has NOW and makes
+// the one call (candCap gated candidates per pair come back with the results).  Inside the loop, in place of
+// ResidentFuse::Fuse(h, pKFk, ...), call Fuse(k, pKFk, vpMapPointMatches, descOfMP): the body of ResidentFuse::Fuse for
+// target k on the graph as it is NOW --
+//   * a pair that is skipped by now (isBad() / IsInKeyFrame, which only ever turn on during the loop) is skipped;
+//   * a point whose descriptor bytes differ from the remembered ones (MapPoint::Replace recomputed them, src/MapPoint.cc:311 --
+//     judged from the bytes when target k's turn begins, whichever edit changed them) gets its result for this target from
+//     orbfe_fuse_select over its candidate list with the bytes of now;
+//   * where that list is truncated (more than candCap candidates) the point is collected, and ONE orbfe_fuse_search_keyframe
+//     for the collected points runs before target k is processed, after map.Update of exactly those points;
+//   * every other pair takes the row of the one call.
+// The result -- nFused, the Replace / AddObservation / AddMapPoint calls and their order -- is that of the K sequential
+// ResidentFuse::Fuse calls with the ResidentMap updated between them.  The graph edits stay the caller's types' own; the points'
+// positions and distance ranges must not change during the loop (the reference runs UpdateNormalAndDepth after it, :857-870).
+// candCap = 4: in the project's K = 20, th = 10 scenes no pair has more than 4 gated candidates (overflow rate 0).
+class NeighbourFuseBatch {
+public:
+    template <class KeyFramePtr, class MapPointPtr, class DescOfKF, class DescOfMP>
+    NeighbourFuseBatch(orbfe_handle* h, const std::vector<KeyFramePtr>& vpTargetKFs, const std::vector<const ResidentKeyFrame*>& resident,
+                       const std::vector<orbfe_frustum>& frusta, ResidentMap& map, const std::vector<MapPointPtr>& vpMapPointMatches,
+                       const std::vector<int>& ids, float th, DescOfKF descOfKF, DescOfMP descOfMP, int candCap = 4)
+        : h_(h), map_(&map), frusta_(frusta), ids_(ids), th_(th), K_((int)vpTargetKFs.size()), M_((int)vpMapPointMatches.size()),
+          cap_(candCap)
+    {
+        if ((int)resident.size() != K_ || (int)frusta.size() != K_ || (int)ids.size() != M_ || candCap < 1 || candCap > 16)
+            throw std::invalid_argument("NeighbourFuseBatch: one ResidentKeyFrame and frustum per target, one id per map point, candCap in [1, 16]");
+        const size_t KM = (size_t)(K_ > 0 ? K_ : 1) * (M_ > 0 ? M_ : 1);
+        std::vector<uint8_t> skip(KM, 0);
+        desc0_.assign((size_t)(M_ > 0 ? M_ : 1) * 32, 0);
+        for (int i = 0; i < M_; i++)
+            if (vpMapPointMatches[i]) std::memcpy(&desc0_[(size_t)i * 32], descOfMP(vpMapPointMatches[i]), 32);
+        for (int k = 0; k < K_; k++) {
+            kf_.push_back(resident[k]->get());
+            kfDesc_.push_back(descOfKF(vpTargetKFs[k]));
+            kfN_.push_back(vpTargetKFs[k]->N);
+            for (int i = 0; i < M_; i++) {
+                const auto& pMP = vpMapPointMatches[i];
+                skip[(size_t)k * M_ + i] = (!pMP || pMP->IsInKeyFrame(vpTargetKFs[k])) ? 1 : 0;
+            }
+        }
+        bestIdx_.assign(KM, -1);
+        bestDist_.assign(KM, 256);
+        candIdx_.assign(KM * cap_, -1);
+        candCount_.assign(KM, 0);
+        orbfe_detail::check(orbfe_fuse_search_keyframes(h, K_, kf_.data(), frusta_.data(), map.get(), M_, ids_.data(), skip.data(), th,
+                                                        bestIdx_.data(), bestDist_.data(), cap_, candIdx_.data(), candCount_.data()),
+                            h, "orbfe_fuse_search_keyframes");
+        submissions_ = 1;
+    }
+
+    template <class KeyFramePtr, class MapPointPtr, class DescOfMP>
+    int Fuse(int k, KeyFramePtr pKF, const std::vector<MapPointPtr>& vpMapPoints, DescOfMP descOfMP)
+    {
+        if (k < 0 || k >= K_ || (int)vpMapPoints.size() != M_) throw std::invalid_argument("NeighbourFuseBatch::Fuse: target or list out of range");
+        const size_t row = (size_t)k * M_;
+        std::vector<int> bestIdx(bestIdx_.begin() + row, bestIdx_.begin() + row + M_), bestDist(bestDist_.begin() + row, bestDist_.begin() + row + M_);
+        std::vector<int> over;  // dirty points whose candidate list is truncated
+        for (int i = 0; i < M_; i++) {
+            const auto& pMP = vpMapPoints[i];
+            if (!pMP || pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;
+            const uint8_t* d = descOfMP(pMP);
+            if (std::memcmp(d, &desc0_[(size_t)i * 32], 32) == 0) continue;
+            hostSelects_++;
+            const int rc = orbfe_fuse_select(&candIdx_[(row + i) * cap_], candCount_[row + i], cap_, kfDesc_[k], kfN_[k], d, &bestIdx[i], &bestDist[i]);
+            if (rc == ORBFE_ERR_UNSUPPORTED) over.push_back(i);
+            else orbfe_detail::check(rc, nullptr, "orbfe_fuse_select");
+        }
+        if (!over.empty()) {
+            std::vector<MapPointPtr> pts;
+            std::vector<int> sel;
+            for (int i : over) {
+                pts.push_back(vpMapPoints[i]);
+                sel.push_back(ids_[i]);
+            }
+            map_->Update(pts, sel, descOfMP);
+            std::vector<int> a(over.size()), b(over.size());
+            orbfe_detail::check(orbfe_fuse_search_keyframe(h_, kf_[k], map_->get(), (int)sel.size(), sel.data(), &frusta_[k], th_, a.data(), b.data()),
+                                h_, "orbfe_fuse_search_keyframe");
+            for (size_t j = 0; j < over.size(); j++) {
+                bestIdx[over[j]] = a[j];
+                bestDist[over[j]] = b[j];
+            }
+            submissions_++;
+            overflows_ += (int)over.size();
+        }
+        int nFused = 0;
+        for (int i = 0; i < M_; i++) {
+            const auto& pMP = vpMapPoints[i];
+            if (!pMP || pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;  // :701-720, re-evaluated in order
+            if (bestDist[i] > ORBFE_TH_LOW) continue;                       // :829
+            auto pMPinKF = pKF->GetMapPoint(bestIdx[i]);
+            if (pMPinKF) {
+                if (!pMPinKF->isBad()) {
+                    if (pMPinKF->Observations() > pMP->Observations()) pMP->Replace(pMPinKF);
+                    else pMPinKF->Replace(pMP);
+                }
+            } else {
+                pMP->AddObservation(pKF, bestIdx[i]);
+                pKF->AddMapPoint(pMP, bestIdx[i]);
+            }
+            nFused++;
+        }
+        return nFused;
+    }
+
+    int Submissions() const { return submissions_; }  // 1 + the targets that needed a fallback search
+    int HostSelects() const { return hostSelects_; }  // orbfe_fuse_select calls (dirty pairs)
+    int Overflows() const { return overflows_; }      // of those: truncated lists, searched again on the device
+    // pairs of the one call whose true candidate count exceeds candCap (the measured overflow rate's numerator)
+    size_t PairsAboveCap() const
+    {
+        size_t n = 0;
+        for (int c : candCount_) n += c > cap_;
+        return n;
+    }
+
+private:
+    orbfe_handle* h_;
+    ResidentMap* map_;
+    std::vector<orbfe_frustum> frusta_;
+    std::vector<int> ids_;
+    float th_;
+    int K_, M_, cap_;
+    std::vector<const orbfe_keyframe*> kf_;
+    std::vector<const uint8_t*> kfDesc_;
+    std::vector<int> kfN_;
+    std::vector<uint8_t> desc0_;
+    std::vector<int> bestIdx_, bestDist_, candIdx_, candCount_;
+    int submissions_ = 0, hostSelects_ = 0, overflows_ = 0;
+};
+
 // The SearchForTriangulation loop of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:455-488) with ONE GPU launch for
 // all neighbours.  Construct it before the loop (prm[k] = the F12 / epipole / camera block of the pair (pKF1, neighbour
 // k), computed with the reference's own expressions); inside the loop, where the reference calls

@@ -27,30 +27,43 @@ namespace {
 // PredictScale, KeyFrame::GetFeaturesInArea through the per-level cell-range tables, the chi-square gate
 // (:794-817) and the nearest descriptor under (distance, visit position) == the reference's strict "<" scan.
 // ---------------------------------------------------------------------------------------------
-// GATHER: the map points are entries ids[i] of a resident map of mapCap entries (orbfe_map): id >= 0 the entry, ~id (negative)
-// the entry with this call's skip flag set, outside the map no point -- pts / mpDesc are then the map's arrays.
-template <bool GATHER>
-__global__ __launch_bounds__(256) void fuse_search_kernel(ProjArgs A, orbfe_frustum F, float th, int M,
-                                                          const int* __restrict__ ids, int mapCap,
-                                                          const orbfe_world_point* __restrict__ pts,
-                                                          const uint8_t* __restrict__ mpDesc,
-                                                          const float* __restrict__ invLevelSigma2,
-                                                          const float* __restrict__ uRight, int chi2Gate,
-                                                          const unsigned long long* __restrict__ rightDesc, int nRight,
-                                                          int* __restrict__ bestIdxOut, int* __restrict__ bestDistOut)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;  // (one wave per block for a single call: see fuse_search_run)
-    if (i >= M) return;
-    int src = i;
-    bool skipped = false;
-    if (GATHER) {
-        const int id = ids[i];
-        src = id < 0 ? ~id : id;
-        skipped = id < 0 || src >= mapCap;
-        if (src >= mapCap) src = 0;
+// Candidate sink of the walk below (orbfe_fuse_search_keyframes): the visit positions (ranks) of the features that passed every
+// gate, kept sorted -- the walk visits level lvl-1 before lvl, the reference's strict "<" sees them in rank order.  The slots are
+// registers: the insertion is a fixed chain of compare-selects, never an array indexed at run time.
+constexpr int kFuseCandMax = 16;
+struct CandSink {
+    uint32_t r[kFuseCandMax];
+    int count;
+    __device__ __forceinline__ void clear()
+    {
+#pragma unroll
+        for (int j = 0; j < kFuseCandMax; j++) r[j] = kKey32None;
+        count = 0;
     }
-    const orbfe_world_point p = pts[src];
-    int bestIdx = -1, bestDist = 256;
+    __device__ __forceinline__ void push(uint32_t rank)
+    {
+        count++;
+#pragma unroll
+        for (int j = 0; j < kFuseCandMax; j++) {  // the kFuseCandMax smallest ranks survive, ascending
+            const uint32_t lo = min(r[j], rank);
+            rank = max(r[j], rank);
+            r[j] = lo;
+        }
+    }
+};
+
+// The per-point walk of ORBmatcher::Fuse(pKF, vpMapPoints, th) (:706-832) for ONE map point: shared by fuse_search_kernel
+// (one target per launch) and fuse_neighbors_kernel (a table of targets).  src = the point's row of mpDesc.  CANDS: every
+// feature that passes the gates also goes to `sink`.
+template <bool GATHER, bool CANDS>
+__device__ __forceinline__ void fuse_walk(const ProjArgs& A, const orbfe_frustum& F, float th, bool skipped,
+                                          const orbfe_world_point& p, const uint8_t* __restrict__ mpDesc, int src,
+                                          const float* __restrict__ invLevelSigma2, const float* __restrict__ uRight, int chi2Gate,
+                                          const unsigned long long* __restrict__ rightDesc, int nRight, int& bestIdx, int& bestDist,
+                                          CandSink& sink)
+{
+    bestIdx = -1;
+    bestDist = 256;
     do {
         if (skipped || (!GATHER && p.skip) || p.bad) break;  // :706-721 (a resident entry's own skip member is per frame: ignored)
         const float X = p.x, Y = p.y, Z = p.z;
@@ -111,6 +124,7 @@ __global__ __launch_bounds__(256) void fuse_search_kernel(ProjArgs A, orbfe_frus
                         const float e2 = ex * ex + ey * ey;
                         if ((double)(e2 * invS2) > 5.99) continue;
                     }
+                    if (CANDS) sink.push((uint32_t)rq.x);  // passed every gate of :787-820
                     const unsigned long long* kd = A.descS + (size_t)sl * 4;
                     if (rightDesc) {  // bRight (:820): the left feature passed the gates, its right twin's row is compared
                         const int idx = A.order[rq.x];
@@ -127,8 +141,86 @@ __global__ __launch_bounds__(256) void fuse_search_kernel(ProjArgs A, orbfe_frus
             bestDist = (int)(best >> kRankBits);
         }
     } while (false);
+}
+
+// GATHER: the map points are entries ids[i] of a resident map of mapCap entries (orbfe_map): id >= 0 the entry, ~id (negative)
+// the entry with this call's skip flag set, outside the map no point -- pts / mpDesc are then the map's arrays.
+template <bool GATHER>
+__global__ __launch_bounds__(256) void fuse_search_kernel(ProjArgs A, orbfe_frustum F, float th, int M,
+                                                          const int* __restrict__ ids, int mapCap,
+                                                          const orbfe_world_point* __restrict__ pts,
+                                                          const uint8_t* __restrict__ mpDesc,
+                                                          const float* __restrict__ invLevelSigma2,
+                                                          const float* __restrict__ uRight, int chi2Gate,
+                                                          const unsigned long long* __restrict__ rightDesc, int nRight,
+                                                          int* __restrict__ bestIdxOut, int* __restrict__ bestDistOut)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;  // (one wave per block for a single call: see fuse_search_run)
+    if (i >= M) return;
+    int src = i;
+    bool skipped = false;
+    if (GATHER) {
+        const int id = ids[i];
+        src = id < 0 ? ~id : id;
+        skipped = id < 0 || src >= mapCap;
+        if (src >= mapCap) src = 0;
+    }
+    const orbfe_world_point p = pts[src];
+    int bestIdx, bestDist;
+    CandSink none;
+    fuse_walk<GATHER, false>(A, F, th, skipped, p, mpDesc, src, invLevelSigma2, uRight, chi2Gate, rightDesc, nRight, bestIdx, bestDist,
+                             none);
     bestIdxOut[i] = bestIdx;
     bestDistOut[i] = bestDist;
+}
+
+// ---------------------------------------------------------------------------------------------
+// orbfe_fuse_search_keyframes: the Fuse searches of LocalMapping::SearchInNeighbors (src/LocalMapping.cc:819-824) into all K
+// targets in ONE launch.  Grid (ceil(M / 64), K), one wave per block: the target is wave-uniform, its record comes out of a
+// K-entry table in device memory through uniform addresses.  Per pair the walk is fuse_walk -- the single call's -- with the
+// candidate sink: besides (bestIdx, bestDist) under the descriptor the map holds NOW, the features that passed every gate in
+// visit order, so that the caller can redo the strict "<" scan on the host when a Replace changed the point's descriptor.
+// ---------------------------------------------------------------------------------------------
+struct FuseTarget {
+    ProjArgs A;
+    orbfe_frustum F;
+    const float* invLevelSigma2;
+    const float* uRight;
+    int n;  // features of the target: 0 = no tables were built, nothing qualifies
+};
+
+template <bool CANDS>
+__global__ __launch_bounds__(64) void fuse_neighbors_kernel(const FuseTarget* __restrict__ tab, float th, int M,
+                                                            const int* __restrict__ ids, const uint8_t* __restrict__ skip,
+                                                            int mapCap, const orbfe_world_point* __restrict__ pts,
+                                                            const uint8_t* __restrict__ mpDesc, int* __restrict__ bestIdxOut,
+                                                            int* __restrict__ bestDistOut, int candCap, int* __restrict__ candIdxOut,
+                                                            int* __restrict__ candCountOut)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= M) return;
+    const int k = blockIdx.y;
+    const size_t row = (size_t)k * M + i;
+    const FuseTarget& T = tab[k];
+    int id = ids[i];
+    if (skip && skip[row]) id = id < 0 ? id : ~id;
+    const int src = id < 0 ? ~id : id;
+    int bestIdx = -1, bestDist = 256;
+    CandSink sink;
+    if (CANDS) sink.clear();
+    if (id >= 0 && src < mapCap && T.n > 0) {  // skipped lanes leave at once
+        const orbfe_world_point p = pts[src];
+        fuse_walk<true, CANDS>(T.A, T.F, th, false, p, mpDesc, src, T.invLevelSigma2, T.uRight, 1, nullptr, -1, bestIdx, bestDist, sink);
+    }
+    bestIdxOut[row] = bestIdx;
+    bestDistOut[row] = bestDist;
+    if (CANDS) {
+        candCountOut[row] = sink.count;
+        int* out = candIdxOut + row * (size_t)candCap;
+#pragma unroll
+        for (int j = 0; j < kFuseCandMax; j++)
+            if (j < candCap) out[j] = sink.r[j] != kKey32None ? T.A.order[sink.r[j]] : -1;
+    }
 }
 
 // PredictScale (src/MapPoint.cc:580-612) on the pinned logarithm, SPEC DECISION S8
@@ -483,6 +575,82 @@ int fuse_search_keyframe_run(MatchScratch& m, hipStream_t s, const KeyFrameDev* 
     MCHK(hipStreamSynchronize(s));
     memcpy(bestIdxOut, hBest, (size_t)M * sizeof(int));
     memcpy(bestDistOut, hBest + M, (size_t)M * sizeof(int));
+    return ORBFE_OK;
+}
+
+int fuse_search_keyframes_run(MatchScratch& m, hipStream_t s, int K, const KeyFrameDev* const* kfs, const orbfe_frustum* frusta,
+                              int mapCap, const orbfe_world_point* mapPts, const uint8_t* mapDesc, int M, const int* ids,
+                              const uint8_t* skip, float th, int* bestIdxOut, int* bestDistOut, int candCap, int* candIdxOut,
+                              int* candCountOut, std::string& err)
+{
+    const size_t KM = (size_t)K * M;
+    Carver c;
+    const size_t oTab = c.take((size_t)K * sizeof(FuseTarget));
+    const size_t oIds = c.take((size_t)M * sizeof(int));
+    const size_t oSkip = c.take(skip ? KM : 0);
+    const size_t inBytes = c.off;
+    const size_t outInts = KM * (size_t)(candCap > 0 ? 3 + candCap : 2);  // [bestIdx | bestDist | candCount | candIdx]
+    const size_t oOut = c.take(outInts * sizeof(int));
+    int rc = ensure(m, c.off, c.off, err);
+    if (rc != ORBFE_OK) return rc;
+    uint8_t* hp = static_cast<uint8_t*>(m.hpin);
+    uint8_t* dp = static_cast<uint8_t*>(m.d);
+    FuseTarget* hTab = reinterpret_cast<FuseTarget*>(hp + oTab);
+    for (int k = 0; k < K; k++) {
+        hTab[k].A = kfs[k]->grid;
+        hTab[k].F = frusta[k];
+        hTab[k].invLevelSigma2 = kfs[k]->invLevelSigma2;
+        hTab[k].uRight = kfs[k]->uRight;
+        hTab[k].n = kfs[k]->n;
+    }
+    memcpy(hp + oIds, ids, (size_t)M * sizeof(int));
+    if (skip) memcpy(hp + oSkip, skip, KM);
+    MCHK(hipMemcpyAsync(dp, hp, inBytes, hipMemcpyHostToDevice, s));  // table, ids and skip flags in one copy
+    int* dOut = reinterpret_cast<int*>(dp + oOut);
+    const FuseTarget* dTab = reinterpret_cast<const FuseTarget*>(dp + oTab);
+    const int* dIds = reinterpret_cast<const int*>(dp + oIds);
+    const uint8_t* dSkip = skip ? dp + oSkip : nullptr;
+    const dim3 grid((M + 63) / 64, K);
+    if (candCap > 0)
+        hipLaunchKernelGGL(fuse_neighbors_kernel<true>, grid, dim3(64), 0, s, dTab, th, M, dIds, dSkip, mapCap, mapPts, mapDesc, dOut,
+                           dOut + KM, candCap, dOut + 3 * KM, dOut + 2 * KM);
+    else
+        hipLaunchKernelGGL(fuse_neighbors_kernel<false>, grid, dim3(64), 0, s, dTab, th, M, dIds, dSkip, mapCap, mapPts, mapDesc, dOut,
+                           dOut + KM, 0, static_cast<int*>(nullptr), static_cast<int*>(nullptr));
+    MCHK(hipGetLastError());
+    int* hOut = reinterpret_cast<int*>(hp + oOut);
+    MCHK(hipMemcpyAsync(hOut, dOut, outInts * sizeof(int), hipMemcpyDeviceToHost, s));
+    MCHK(hipStreamSynchronize(s));
+    memcpy(bestIdxOut, hOut, KM * sizeof(int));
+    memcpy(bestDistOut, hOut + KM, KM * sizeof(int));
+    if (candCap > 0) {
+        memcpy(candCountOut, hOut + 2 * KM, KM * sizeof(int));
+        memcpy(candIdxOut, hOut + 3 * KM, KM * (size_t)candCap * sizeof(int));
+    }
+    return ORBFE_OK;
+}
+
+// src/ORBmatcher.cc:824-832 for one pair on the host: the strict "<" over the candidate list, which is in visit order
+int fuse_select_host(const int* candIdx, int candCount, int candCap, const uint8_t* kfDesc, int nKf, const uint8_t* mpDesc,
+                     int* bestIdx, int* bestDist)
+{
+    *bestIdx = -1;
+    *bestDist = 256;
+    if (candCount > candCap) return ORBFE_ERR_UNSUPPORTED;
+    unsigned long long d[4];
+    memcpy(d, mpDesc, 32);
+    for (int j = 0; j < candCount; j++) {
+        const int idx = candIdx[j];
+        if (idx < 0 || idx >= nKf) return ORBFE_ERR_INVALID_ARG;
+        unsigned long long q[4];
+        memcpy(q, kfDesc + (size_t)idx * 32, 32);
+        const int dist = __builtin_popcountll(q[0] ^ d[0]) + __builtin_popcountll(q[1] ^ d[1]) + __builtin_popcountll(q[2] ^ d[2]) +
+                         __builtin_popcountll(q[3] ^ d[3]);
+        if (dist < *bestDist) {
+            *bestDist = dist;
+            *bestIdx = idx;
+        }
+    }
     return ORBFE_OK;
 }
 

@@ -50,6 +50,16 @@ int keyframe_set_grid(KeyFrameDev* K, hipStream_t s, int gridCols, int gridRows,
 int fuse_search_keyframe_run(MatchScratch& m, hipStream_t s, const KeyFrameDev* K, int mapCap, const orbfe_world_point* mapPts,
                              const uint8_t* mapDesc, int M, const int* ids, const orbfe_frustum* F, float th, int* bestIdxOut,
                              int* bestDistOut, std::string& err);
+// the same for K resident targets in ONE submission (LocalMapping::SearchInNeighbors, src/LocalMapping.cc:819-824): row k is
+// fuse_search_keyframe_run on kfs[k] / frusta[k] with ids complemented where skip[k * M + i] is set (skip may be null).  candCap > 0:
+// also the features that passed every gate, per pair, in visit order (candIdx[(k * M + i) * candCap ..], candCount the true count).
+int fuse_search_keyframes_run(MatchScratch& m, hipStream_t s, int K, const KeyFrameDev* const* kfs, const orbfe_frustum* frusta,
+                              int mapCap, const orbfe_world_point* mapPts, const uint8_t* mapDesc, int M, const int* ids,
+                              const uint8_t* skip, float th, int* bestIdxOut, int* bestDistOut, int candCap, int* candIdxOut,
+                              int* candCountOut, std::string& err);
+// the strict "<" scan of src/ORBmatcher.cc:824-832 over one such candidate list with the descriptor the point has now (host only)
+int fuse_select_host(const int* candIdx, int candCount, int candCap, const uint8_t* kfDesc, int nKf, const uint8_t* mpDesc,
+                     int* bestIdx, int* bestDist);
 
 // SearchForTriangulation of key frame 1 against K neighbours in one launch: raw matches + rotation bins per (neighbour,
 // feature of key frame 1); the per-neighbour selection runs on the host (orbfe_triangulation_select)

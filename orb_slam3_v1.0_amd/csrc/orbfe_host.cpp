@@ -2296,6 +2296,48 @@ int orbfe_fuse_search_keyframe(orbfe_handle* h, const orbfe_keyframe* kf, const 
     return rc;
 }
 
+int orbfe_fuse_search_keyframes(orbfe_handle* h, int K, const orbfe_keyframe* const* kfs, const orbfe_frustum* frusta,
+                                const orbfe_map* map, int M, const int* ids, const uint8_t* skip, float th, int* best_idx_out,
+                                int* best_dist_out, int cand_cap, int* cand_idx_out, int* cand_count_out)
+{
+    if (!h || !map || map->h != h || K < 0 || K > 4096 || M < 0 || cand_cap < 0 || cand_cap > 16) return ORBFE_ERR_INVALID_ARG;
+    if (K > 0 && (!kfs || !frusta)) return ORBFE_ERR_INVALID_ARG;
+    if (K > 0 && M > 0 && (!ids || !best_idx_out || !best_dist_out || (cand_cap > 0 && (!cand_idx_out || !cand_count_out))))
+        return ORBFE_ERR_INVALID_ARG;
+    std::vector<const orbfe::KeyFrameDev*> kd((size_t)K);
+    for (int k = 0; k < K; k++) {
+        if (!kfs[k] || kfs[k]->device != h->device) return ORBFE_ERR_INVALID_ARG;
+        const int rc0 = frustum_validate(&frusta[k]);
+        if (rc0 != ORBFE_OK) return rc0;
+        kd[(size_t)k] = kfs[k]->k;
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    for (int k = 0; k < K; k++) {  // the single call's checks for every target, before anything is enqueued
+        if (!kd[(size_t)k]->hasGrid) {
+            h->err = "orbfe_fuse_search_keyframes: target " + std::to_string(k) + " has no grid (orbfe_keyframe_set_grid)";
+            return ORBFE_ERR_INVALID_ARG;
+        }
+        if (kd[(size_t)k]->n > 0 && M > 0 && frusta[k].n_levels > kd[(size_t)k]->nLevels) return ORBFE_ERR_INVALID_ARG;
+    }
+    if (K == 0 || M == 0) return ORBFE_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    std::string err;
+    MatchScope scope_(h, h->stream);  // also orders the call behind an orbfe_map_update of another stream's making
+    if (scope_.rc != ORBFE_OK) return scope_.rc;
+    const int rc = fuse_search_keyframes_run(h->match, h->stream, K, kd.data(), frusta, map->cap, map->dPts, map->dDesc, M, ids, skip, th,
+                                             best_idx_out, best_dist_out, cand_cap, cand_idx_out, cand_count_out, err);
+    if (rc != ORBFE_OK) h->err = err;
+    return rc;
+}
+
+int orbfe_fuse_select(const int* cand_idx, int cand_count, int cand_cap, const uint8_t* kf_desc, int n_kf, const uint8_t* mp_desc,
+                      int* best_idx, int* best_dist)
+{
+    if (!best_idx || !best_dist || cand_count < 0 || cand_cap < 0 || cand_cap > 16 || n_kf < 0 || !mp_desc) return ORBFE_ERR_INVALID_ARG;
+    if (cand_count > 0 && cand_count <= cand_cap && (!cand_idx || !kf_desc)) return ORBFE_ERR_INVALID_ARG;
+    return fuse_select_host(cand_idx, cand_count, cand_cap, kf_desc, n_kf, mp_desc, best_idx, best_dist);
+}
+
 int orbfe_match_triangulation_batch(orbfe_handle* h, const orbfe_keyframe* kf1, const uint8_t* has_mp1, int K,
                                     const orbfe_keyframe* const* kf2, const uint8_t* const* has_mp2,
                                     const orbfe_tri_params* params, int* raw_match12, uint8_t* raw_bin)

@@ -158,7 +158,7 @@ SYMBOLS = [
     "orbfe_keyframe_create", "orbfe_keyframe_destroy", "orbfe_keyframe_size", "orbfe_match_triangulation_batch",
     "orbfe_triangulation_select", "orbfe_create_new_points_batch", "orbfe_triangulate_pairs", "orbfe_map_create", "orbfe_map_destroy", "orbfe_map_update", "orbfe_stream_enable_track",
     "orbfe_stream_submit_track", "orbfe_stream_collect_track", "orbfe_track_frame_map", "orbfe_track_reference_keyframe", "orbfe_debug_graph_stats", "orbfe_set_graph_capture",
-    "orbfe_debug_clock_probe", "orbfe_keyframe_set_grid", "orbfe_fuse_search_keyframe",
+    "orbfe_debug_clock_probe", "orbfe_keyframe_set_grid", "orbfe_fuse_search_keyframe", "orbfe_fuse_search_keyframes", "orbfe_fuse_select",
     "orbfe_init_frame_create", "orbfe_init_frame_destroy", "orbfe_init_frame_size", "orbfe_track_initialization",
     "orbfe_set_stream_priority",
     "orbfe_shard_range", "orbfe_pool_create", "orbfe_pool_destroy", "orbfe_pool_size", "orbfe_pool_member",
@@ -272,6 +272,8 @@ def lib():
     L.orbfe_keyframe_size.argtypes = [vp]
     L.orbfe_keyframe_set_grid.argtypes = [vp, vp, ci, ci, cf, cf, cf, cf, vp, vp]
     L.orbfe_fuse_search_keyframe.argtypes = [vp, vp, vp, ci, vp, C.POINTER(Frustum), cf, vp, vp]
+    L.orbfe_fuse_search_keyframes.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, cf, vp, vp, ci, vp, vp]
+    L.orbfe_fuse_select.argtypes = [vp, ci, ci, vp, ci, vp, C.POINTER(ci), C.POINTER(ci)]
     L.orbfe_match_triangulation_batch.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, vp]
     L.orbfe_triangulation_select.argtypes = [ci, vp, vp, vp, ci, vp, vp]
     if hasattr(L, "orbfe_create_new_points_batch"):  # an earlier build loaded for an A/B (bench.py --lib tools/ab/...) lacks the two
@@ -836,6 +838,33 @@ class ORBmatcher:
                     "orbfe_fuse_search_keyframe")
         return bi[:M], bd[:M]
 
+    def Fuse_search_keyframes(self, kfs, map_points, ids, frusta, th, skip=None, cand_cap=0):
+        """orbfe_fuse_search_keyframes: Fuse_search_keyframe into all K targets of one SearchInNeighbors loop in ONE submission.
+        kfs / frusta: K resident KeyFrames (set_grid done) and their Frustums; ids: M entries of the map; skip: (K, M) flags
+        "!pMP || pMP->IsInKeyFrame(pKFk)" or None.  -> (bestIdx, bestDist) shaped (K, M); with cand_cap > 0 also
+        (candIdx (K, M, cand_cap), candCount (K, M)): the features that passed every gate, in visit order, for fuse_select."""
+        ids = np.ascontiguousarray(ids, np.int32)
+        K, M = len(kfs), len(ids)
+        assert len(frusta) == K
+        fr = (Frustum * max(K, 1))()
+        for k in range(K):
+            C.memmove(C.byref(fr, k * C.sizeof(Frustum)), C.byref(frusta[k]), C.sizeof(Frustum))
+        hs = (C.c_void_p * max(K, 1))(*[kf.h.value for kf in kfs])
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, np.uint8)
+            assert skip.shape == (K, M)
+        n = max(K * M, 1)
+        bi = np.zeros(n, np.int32)
+        bd = np.zeros(n, np.int32)
+        ci_ = np.zeros(n * max(cand_cap, 1), np.int32)
+        cc = np.zeros(n, np.int32)
+        self.e._chk(self.L.orbfe_fuse_search_keyframes(self.e.h, K, hs, fr, map_points.h, M, _p(ids), _p(skip), th, _p(bi), _p(bd),
+                                                       cand_cap, _p(ci_), _p(cc)), "orbfe_fuse_search_keyframes")
+        out = bi[:K * M].reshape(K, M), bd[:K * M].reshape(K, M)
+        if cand_cap > 0:
+            out += (ci_[:K * M * cand_cap].reshape(K, M, cand_cap), cc[:K * M].reshape(K, M))
+        return out
+
     def Fuse_search_right(self, kf_left_view, nRight, invLevelSigma2, uRight, frustum, th, points, mpDesc):
         """Fuse(pKF, vpMapPoints, th, bRight = true) (src/ORBmatcher.cc:684-688,:820): kf_left_view describes the NLeft left
         features with desc = all NLeft + nRight rows of mDescriptors; frustum = right pose / mpCamera2; returned indices are
@@ -1052,6 +1081,21 @@ def triangulation_select(raw_match12, raw_bin, hasMP1_now, checkOrientation=True
     if rc != 0:
         raise OrbfeError(rc, "orbfe_triangulation_select")
     return n.value, out[:len(raw)]
+
+
+def fuse_select(cand_idx, cand_count, cand_cap, kf_desc, mp_desc):
+    """orbfe_fuse_select (host only): the strict "<" scan of src/ORBmatcher.cc:824-832 for one pair over a candidate list of
+    ORBmatcher.Fuse_search_keyframes, with the descriptor the point has NOW -> (bestIdx, bestDist).  Raises OrbfeError
+    (ORBFE_ERR_UNSUPPORTED) when the list is truncated (cand_count > cand_cap)."""
+    cand_idx = np.ascontiguousarray(cand_idx, np.int32)
+    kf_desc = np.ascontiguousarray(kf_desc, np.uint8)
+    mp_desc = np.ascontiguousarray(mp_desc, np.uint8)
+    bi, bd = C.c_int(-1), C.c_int(256)
+    rc = lib().orbfe_fuse_select(_p(cand_idx), int(cand_count), int(cand_cap), _p(kf_desc), len(kf_desc), _p(mp_desc), C.byref(bi),
+                                 C.byref(bd))
+    if rc != 0:
+        raise OrbfeError(rc, "orbfe_fuse_select")
+    return bi.value, bd.value
 
 
 class FrameTracker:
