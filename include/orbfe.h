@@ -190,7 +190,10 @@ int orbfe_debug_get_candidates(orbfe_handle *h, int frame, int level, uint32_t *
  * one event per stage boundary (a pool of 128 event sets; enabling resets the pool).
  * orbfe_get_stage_ms() synchronises on the recorded events and returns, per stage in the order of
  * orbfe_stage_name(), the SUM of elapsed milliseconds over the recorded calls; *n_calls receives
- * how many calls were summed (<= 128).  The last stage is the whole chain ("total"). */
+ * how many calls were summed (<= 128).  The last stage is the whole chain ("total").
+ * A launch that takes the fused level build (one FAST launch per level that also writes the next
+ * level; liborbfe_diag.so with ORBFE_FUSED_PYRAMID=1 only, as shipped no launch does) has no pyramid
+ * launches: its "pyramid_resize" reads ~0 and "fast_nms_blur" covers the per-level launches. */
 #define ORBFE_NUM_STAGES 5
 int orbfe_set_stage_timing(orbfe_handle *h, int enabled);
 int orbfe_get_stage_ms(orbfe_handle *h, float ms[ORBFE_NUM_STAGES], int *n_calls);

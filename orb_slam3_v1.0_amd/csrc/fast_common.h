@@ -8,6 +8,13 @@ namespace orbfe {
 
 constexpr int kFastTW = 64, kFastTH = 32;  // FAST tile (pixels)
 
+// Launches of at least this many frames build pyramid level l+1 inside the FAST launch of level l (one FAST launch per
+// level, no pyramid launches: extract_chain); 0 = no launch does.  Measured at 512 frames of 752x480 the fused build costs
+// the FAST kernel 0.46 ms against the 0.42 ms of the seven pyramid launches it removes plus 0.06 ms for the split into
+// eight launches (profiles/r09_fused_pyramid_ab.json), so the shipped library keeps the pyramid
+// kernels at every size; liborbfe_diag.so forces either form with ORBFE_FUSED_PYRAMID.
+constexpr int kFusedPyramidMinFrames = 0;
+
 // 16-bit circular mask contains >= 9 contiguous ones (== c_table lookup, src/cuda/Fast_gpu.cu:187-191)
 __device__ __forceinline__ bool arc9(uint32_t m)
 {

@@ -30,7 +30,7 @@
 //            register window (three byte loads + nine fast instructions per pixel); survivors (~20 % of the
 //            positions) go to an LDS queue through a hand-scheduled compaction step;
 //   stage B  segment test + corner score of one queued pixel per lane: the sixteen 9-arcs of both polarities by
-//            prefix / suffix minima over the ring halves (42 v_min_u16 + 15 v_max_u16 per polarity);
+//            pairwise-shared arc cores (32 v_min_u16 + 15 v_max_u16 per polarity);
 //   stage C  NMS + compaction over the dense corner queue.
 // Candidate order in HBM is not deterministic (one atomicAdd per block reserves the slots) -- every
 // consumer is order-independent: it uses the raster key (y, x) carried in the word (S2b).
@@ -162,73 +162,34 @@ __device__ __forceinline__ uint32_t maxi16(uint32_t a, uint32_t b)  // signed
 }
 
 // max over the sixteen 9-arcs of the arc minimum of ONE pixel's ring p[0..15] (values 0..255).  Arc k = ring positions
-// k..k+8.  With S[k] = min(p[k..7]), S'[k] = min(p[k..15]), P[k] = min(p[8..k]), P'[k] = min(p[0..k]):  arc k =
-// min(S[k], P[k+8]) for k < 8 and min(S'[k], P'[k-8]) for k >= 8 -- 26 + 16 two-input minima, then 15 maxima
-// (42 v_min_u16 + 15 v_max_u16).
-__device__ __forceinline__ uint32_t arc_max_of_min(const uint32_t (&p)[16])
+// k..k+8 (indices mod 16).  Arcs k and k+1 share core_k = min(p[k+1..k+8]), and
+// max(min(core, p[k]), min(core, p[k+9])) = min(core, max(p[k], p[k+9])), so for the eight even k: 8 pair minima at odd
+// starts, 8 quad minima, 8 octet minima (= the eight cores), 8 maxima max(p[k], p[k+9]), 8 minima and 7 maxima to
+// reduce -- 47 two-input operations (32 v_min_u16 + 15 v_max_u16) against 57 for prefix / suffix minima over the ring halves.
+// DARK exchanges min and max: min over the arcs of the arc maximum.
+template <bool DARK>
+__device__ __forceinline__ uint32_t arc_extreme(const uint32_t (&p)[16])
 {
-    uint32_t S[16], Pf[16];
-    S[7] = p[7];
-    S[15] = p[15];
+    auto lo = [](uint32_t a, uint32_t b) { return DARK ? max16(a, b) : min16(a, b); };
+    auto hi = [](uint32_t a, uint32_t b) { return DARK ? min16(a, b) : max16(a, b); };
+    uint32_t m2[8], m4[8], a[8];
 #pragma unroll
-    for (int k = 6; k >= 0; k--) {
-        S[k] = min16(p[k], S[k + 1]);
-        S[k + 8] = min16(p[k + 8], S[k + 9]);
-    }
-    Pf[0] = p[0];
-    Pf[8] = p[8];
+    for (int j = 0; j < 8; j++) m2[j] = lo(p[2 * j + 1], p[(2 * j + 2) & 15]);        // p[2j+1 .. 2j+2]
 #pragma unroll
-    for (int k = 1; k < 7; k++) {
-        Pf[k] = min16(p[k], Pf[k - 1]);
-        Pf[k + 8] = min16(p[k + 8], Pf[k + 7]);
-    }
-    Pf[7] = S[0];
-    Pf[15] = S[8];
-    uint32_t a[16];
+    for (int j = 0; j < 8; j++) m4[j] = lo(m2[j], m2[(j + 1) & 7]);                   // p[2j+1 .. 2j+4]
 #pragma unroll
-    for (int k = 0; k < 8; k++) {
-        a[k] = min16(S[k], Pf[k + 8]);
-        a[k + 8] = min16(S[k + 8], Pf[k]);
+    for (int j = 0; j < 8; j++) {
+        const uint32_t core = lo(m4[j], m4[(j + 2) & 7]);                            // p[2j+1 .. 2j+8] = core of arcs 2j, 2j+1
+        a[j] = lo(core, hi(p[2 * j], p[(2 * j + 9) & 15]));
     }
 #pragma unroll
-    for (int st = 8; st >= 1; st >>= 1)
+    for (int st = 4; st >= 1; st >>= 1)
 #pragma unroll
-        for (int k = 0; k < st; k++) a[k] = max16(a[k], a[k + st]);
+        for (int k = 0; k < st; k++) a[k] = hi(a[k], a[k + st]);
     return a[0];
 }
-
-// the dark polarity: min over the sixteen 9-arcs of the arc maximum (the same scheme with min / max exchanged)
-__device__ __forceinline__ uint32_t arc_min_of_max(const uint32_t (&p)[16])
-{
-    uint32_t S[16], Pf[16];
-    S[7] = p[7];
-    S[15] = p[15];
-#pragma unroll
-    for (int k = 6; k >= 0; k--) {
-        S[k] = max16(p[k], S[k + 1]);
-        S[k + 8] = max16(p[k + 8], S[k + 9]);
-    }
-    Pf[0] = p[0];
-    Pf[8] = p[8];
-#pragma unroll
-    for (int k = 1; k < 7; k++) {
-        Pf[k] = max16(p[k], Pf[k - 1]);
-        Pf[k + 8] = max16(p[k + 8], Pf[k + 7]);
-    }
-    Pf[7] = S[0];
-    Pf[15] = S[8];
-    uint32_t a[16];
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        a[k] = max16(S[k], Pf[k + 8]);
-        a[k + 8] = max16(S[k + 8], Pf[k]);
-    }
-#pragma unroll
-    for (int st = 8; st >= 1; st >>= 1)
-#pragma unroll
-        for (int k = 0; k < st; k++) a[k] = min16(a[k], a[k + st]);
-    return a[0];
-}
+__device__ __forceinline__ uint32_t arc_max_of_min(const uint32_t (&p)[16]) { return arc_extreme<false>(p); }
+__device__ __forceinline__ uint32_t arc_min_of_max(const uint32_t (&p)[16]) { return arc_extreme<true>(p); }
 
 // lane mask of th < (signed 16-bit) m, into an SGPR pair (the e64 compare; VCC stays free)
 __device__ __forceinline__ unsigned long long mask_th_i16(int th, uint32_t m)
@@ -265,9 +226,18 @@ __device__ __forceinline__ int queue_slot1(uint32_t m, int th, unsigned long lon
 // MODE is a timing-only ablation switch (bit 0 = Gaussian, bit 1 = FAST, bit 2 = stop after stage A, bit 3 = stop
 // after stage B); the shipped library instantiates MODE 3 only -- the other variants exist in the -DORBFE_ABLATION
 // build (`make ablation`) used by tools/fast_stage_*.sh.
-template <int MODE>
+//
+// BUILD: the block also writes the pixels of the NEXT unblurred pyramid level that its tile owns:
+// level l+1 is the bilinear resize of the unblurred level l (S1, kernels_pyramid.hip), pixel (X, Y) reads source columns
+// x1, x1 + 1 and rows y1, y1 + 1 (x1 | wx << 16 from the level's tables), and the tile that contains (x1, y1) owns it --
+// both far taps then lie in the tile's staged halo, so the level is built from LDS without a global load.  Ownership is
+// a partition of level l+1 (`own` tables, orbfe_create: first owned column per tile column, first owned row per tile
+// row).  Launched one level at a time (tileBase = first tile of the level): level l+1 is complete when its own launch
+// starts, by stream order alone.
+template <int MODE, bool BUILD>
 __global__ __launch_bounds__(256) void fast_blur_kernel(const PipelineDesc* __restrict__ P,
-                                                        const uint32_t* __restrict__ tileInfo,
+                                                        const uint32_t* __restrict__ tileInfo, int tileBase,
+                                                        const uint32_t* __restrict__ tabs,
                                                         const uint8_t* __restrict__ gray0, size_t gray0FrameStride,
                                                         int gray0Pitch, int gray0Aligned4,
                                                         uint8_t* __restrict__ ws, uint32_t* __restrict__ cand,
@@ -291,7 +261,7 @@ __global__ __launch_bounds__(256) void fast_blur_kernel(const PipelineDesc* __re
     __shared__ uint32_t sQ[3];  // entries of queue A by wave 0 / wave 1, corner-queue entries
 
     const int f = blockIdx.x;
-    const int tile = blockIdx.y;
+    const int tile = (int)blockIdx.y + tileBase;
     const int nL = P->nLevels;
     // tile -> (level, tile column, tile row) from one scalar load (host table, orbfe_create)
     const uint32_t ti = tileInfo[tile];
@@ -320,6 +290,22 @@ __global__ __launch_bounds__(256) void fast_blur_kernel(const PipelineDesc* __re
     if (tid < 4) sCnt[tid] = 0;
     if (tid < 3) sQ[tid] = 0;
     if (tid < kFastTH) sRow[tid] = 0;
+
+    // BUILD: the table entries of the pixels of level l+1 this tile owns (columns bXa .. bXa + bNX - 1, lane = column; rows
+    // bYa .. bYa + bNY - 1, lane = row) are requested in front of the staging loads and used behind the staging barrier
+    int bXa = 0, bNX = 0, bYa = 0, bNY = 0;
+    uint32_t bXt = 0, bYt = 0;
+    if constexpr (BUILD) {
+        const uint32_t* own = tabs + L.ownOff;
+        const int tX = (int)(ti & 0xfffu), tY = (int)((ti >> 12) & 0xfffu);
+        bXa = (int)own[tX];
+        bNX = (int)own[tX + 1] - bXa;
+        bYa = (int)own[L.tilesX + 1 + tY];
+        bNY = (int)own[L.tilesX + 2 + tY] - bYa;
+        const LevelDesc& D = P->lv[l + 1];
+        if (lane < bNX) bXt = tabs[D.xtabOff + (size_t)(bXa + lane)];
+        if (lane < bNY) bYt = tabs[D.ytabOff + (size_t)(bYa + lane)];
+    }
 
     // ---- stage the 72 x 40 tile (origin x0-4, y0-4).  Thread -> fixed dword column c4 (18 per row) and
     //      rows r0, r0+14, r0+28: the three loads are issued back to back.  Rows outside the level follow
@@ -389,11 +375,41 @@ __global__ __launch_bounds__(256) void fast_blur_kernel(const PipelineDesc* __re
     }
     __syncthreads();
 
+    if constexpr (BUILD) {
+        // ================= next unblurred level (S1), from the staged tile =================
+        // lane = owned output column (at most 64: x1 is strictly increasing), wave q takes the owned rows q, q + 4, ...:
+        // every pixel on its own -- four byte reads, the arithmetic of resize_kernel (Q11 weights, one rounding
+        // (v + 2^21) >> 22, every product below 2^24 operands) and a byte store; the reads of a wave's rows are issued together.
+        // Rows past the tile's last owned row are evaluated on that row and not stored (wave-uniform).
+        static_assert(kFastTH == 32, "eight owned rows per wave at most");
+        const LevelDesc& D = P->lv[l + 1];
+        if (lane < bNX && bNY > 0) {
+            const uint32_t wx = bXt >> 16, wxc = 2048u - wx;
+            const uint8_t* sp = &sImg[0][0] + ((int)(bXt & 0xffffu) - (x0 - 4));  // staged (row y0 - 4, column x1)
+            uint8_t* dcol = ws + D.imgOff + (size_t)f * D.imgFrameStride + (uint32_t)(bYa * D.pitch + bXa + lane);
+            const int q = __builtin_amdgcn_readfirstlane(tid >> 6);
+            uint32_t top[8], bot[8], wy[8];
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                const uint32_t yt = (uint32_t)__builtin_amdgcn_readlane((int)bYt, min(q + 4 * k, bNY - 1));
+                const uint8_t* pr = sp + ((int)(yt & 0xffffu) - (y0 - 4)) * kImgW;
+                wy[k] = yt >> 16;
+                top[k] = __umul24(pr[0], wxc) + __umul24(pr[1], wx);
+                bot[k] = __umul24(pr[kImgW], wxc) + __umul24(pr[kImgW + 1], wx);
+            }
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                const uint32_t v = __umul24(top[k], 2048u - wy[k]) + __umul24(bot[k], wy[k]) + (1u << 21);
+                if (q + 4 * k < bNY) dcol[(uint32_t)((q + 4 * k) * D.pitch)] = (uint8_t)(v >> 22);
+            }
+        }
+    }
+
     if constexpr ((MODE & 1) != 0) {
     // ================= Gaussian 5x5 of the tile (S1) =================
     // horizontal: item = (row pair j, 4 output columns xl..xl+3); output column x of tmp row rr (image
-    // row y0-2+rr) taps LDS cols x+2..x+6.  Byte windows via v_alignbyte, 4 taps per v_dot4_u32_u8:
-    // o = dot4(bytes x+2..x+5, {22,62,88,62}) + dot4(bytes x+3..x+6, {0,0,0,22})  (<= 65280).
+    // row y0-2+rr) taps LDS cols x+2..x+6: two v_dot4_u32_u8 per output on the aligned dwords w0 w1 w2 of the item, e.g.
+    // o0 = dot4(w0, {0,0,22,62}) + dot4(w1, {88,62,22,0})  (<= 65280).
     // sTmp holds row PAIRS: dword [j][x] = tmp row 2j (low half) | tmp row 2j+1 (high half), so the vertical
     // pass is three v_dot2_u32_u16 per output.
     for (int e = tid; e < (kTmpH / 2) * (kFastTW / 4); e += 256) {
@@ -404,16 +420,12 @@ __global__ __launch_bounds__(256) void fast_blur_kernel(const PipelineDesc* __re
         for (int half = 0; half < 2; half++) {
             const uint32_t* rowp = reinterpret_cast<const uint32_t*>(&sImg[2 * j + half + 2][xl]);
             const uint32_t w0 = rowp[0], w1 = rowp[1], w2 = rowp[2];
-            uint32_t win[5];
-            win[0] = __builtin_amdgcn_alignbyte(w1, w0, 2);  // bytes 2..5
-            win[1] = __builtin_amdgcn_alignbyte(w1, w0, 3);  // bytes 3..6
-            win[2] = w1;                                     // bytes 4..7
-            win[3] = __builtin_amdgcn_alignbyte(w2, w1, 1);  // bytes 5..8
-            win[4] = __builtin_amdgcn_alignbyte(w2, w1, 2);  // bytes 6..9
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-                o[half][i] = __builtin_amdgcn_udot4(win[i + 1], 0x16000000u,
-                                                    __builtin_amdgcn_udot4(win[i], 0x3E583E16u, 0u, false), false);
+            // output i taps bytes i + 2 .. i + 6 of the three dwords: with the taps shifted inside the constants the aligned
+            // dwords serve directly (no v_alignbyte byte windows)
+            o[half][0] = __builtin_amdgcn_udot4(w1, 0x00163E58u, __builtin_amdgcn_udot4(w0, 0x3E160000u, 0u, false), false);
+            o[half][1] = __builtin_amdgcn_udot4(w1, 0x163E583Eu, __builtin_amdgcn_udot4(w0, 0x16000000u, 0u, false), false);
+            o[half][2] = __builtin_amdgcn_udot4(w2, 0x00000016u, __builtin_amdgcn_udot4(w1, 0x3E583E16u, 0u, false), false);
+            o[half][3] = __builtin_amdgcn_udot4(w2, 0x0000163Eu, __builtin_amdgcn_udot4(w1, 0x583E1600u, 0u, false), false);
         }
         uint4 pk;
         pk.x = o[0][0] | (o[1][0] << 16);
@@ -730,17 +742,44 @@ void fast_tiles_for(int w, int h, int* tx, int* ty)
     *ty = (h + kFastTH - 1) / kFastTH;
 }
 
+bool fast_next_level_fits(const uint32_t* xtab, const uint32_t* ytab, int sw, int sh, int dw, int dh, uint32_t* own)
+{
+    int tx, ty;
+    fast_tiles_for(sw, sh, &tx, &ty);
+    bool ok = true;
+    // x1 / y1 never decrease along a table: tile t owns the pixels from the first one whose tap lies in or behind it
+    // up to the first one of tile t + 1
+    auto fill = [&](const uint32_t* tab, int srcN, int dstN, int tile, int nTiles, uint32_t* o) {
+        int p = 0;
+        for (int t = 0; t <= nTiles; t++) {
+            while (p < dstN && (int)(tab[p] & 0xffffu) < t * tile) p++;
+            o[t] = (uint32_t)(t == nTiles ? dstN : p);
+            if (t > 0 && o[t] - o[t - 1] > 64u) ok = false;
+        }
+        for (int i = 0; i < dstN; i++)
+            if ((int)(tab[i] & 0xffffu) + 1 > srcN - 1 || (i > 0 && (tab[i] & 0xffffu) < (tab[i - 1] & 0xffffu))) ok = false;
+    };
+    fill(xtab, sw, dw, kFastTW, tx, own);
+    fill(ytab, sh, dh, kFastTH, ty, own + tx + 1);
+    return ok;
+}
+
 uint32_t fast_tile_info(int level, int tileX, int tileY) { return ((uint32_t)level << 24) | ((uint32_t)tileY << 12) | (uint32_t)tileX; }
 
-void launch_fast_blur(hipStream_t s, int frames, int totalTiles, const PipelineDesc* dP, const uint32_t* dTileInfo,
-                      const uint8_t* gray0, size_t gray0FrameStride, int gray0Pitch, int gray0Aligned4, uint8_t* ws,
-                      uint32_t* cand, uint32_t* counters, uint16_t* tileRows)
+void launch_fast_blur(hipStream_t s, int frames, int tileBase, int nTiles, bool buildNext, const PipelineDesc* dP,
+                      const uint32_t* dTileInfo, const uint32_t* dTabs, const uint8_t* gray0, size_t gray0FrameStride, int gray0Pitch,
+                      int gray0Aligned4, uint8_t* ws, uint32_t* cand, uint32_t* counters, uint16_t* tileRows)
 {
     dim3 block(256);
-    dim3 grid(frames, totalTiles);
-#define ORBFE_LAUNCH_FB(M)                                                                                          \
-    hipLaunchKernelGGL(fast_blur_kernel<M>, grid, block, 0, s, dP, dTileInfo, gray0, gray0FrameStride, gray0Pitch, \
-                       gray0Aligned4, ws, cand, counters, tileRows)
+    dim3 grid(frames, nTiles);
+    if (buildNext) {
+        hipLaunchKernelGGL((fast_blur_kernel<3, true>), grid, block, 0, s, dP, dTileInfo, tileBase, dTabs, gray0, gray0FrameStride,
+                           gray0Pitch, gray0Aligned4, ws, cand, counters, tileRows);
+        return;
+    }
+#define ORBFE_LAUNCH_FB(M)                                                                                                      \
+    hipLaunchKernelGGL((fast_blur_kernel<M, false>), grid, block, 0, s, dP, dTileInfo, tileBase, dTabs, gray0, gray0FrameStride, \
+                       gray0Pitch, gray0Aligned4, ws, cand, counters, tileRows)
 #ifdef ORBFE_ABLATION
     // timing-only build (liborbfe_ablation.so, `make ablation`): ORBFE_FAST_MODE selects a truncated kernel whose
     // RESULTS ARE WRONG unless it is 3.  The shipped library does not contain these variants and reads no variable.

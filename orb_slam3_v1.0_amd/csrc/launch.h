@@ -22,9 +22,15 @@ void launch_pyramid_chain(hipStream_t s, int frames, const PipelineDesc* dP, con
 // kernels_fast.hip (FAST + NMS + compaction fused with the Gaussian blur of the same tile)
 void fast_tiles_for(int w, int h, int* tx, int* ty);
 uint32_t fast_tile_info(int level, int tileX, int tileY);  // entry of the per-tile table (level << 24 | ty << 12 | tx)
-void launch_fast_blur(hipStream_t s, int frames, int totalTiles, const PipelineDesc* dP, const uint32_t* dTileInfo,
-                      const uint8_t* gray0, size_t gray0FrameStride, int gray0Pitch, int gray0Aligned4, uint8_t* ws,
-                      uint32_t* cand, uint32_t* counters, uint16_t* tileRows);
+// tiles tileBase .. tileBase + nTiles - 1 of the per-tile table; buildNext: the tiles (all of ONE level l) also write the
+// unblurred level l+1 (fast_next_level_fits must hold for it)
+void launch_fast_blur(hipStream_t s, int frames, int tileBase, int nTiles, bool buildNext, const PipelineDesc* dP,
+                      const uint32_t* dTileInfo, const uint32_t* dTabs, const uint8_t* gray0, size_t gray0FrameStride, int gray0Pitch,
+                      int gray0Aligned4, uint8_t* ws, uint32_t* cand, uint32_t* counters, uint16_t* tileRows);
+// fills own[0 .. tilesX] / own[tilesX + 1 .. tilesX + tilesY + 1] (first pixel of the dw x dh level owned by each tile column /
+// row of the sw x sh level) and says whether the FAST kernel can build the level: no clamped far tap and at most 64 owned
+// columns and rows per tile
+bool fast_next_level_fits(const uint32_t* xtab, const uint32_t* ytab, int sw, int sh, int dw, int dh, uint32_t* own);
 
 // kernels_quadtree.hip
 int quadtree_node_capacity(int maxNodeCap);

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "launch.h"
+#include "fast_common.h"
 #include "match.h"
 #include "match_common.h"
 #include "match_proj.h"
@@ -66,6 +67,9 @@ struct orbfe_handle {
     uint32_t* dTabs = nullptr;      // resize tables
     uint32_t* dTileInfo = nullptr;  // FAST tile -> (level, tile column, tile row)
     bool pyrFits[kMaxLevels]{};     // level is produced by the row-streaming pyramid kernel (else: the table-driven tile kernel)
+    bool fusedFits[kMaxLevels]{};   // large launches: level is written by the FAST launch of the level below it
+    int fusedMinFrames = kFusedPyramidMinFrames;  // launches of at least this many frames take the fused level build (0: none)
+    bool fusedSplitOnly = false;    // liborbfe_diag.so: one FAST launch per level behind the pyramid launches (what do the launches cost?)
     float* dSf = nullptr;           // mvScaleFactor on the device (batched matcher)
 
     // staging for the host-pointer API
@@ -411,6 +415,9 @@ int orbfe_create(const orbfe_params* p, orbfe_handle** out)
         tabOff += align_up((size_t)L.w, 4);
         L.ytabOff = tabOff;
         tabOff += align_up((size_t)L.h, 4);
+        tabOff = align_up(tabOff, 4);
+        L.ownOff = (uint32_t)tabOff;  // ownership tables of the fused level build (filled below)
+        tabOff += (size_t)L.tilesX + L.tilesY + 2;
         h->maxNodeCap = std::max(h->maxNodeCap, L.nodeCap);
     }
     if (status == ORBFE_OK && quadtree_node_capacity(h->maxNodeCap) == 0) status = ORBFE_ERR_UNSUPPORTED;  // > 65535 nodes/level
@@ -434,6 +441,10 @@ int orbfe_create(const orbfe_params* p, orbfe_handle** out)
         if (pyramid_level_fits(tabs.data() + P.lv[l].xtabOff, tabs.data() + P.lv[l].ytabOff, P.lv[l - 1].w, P.lv[l - 1].h, P.lv[l].w,
                                P.lv[l].h))
             h->pyrFits[l] = true;
+    // the fused build takes the levels the row-streaming kernel takes (no clamped far tap) whose tiles own at most 64 columns
+    for (int l = 1; l < nL; l++)
+        h->fusedFits[l] = fast_next_level_fits(tabs.data() + P.lv[l].xtabOff, tabs.data() + P.lv[l].ytabOff, P.lv[l - 1].w, P.lv[l - 1].h,
+                                               P.lv[l].w, P.lv[l].h, tabs.data() + P.lv[l - 1].ownOff) && h->pyrFits[l];
 
 #define CREATE_CHK(call)                                                  \
     do {                                                                  \
@@ -499,6 +510,12 @@ int orbfe_create(const orbfe_params* p, orbfe_handle** out)
     h->hDesc = h->hOutBlock + h->offDesc;
 #ifdef ORBFE_DIAG
     h->useGraph = getenv("ORBFE_NO_GRAPH") == nullptr;  // liborbfe_diag.so only: plain launches, e.g. under a debugger
+    // liborbfe_diag.so only: ORBFE_FUSED_PYRAMID=1 forces the fused level build on every launch, =0 never takes it, =2 keeps
+    // the pyramid launches and only splits FAST into one launch per level (timing experiment)
+    if (const char* e = getenv("ORBFE_FUSED_PYRAMID")) {
+        h->fusedMinFrames = atoi(e) ? 1 : 0;
+        h->fusedSplitOnly = atoi(e) == 2;
+    }
 #endif
     CREATE_CHK(hipEventCreateWithFlags(&h->evExtract, hipEventDisableTiming));
     CREATE_CHK(hipEventCreateWithFlags(&h->evMatch, hipEventDisableTiming));
@@ -615,7 +632,9 @@ static int extract_chain(orbfe_handle* h, const uint8_t* d_gray, size_t frame_st
         h->evHead = (h->evHead + 1) % kEventSets;
         h->evCount++;
     }
-    const bool chainPyr = (long long)batch * nL <= 64 && !ev && nL > 1;  // one to eight frames: see below
+    // fused level build: no pyramid launches, one FAST launch per level that also writes the next level (kernels_fast.hip)
+    const bool fused = h->fusedMinFrames > 0 && batch >= h->fusedMinFrames && nL > 1;
+    const bool chainPyr = !fused && (long long)batch * nL <= 64 && !ev && nL > 1;  // one to eight frames: see below
     if (!chainPyr) HIPCHK(h, hipMemsetAsync(h->dCounters, 0, (size_t)batch * nL * kCntWords * sizeof(uint32_t), s));
     if (ev) HIPCHK(h, hipEventRecord(ev[0], s));
     // ComputePyramid (:607-623): level l from the UNBLURRED level l-1
@@ -627,22 +646,32 @@ static int extract_chain(orbfe_handle* h, const uint8_t* d_gray, size_t frame_st
                              l == 1 ? h->dCounters : nullptr, nL * kCntWords);  // the first launch clears the level counters
         l += depth;
     }
-    for (int l = chainPyr ? nL : 1; l < nL; l++) {
+    auto pyramid_level = [&](int l) {
         const LevelDesc& S = P.lv[l - 1];
         const LevelDesc& D = P.lv[l];
         if (h->pyrFits[l] && (l > 1 || aligned4)) {
             launch_pyramid_level(s, batch, h->dP, l, D.w, D.h, d_gray, frame_stride, pitch, h->ws, h->dTabs);
-            continue;
+            return;
         }
         const uint8_t* src = l == 1 ? d_gray : h->ws + S.imgOff;
         const size_t sstride = l == 1 ? frame_stride : S.imgFrameStride;
         const int spitch = l == 1 ? pitch : S.pitch;
         launch_resize(s, batch, src, sstride, S.w, S.h, spitch, l == 1 ? aligned4 : 1, h->ws + D.imgOff, D.imgFrameStride, D.w, D.h,
                       D.pitch, h->dTabs + D.xtabOff, h->dTabs + D.ytabOff);
+    };
+    for (int l = chainPyr || (fused && !h->fusedSplitOnly) ? nL : 1; l < nL; l++) pyramid_level(l);
+    if (ev) HIPCHK(h, hipEventRecord(ev[1], s));  // fused: nothing in front of it, the FAST stage covers the level build
+    if (fused) {
+        for (int l = 0; l < nL; l++) {
+            const bool build = l + 1 < nL && h->fusedFits[l + 1] && !h->fusedSplitOnly;
+            launch_fast_blur(s, batch, P.lv[l].tileBase, P.lv[l].tilesX * P.lv[l].tilesY, build, h->dP, h->dTileInfo, h->dTabs, d_gray,
+                             frame_stride, pitch, aligned4, h->ws, h->dCand, h->dCounters, h->dTileRows);
+            if (l + 1 < nL && !build && !h->fusedSplitOnly) pyramid_level(l + 1);  // a level the tiles cannot build: its own launch, from level l
+        }
+    } else {
+        launch_fast_blur(s, batch, 0, P.totalTiles, false, h->dP, h->dTileInfo, h->dTabs, d_gray, frame_stride, pitch, aligned4, h->ws,
+                         h->dCand, h->dCounters, h->dTileRows);
     }
-    if (ev) HIPCHK(h, hipEventRecord(ev[1], s));
-    launch_fast_blur(s, batch, P.totalTiles, h->dP, h->dTileInfo, d_gray, frame_stride, pitch, aligned4, h->ws, h->dCand, h->dCounters,
-                     h->dTileRows);
     if (ev) HIPCHK(h, hipEventRecord(ev[2], s));
     launch_quadtree(s, batch, nL, h->maxNodeCap, h->dP, h->dCand, h->dNodeOf, h->dCounters, h->dLvlKp, d_gray, frame_stride,
                     pitch, h->ws, h->dTileRows, h->dQtScratch);

@@ -81,7 +81,8 @@ struct LevelDesc {
     int kpBase;               // first slot of this level in the per-frame level-keypoint array
     float invScale;           // mvInvScaleFactor[l]
     int scaledPatch;          // (int)(31 * invScale)
-    uint32_t pad_;
+    uint32_t ownOff;          // u32 index of the level's ownership tables (fused level build, kernels_fast.hip): tilesX + 1 first
+                              // owned columns of level l+1, then tilesY + 1 first owned rows
     size_t imgOff;            // byte offset of frame 0's unblurred level image in the workspace
     size_t imgFrameStride;    // bytes between consecutive frames of this level
     size_t blurOff, blurFrameStride;

@@ -130,7 +130,9 @@ for k, cs in grbm.items():
         kern[k]["effective_clock_mhz"] = gui / (kern[k]["avg_ms"] * 1e-3) / 1e6
 
 # the emitted ISA of the kernels the bench line prices (tools/isa_mix.py; hipcc is on the box)
-ISA = {"fast_blur_kernel<3>": ("kernels_fast.hip", "fast_blur_kernelILi3E"), "orient_brief_kernel": ("kernels_desc.hip", "orient_brief_kernel"),
+# (pyramid_kernel is absent from a trace whose launches all take the fused level build: only kernels in the trace are priced)
+ISA = {"fast_blur_kernel<3, false>": ("kernels_fast.hip", "fast_blur_kernelILi3ELb0E"),
+       "fast_blur_kernel<3, true>": ("kernels_fast.hip", "fast_blur_kernelILi3ELb1E"), "orient_brief_kernel": ("kernels_desc.hip", "orient_brief_kernel"),
        "pyramid_kernel": ("kernels_pyramid.hip", "14pyramid_kernel"), "quadtree_kernel<512, false, 512>": ("kernels_quadtree.hip", "quadtree_kernelILi512ELb0ELi512E")}
 try:
     sys.path.insert(0, os.path.join(ROOT, "tools"))
