@@ -800,6 +800,73 @@ int orbfe_track_initialization(orbfe_handle *h, const uint8_t *gray, int pitch, 
                                int *matches12_out, int *n_matches);
 
 /* -------------------------------------------------------------------------------------------
+ * Two-view reconstruction: the line behind orbfe_track_initialization while the map is being initialised
+ * ---------------------------------------------------------------------------------------- */
+/* TwoViewReconstruction's constructor arguments and the two constants of Reconstruct (src/TwoViewReconstruction.cc:31-38,
+ * :113,:120,:125); versioned by struct_size like orbfe_tri_params */
+typedef struct orbfe_two_view_params {
+    int struct_size;          /* sizeof(orbfe_two_view_params) at the caller's compile time */
+    float fx, fy, cx, cy;     /* mK of the pinhole camera (src/CameraModels/Pinhole.cpp:81-88) */
+    float sigma;              /* mSigma: 1.0 at both call sites */
+    int iterations;           /* mMaxIterations: 200 at both call sites; [1, 4096] */
+    float min_parallax_deg;   /* minParallax, :113: only 1.0 is built (the decision is a cosine comparison, S12) */
+    int min_triangulated;     /* 50, :120,:125 */
+} orbfe_two_view_params;
+#define ORBFE_TWO_VIEW_PARAMS_INIT {(int)sizeof(orbfe_two_view_params), 0.f, 0.f, 0.f, 0.f, 1.0f, 200, 1.0f, 50}
+
+#define ORBFE_TWO_VIEW_MODEL_NONE        0  /* fewer than 8 matches, or SH + SF == 0 (:110) */
+#define ORBFE_TWO_VIEW_MODEL_HOMOGRAPHY  1  /* RH > 0.40: ReconstructH (:583-747) */
+#define ORBFE_TWO_VIEW_MODEL_FUNDAMENTAL 2  /* ReconstructF (:473-581) */
+
+/* every intermediate of one call (optional: info may be NULL).  struct_size as above; the pointer members are caller-owned
+ * buffers, each may be NULL.  N = n_matches = the number of i with matches12[i] >= 0; match m is the m-th such i. */
+typedef struct orbfe_two_view_info {
+    int struct_size;          /* sizeof(orbfe_two_view_info) at the caller's compile time */
+    int n_matches;            /* N (mvMatches12.size(), :62) */
+    float SH, SF, RH;         /* :98,:111 (RH = 0 when SH + SF == 0) */
+    int model;                /* ORBFE_TWO_VIEW_MODEL_* */
+    int exit_line;            /* 0 = reconstructed; else the reference line of the `return false` taken (110, 528, 580, 609,
+                                 746), or 62 for fewer than 8 matches */
+    float H21[9], F21[9];     /* best models, row-major (zeros when no hypothesis scored above 0) */
+    int best_it_H, best_it_F; /* their RANSAC iteration, -1 when none */
+    int n_hypotheses;         /* motion hypotheses checked: 0, 4 (F) or 8 (H) */
+    int best_hypothesis;      /* the one returned, -1 when not reconstructed */
+    int n_good[8];            /* CheckRT's return value per hypothesis (:498-501, :719) */
+    float cos_parallax[8];    /* cosine at rank min(50, nGood - 1) of the survivors' ascending cosines (:905-908); 1 when nGood == 0 */
+    float hyp_R[8][9];        /* the motion hypotheses, R row-major (:498-501 order; :632-702 order) */
+    float hyp_t[8][3];
+    float *scores;            /* [2 * iterations]: currentScore of every H iteration, then of every F iteration */
+    uint8_t *inliers_H;       /* [N] vbMatchesInliersH */
+    uint8_t *inliers_F;       /* [N] vbMatchesInliersF */
+    uint8_t *rt_flags;        /* [8][N]: bit 0 = counted in nGood, bit 1 = vbGood (cosParallax < 0.99998) */
+    float *rt_x3d;            /* [8][N][3]: p3dC1 of the counted matches, zeros elsewhere */
+    float *rt_cos;            /* [8][N]: cosParallax of the counted matches, zeros elsewhere */
+} orbfe_two_view_info;
+
+/* replaces TwoViewReconstruction::Reconstruct (src/TwoViewReconstruction.cc:40-127; the call: src/Tracking.cc:616 ->
+ * Pinhole::ReconstructWithTwoViews, src/CameraModels/Pinhole.cpp:81-88) for a pinhole K:
+ *   Normalize (:750-797)                                   on the host, inside the call
+ *   FindHomography / FindFundamental (:129-228): ComputeH21 / ComputeF21 (:230-306) and CheckHomography / CheckFundamental
+ *   (:308-471) for all 2 x iterations hypotheses           one launch, one wave per hypothesis; a second picks the two winners
+ *   ReconstructH / ReconstructF up to the hypotheses (:473-501, :583-702), DecomposeE (:916-940)       on the host
+ *   CheckRT (:799-914) for the 4 or 8 motion hypotheses    one launch
+ *   the selection rules (:503-580, :705-746)               on the host
+ * Numerics: SPEC DECISION S12.  kp1 / kp2 = mvKeysUn of the reference and of the current frame,
+ * matches12 (n1 ints) = vnMatches12 as orbfe_track_initialization returns it.  sets = iterations x 8 indices into the MATCH
+ * list (mvSets, :75-94): an input, because the reference draws them from a rand() stream that belongs to the process
+ * (Thirdparty/DBoW2/src/DUtils/Random.cpp:38-50; include/orbfe_adaptor.hpp draws them as the reference does).
+ * *reconstructed = the function's return value; R21 (9, row-major) / t21 (3) = T21; p3d (n1 x 3) = vP3D and triangulated (n1)
+ * = vbTriangulated, indexed by the keypoint of frame 1; all zeros when not reconstructed.
+ * Fewer than 8 matches: *reconstructed = 0, ORBFE_OK, no GPU work (the reference indexes an empty vector there).
+ * ORBFE_ERR_INVALID_ARG: a set index outside the match list or repeated inside a set, a match index outside frame 2,
+ * iterations outside [1, 4096], min_parallax_deg != 1.0, a wrong struct_size (params or info).
+ * KannalaBrandt8::ReconstructWithTwoViews undistorts with OpenCV first: its caller passes the undistorted points and K.
+ * HOST pointers.  Two submissions and two synchronisations per call (the decompositions run between them). */
+int orbfe_two_view_reconstruct(orbfe_handle *h, const orbfe_two_view_params *p, int n1, const orbfe_keypoint *kp1, int n2,
+                               const orbfe_keypoint *kp2, const int *matches12, const int *sets, int *reconstructed,
+                               float *R21, float *t21, float *p3d, uint8_t *triangulated, orbfe_two_view_info *info);
+
+/* -------------------------------------------------------------------------------------------
  * Multi-device pool: the batched many-frame mode with host frames, sharded over several GPUs
  * ---------------------------------------------------------------------------------------- */
 /* A pool owns N members.  Member k is a handle made from *params with device_id = devices[k] (params->device_id is ignored),

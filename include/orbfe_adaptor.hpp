@@ -15,9 +15,11 @@
 // classes in the reference tree and against light mock types in tests/cpp/test_adaptor.cpp.
 #pragma once
 
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -1387,6 +1389,81 @@ public:
 private:
     ORBextractor& ex_;
     orbfe_init_frame* f1_ = nullptr;
+};
+
+// TwoViewReconstruction (include/TwoViewReconstruction.h, src/TwoViewReconstruction.cc:31-127) for a pinhole K as ONE call
+// (orbfe_two_view_reconstruct): the line behind SearchForInitialization in Tracking::MonocularInitialization
+// (src/Tracking.cc:616 -> Pinhole::ReconstructWithTwoViews, src/CameraModels/Pinhole.cpp:81-88).  The RANSAC sets are drawn
+// here exactly as :64-94 draws them -- srand(0) once per process (DUtils::Random::SeedRandOnce(0)), then the RandomInt formula
+// of Thirdparty/DBoW2/src/DUtils/Random.cpp:47-50 on the process's rand() stream -- so a process that replaces the reference's
+// class by this one sees the same sets.  std::array / std::vector stand in for Sophus::SE3f / cv::Point3f.
+class TwoViewReconstruction {
+public:
+    TwoViewReconstruction(ORBextractor& extractor, float fx, float fy, float cx, float cy, float sigma = 1.0f, int iterations = 200)
+        : ex_(extractor)
+    {
+        p_ = ORBFE_TWO_VIEW_PARAMS_INIT;
+        p_.fx = fx; p_.fy = fy; p_.cx = cx; p_.cy = cy;
+        p_.sigma = sigma;
+        p_.iterations = iterations;
+    }
+    // mvSets for N matches (:64-94)
+    std::vector<int> DrawSets(int N) const
+    {
+        static const bool seeded = (srand(0), true);  // DUtils::Random::SeedRandOnce(0)
+        (void)seeded;
+        std::vector<int> sets((size_t)p_.iterations * 8, 0);
+        std::vector<int> all((size_t)N), avail;
+        for (int i = 0; i < N; i++) all[(size_t)i] = i;
+        for (int it = 0; it < p_.iterations; it++) {
+            avail = all;
+            for (int j = 0; j < 8; j++) {
+                const int d = (int)avail.size();
+                const int randi = int(((double)rand() / ((double)RAND_MAX + 1.0)) * d);
+                sets[(size_t)it * 8 + j] = avail[(size_t)randi];
+                avail[(size_t)randi] = avail.back();
+                avail.pop_back();
+            }
+        }
+        return sets;
+    }
+    // R21 row-major; vP3D[i] / vbTriangulated[i] per keypoint of frame 1.  info (optional) receives every intermediate.
+    bool Reconstruct(const std::vector<KeyPoint>& vKeys1, const std::vector<KeyPoint>& vKeys2, const std::vector<int>& vMatches12,
+                     std::array<float, 9>& R21, std::array<float, 3>& t21, std::vector<std::array<float, 3>>& vP3D,
+                     std::vector<bool>& vbTriangulated, orbfe_two_view_info* info = nullptr, const std::vector<int>* sets = nullptr)
+    {
+        const int n1 = (int)vKeys1.size(), n2 = (int)vKeys2.size();
+        if ((int)vMatches12.size() != n1) throw std::invalid_argument("TwoViewReconstruction::Reconstruct: vMatches12.size() != vKeys1.size()");
+        int N = 0;
+        for (int m : vMatches12) N += m >= 0;
+        std::vector<int> drawn;
+        if (!sets && N >= 8) drawn = DrawSets(N);  // (the reference reads past an empty vector below 8 matches: nothing is drawn)
+        const std::vector<int>& use = sets ? *sets : drawn;
+        std::vector<float> p3d((size_t)(n1 > 0 ? n1 : 1) * 3);
+        std::vector<uint8_t> tri((size_t)(n1 > 0 ? n1 : 1));
+        int reconstructed = 0;
+        orbfe_handle* h = ex_.handle();
+        orbfe_detail::check(orbfe_two_view_reconstruct(h, &p_, n1, reinterpret_cast<const orbfe_keypoint*>(vKeys1.data()), n2,
+                                                       reinterpret_cast<const orbfe_keypoint*>(vKeys2.data()), vMatches12.data(),
+                                                       use.empty() ? nullptr : use.data(), &reconstructed, R21.data(), t21.data(),
+                                                       p3d.data(), tri.data(), info),
+                            h, "orbfe_two_view_reconstruct");
+        if (!reconstructed) return false;  // the reference leaves its outputs untouched
+        vP3D.resize((size_t)n1);
+        vbTriangulated.assign((size_t)n1, false);
+        for (int i = 0; i < n1; i++) {
+            vP3D[(size_t)i] = {p3d[(size_t)3 * i], p3d[(size_t)3 * i + 1], p3d[(size_t)3 * i + 2]};
+            vbTriangulated[(size_t)i] = tri[(size_t)i] != 0;
+        }
+        return true;
+    }
+    // parallax of a motion hypothesis in degrees, for display (the decisions are made on the cosine: S12)
+    static float ParallaxDegrees(float cosParallax) { return (float)(std::acos((double)cosParallax) * 180.0 / 3.14159265358979323846); }
+    const orbfe_two_view_params& params() const { return p_; }
+
+private:
+    ORBextractor& ex_;
+    orbfe_two_view_params p_;
 };
 
 }  // namespace ORB_SLAM3

@@ -15,6 +15,7 @@
 #include "match_common.h"
 #include "device_math.h"
 #include "keyframe.h"
+#include "jacobi.h"
 
 #pragma clang fp contract(off)
 
@@ -95,47 +96,6 @@ __device__ inline void cam_unproject(const CamP& C, float precision, float u, fl
     }
     rx = pwx * scale;
     ry = pwy * scale;
-}
-
-// smallest-eigenvalue eigenvector of the symmetric 4x4 matrix M (destroyed)
-__device__ inline void sym4_min_eigenvector(double (&M)[4][4], double (&vOut)[4])
-{
-    double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-    for (int sweep = 0; sweep < 8; sweep++) {
-        for (int p = 0; p < 3; p++)
-            for (int q = p + 1; q < 4; q++) {
-                const double apq = M[p][q];
-                if (apq == 0.0) continue;
-                const double theta = (M[q][q] - M[p][p]) / (2.0 * apq);
-                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0);
-                const double sn = t * c;
-                for (int k = 0; k < 4; k++) {  // columns p, q of M
-                    const double mkp = M[k][p], mkq = M[k][q];
-                    M[k][p] = c * mkp - sn * mkq;
-                    M[k][q] = sn * mkp + c * mkq;
-                }
-                for (int k = 0; k < 4; k++) {  // rows p, q of M
-                    const double mpk = M[p][k], mqk = M[q][k];
-                    M[p][k] = c * mpk - sn * mqk;
-                    M[q][k] = sn * mpk + c * mqk;
-                }
-                for (int k = 0; k < 4; k++) {
-                    const double vkp = V[k][p], vkq = V[k][q];
-                    V[k][p] = c * vkp - sn * vkq;
-                    V[k][q] = sn * vkp + c * vkq;
-                }
-            }
-    }
-    // column of the smallest diagonal entry, lowest index on ties (selects instead of a run-time column index: the arrays
-    // stay in registers)
-    double best = M[0][0];
-    for (int k = 0; k < 4; k++) vOut[k] = V[k][0];
-    for (int i = 1; i < 4; i++) {
-        const bool less = M[i][i] < best;
-        best = less ? M[i][i] : best;
-        for (int k = 0; k < 4; k++) vOut[k] = less ? V[k][i] : vOut[k];
-    }
 }
 
 __device__ inline bool kb8_epipolar(const CamP& C1, const CamP& C2, float precision, float u1, float v1, float u2, float v2,

@@ -66,6 +66,10 @@ int match_triangulation_run(MatchScratch& m, hipStream_t s, int G, const int* of
                             const uint8_t* stereo1, int n2, const orbfe_keypoint* kp2, const uint8_t* desc2,
                             const uint8_t* hasMP2, const uint8_t* stereo2, const float* sf2, int nLevels2,
                             const orbfe_tri_params* P, int* matches12, int* nMatches, std::string& err);
+// kernels_twoview.hip (TwoViewReconstruction::Reconstruct, SPEC DECISION S12)
+int two_view_run(MatchScratch& m, hipStream_t s, const orbfe_two_view_params* P, int n1, const orbfe_keypoint* kp1, int n2,
+                 const orbfe_keypoint* kp2, const int* matches12, const int* sets, int* reconstructed, float* R21, float* t21,
+                 float* p3d, uint8_t* triangulated, orbfe_two_view_info* info, std::string& err);
 // kernels_distinct.hip (MapPoint::ComputeDistinctiveDescriptors for a batch)
 int distinctive_run(MatchScratch& m, hipStream_t s, int nSets, const int* setOff, const uint8_t* desc, int* bestIdx,
                     int* bestMedian, std::string& err);

@@ -2435,6 +2435,24 @@ int orbfe_triangulate_pairs(orbfe_handle* h, const orbfe_keyframe* kf1, const or
     return rc;
 }
 
+int orbfe_two_view_reconstruct(orbfe_handle* h, const orbfe_two_view_params* p, int n1, const orbfe_keypoint* kp1, int n2,
+                               const orbfe_keypoint* kp2, const int* matches12, const int* sets, int* reconstructed, float* R21,
+                               float* t21, float* p3d, uint8_t* triangulated, orbfe_two_view_info* info)
+{
+    if (!h || !p || n1 < 0 || n2 < 0 || !reconstructed || !R21 || !t21 || (n1 > 0 && (!kp1 || !matches12 || !p3d || !triangulated)) ||
+        (n2 > 0 && !kp2))
+        return ORBFE_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIPCHK(h, hipSetDevice(h->device));
+    std::string err;
+    MatchScope scope_(h, h->stream);
+    if (scope_.rc != ORBFE_OK) return scope_.rc;
+    const int rc = two_view_run(h->match, h->stream, p, n1, kp1, n2, kp2, matches12, sets, reconstructed, R21, t21, p3d, triangulated,
+                                info, err);
+    if (rc != ORBFE_OK) h->err = err;
+    return rc;
+}
+
 int orbfe_triangulation_select(int n1, const int* raw_match12, const uint8_t* raw_bin, const uint8_t* has_mp1_now,
                                int check_orientation, int* matches12_out, int* n_matches)
 {

@@ -126,6 +126,32 @@ def newpoint_params(Tcw1, Tcw2, twc1, twc2, levelSigma2_1, levelSigma2_2, ratioF
     return P
 
 
+class TwoViewParams(C.Structure):
+    """orbfe_two_view_params: K, mSigma, mMaxIterations and the two constants of TwoViewReconstruction::Reconstruct."""
+    _fields_ = [("struct_size", C.c_int), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("sigma", C.c_float), ("iterations", C.c_int), ("min_parallax_deg", C.c_float), ("min_triangulated", C.c_int)]
+
+    def __init__(self, fx=0.0, fy=0.0, cx=0.0, cy=0.0, sigma=1.0, iterations=200, min_parallax_deg=1.0, min_triangulated=50):
+        super().__init__(C.sizeof(TwoViewParams), fx, fy, cx, cy, sigma, iterations, min_parallax_deg, min_triangulated)
+
+
+class TwoViewInfo(C.Structure):
+    """orbfe_two_view_info: every intermediate of one orbfe_two_view_reconstruct call."""
+    _fields_ = [("struct_size", C.c_int), ("n_matches", C.c_int), ("SH", C.c_float), ("SF", C.c_float), ("RH", C.c_float),
+                ("model", C.c_int), ("exit_line", C.c_int), ("H21", C.c_float * 9), ("F21", C.c_float * 9),
+                ("best_it_H", C.c_int), ("best_it_F", C.c_int), ("n_hypotheses", C.c_int), ("best_hypothesis", C.c_int),
+                ("n_good", C.c_int * 8), ("cos_parallax", C.c_float * 8), ("hyp_R", C.c_float * 72), ("hyp_t", C.c_float * 24),
+                ("scores", C.c_void_p), ("inliers_H", C.c_void_p), ("inliers_F", C.c_void_p), ("rt_flags", C.c_void_p),
+                ("rt_x3d", C.c_void_p), ("rt_cos", C.c_void_p)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(TwoViewInfo)
+
+
+TWO_VIEW_MODEL_NONE, TWO_VIEW_MODEL_HOMOGRAPHY, TWO_VIEW_MODEL_FUNDAMENTAL = 0, 1, 2
+
+
 class TrackParams(C.Structure):
     """orbfe_track_params: frame grid statics (src/Frame.cc:101-105) + the call parameters of SearchByProjection."""
     _fields_ = [("struct_size", C.c_int), ("grid_cols", C.c_int), ("grid_rows", C.c_int), ("min_x", C.c_float),
@@ -160,7 +186,7 @@ SYMBOLS = [
     "orbfe_stream_submit_track", "orbfe_stream_collect_track", "orbfe_track_frame_map", "orbfe_track_reference_keyframe", "orbfe_debug_graph_stats", "orbfe_set_graph_capture",
     "orbfe_debug_clock_probe", "orbfe_keyframe_set_grid", "orbfe_fuse_search_keyframe", "orbfe_fuse_search_keyframes", "orbfe_fuse_select",
     "orbfe_init_frame_create", "orbfe_init_frame_destroy", "orbfe_init_frame_size", "orbfe_track_initialization",
-    "orbfe_set_stream_priority",
+    "orbfe_set_stream_priority", "orbfe_two_view_reconstruct",
     "orbfe_shard_range", "orbfe_pool_create", "orbfe_pool_destroy", "orbfe_pool_size", "orbfe_pool_member",
     "orbfe_pool_member_frames", "orbfe_pool_last_error", "orbfe_pool_extract", "orbfe_pool_enable_track",
     "orbfe_pool_map_update", "orbfe_pool_track",
@@ -279,6 +305,9 @@ def lib():
     if hasattr(L, "orbfe_create_new_points_batch"):  # an earlier build loaded for an A/B (bench.py --lib tools/ab/...) lacks the two
         L.orbfe_create_new_points_batch.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp]
         L.orbfe_triangulate_pairs.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, vp]
+    if hasattr(L, "orbfe_two_view_reconstruct"):  # (as above: absent from an earlier build loaded for an A/B)
+        L.orbfe_two_view_reconstruct.argtypes = [vp, C.POINTER(TwoViewParams), ci, vp, ci, vp, vp, vp, C.POINTER(ci), vp, vp, vp, vp,
+                                                 C.POINTER(TwoViewInfo)]
     L.orbfe_distinctive_descriptors.argtypes = [vp, ci, vp, vp, vp, vp]
     L.orbfe_vocab_create.argtypes = [vp, ci, vp, vp, vp, vp, vp, ci, C.POINTER(vp)]
     L.orbfe_vocab_destroy.argtypes = [vp]
@@ -1067,6 +1096,46 @@ def triangulate_pairs(extractor, kf1, kf2, np_params, idx1, idx2):
     extractor._chk(extractor.L.orbfe_triangulate_pairs(extractor.h, kf1.h, kf2.h, C.byref(np_params), n, _p(i1), _p(i2), _p(x3d),
                                                        _p(verdict)), "orbfe_triangulate_pairs")
     return x3d[:n], verdict[:n]
+
+
+def two_view_reconstruct(extractor, params, kp1, kp2, matches12, sets, want_info=True):
+    """orbfe_two_view_reconstruct: TwoViewReconstruction::Reconstruct (src/TwoViewReconstruction.cc:40-127) for a pinhole K.
+    kp1 / kp2: KP_DTYPE arrays (mvKeysUn), matches12 [n1] (index in frame 2 or -1), sets [iterations, 8] indices into the match
+    list -> dict(reconstructed, R21 [3, 3], t21 [3], p3d [n1, 3], triangulated [n1]) plus, with want_info, every field of
+    orbfe_two_view_info under its own name (the optional buffers included)."""
+    kp1 = np.ascontiguousarray(kp1, KP_DTYPE)
+    kp2 = np.ascontiguousarray(kp2, KP_DTYPE)
+    m12 = np.ascontiguousarray(matches12, np.int32)
+    assert len(m12) == len(kp1)
+    st = None if sets is None else np.ascontiguousarray(sets, np.int32)
+    n1, n2 = len(kp1), len(kp2)
+    N = int((m12 >= 0).sum())
+    it = max(int(params.iterations), 1)
+    R21, t21 = np.zeros((3, 3), np.float32), np.zeros(3, np.float32)
+    p3d, tri = np.zeros((max(n1, 1), 3), np.float32), np.zeros(max(n1, 1), np.uint8)
+    rec = C.c_int(0)
+    info = None
+    if want_info:
+        info = TwoViewInfo()
+        buf = dict(scores=np.zeros(2 * it, np.float32), inliers_H=np.zeros(max(N, 1), np.uint8), inliers_F=np.zeros(max(N, 1), np.uint8),
+                   rt_flags=np.zeros((8, max(N, 1)), np.uint8), rt_x3d=np.zeros((8, max(N, 1), 3), np.float32),
+                   rt_cos=np.zeros((8, max(N, 1)), np.float32))
+        for k, v in buf.items():
+            setattr(info, k, v.ctypes.data)
+    extractor._chk(extractor.L.orbfe_two_view_reconstruct(extractor.h, C.byref(params), n1, _p(kp1), n2, _p(kp2), _p(m12), _p(st),
+                                                          C.byref(rec), _p(R21), _p(t21), _p(p3d), _p(tri),
+                                                          C.byref(info) if want_info else None), "orbfe_two_view_reconstruct")
+    out = dict(reconstructed=bool(rec.value), R21=R21, t21=t21, p3d=p3d[:n1], triangulated=tri[:n1])
+    if want_info:
+        out.update(n_matches=info.n_matches, SH=np.float32(info.SH), SF=np.float32(info.SF), RH=np.float32(info.RH), model=info.model,
+                   exit_line=info.exit_line, H21=np.array(info.H21, np.float32).reshape(3, 3), F21=np.array(info.F21, np.float32).reshape(3, 3),
+                   best_it_H=info.best_it_H, best_it_F=info.best_it_F, n_hypotheses=info.n_hypotheses,
+                   best_hypothesis=info.best_hypothesis, n_good=np.array(info.n_good, np.int32),
+                   cos_parallax=np.array(info.cos_parallax, np.float32), hyp_R=np.array(info.hyp_R, np.float32).reshape(8, 3, 3),
+                   hyp_t=np.array(info.hyp_t, np.float32).reshape(8, 3), scores=buf["scores"], inliers_H=buf["inliers_H"][:N],
+                   inliers_F=buf["inliers_F"][:N], rt_flags=buf["rt_flags"].reshape(-1)[:8 * N].reshape(8, N),
+                   rt_x3d=buf["rt_x3d"].reshape(-1)[:24 * N].reshape(8, N, 3), rt_cos=buf["rt_cos"].reshape(-1)[:8 * N].reshape(8, N))
+    return out
 
 
 def triangulation_select(raw_match12, raw_bin, hasMP1_now, checkOrientation=True):
