@@ -39,6 +39,40 @@ size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 const char* kStageNames[ORBFE_NUM_STAGES] = {"pyramid_resize", "fast_nms_blur",
                                              "quadtree", "orient_brief", "total"};
 
+// the staging of one per-frame chain: a device input and a device result block, each with a pinned mirror
+// (chain_blocks_alloc / chain_blocks_free)
+struct ChainBlocks {
+    uint8_t *dIn = nullptr, *hIn = nullptr, *dOut = nullptr, *hOut = nullptr;
+};
+
+// The captured graphs of one chain.  Keys are compared as bytes: a key is zeroed with memset before it is filled, so that
+// padding compares equal.  Bounded: a caller cycling through more keys than `bound` drops everything and starts afresh.
+template <class Key>
+struct GraphCache {
+    struct Entry {
+        Key key;
+        hipGraphExec_t exec;
+    };
+    std::vector<Entry> entries;
+    hipGraphExec_t find(const Key& key) const
+    {
+        for (const Entry& e : entries)
+            if (memcmp(&e.key, &key, sizeof key) == 0) return e.exec;
+        return nullptr;
+    }
+    void insert(const Key& key, hipGraphExec_t exec, size_t bound)
+    {
+        if (entries.size() >= bound) drop();
+        entries.push_back({key, exec});
+    }
+    void drop()
+    {
+        for (Entry& e : entries)
+            if (e.exec) (void)hipGraphExecDestroy(e.exec);
+        entries.clear();
+    }
+};
+
 }  // namespace
 
 struct orbfe_map;
@@ -116,17 +150,12 @@ struct orbfe_handle {
         float minX, minY, invW, invH, th, nnRatio, thFar;
         const void* map;  // null: explicit points in the block; else the resident map the ids refer to (its addresses are in the graph)
     };
-    struct TrackGraph {
-        TrackKey key;
-        hipGraphExec_t exec;
-    };
     MatchScratch trackMatch;
-    uint8_t* dTrkIn = nullptr;   // [image | frustum | points (Mb) | descriptors (Mb)]
-    uint8_t* hTrkIn = nullptr;   // pinned mirror
-    uint8_t* dTrkOut = nullptr;  // [n, status, n_matches | per-level | keypoints | descriptors | match | map-point records (Mb) | xr (Mb)]
-    uint8_t* hTrkOut = nullptr;  // pinned mirror
+    // in:  [image | frustum | points (Mb) | descriptors (Mb)]
+    // out: [n, status, n_matches | per-level | keypoints | descriptors | match | map-point records (Mb) | xr (Mb)]
+    ChainBlocks trk;
     int trkCapM = 0;
-    std::vector<TrackGraph> trackGraphs;
+    GraphCache<TrackKey> trackGraphs;
     // orbfe_track_reference_keyframe: extract -> vocabulary descent -> SearchByBoW against a resident key frame.  The key
     // frame is named by a record inside the input block, so a graph depends only on what is in RefKey.
     struct RefKey {
@@ -134,16 +163,11 @@ struct orbfe_handle {
         float nnRatio;
         unsigned long long vocabSerial;
     };
-    struct RefGraph {
-        RefKey key;
-        hipGraphExec_t exec;
-    };
-    uint8_t* dRefIn = nullptr;   // [image | key-frame record | key-frame flags (refCapFlags)]
-    uint8_t* hRefIn = nullptr;
-    uint8_t* dRefOut = nullptr;  // [n, status, n_matches | per-level | keypoints | descriptors | match | (word, node) | leaf | bins]
-    uint8_t* hRefOut = nullptr;
+    // in:  [image | key-frame record | key-frame flags (refCapFlags)]
+    // out: [n, status, n_matches | per-level | keypoints | descriptors | match | (word, node) | leaf | bins]
+    ChainBlocks ref;
     int refCapFlags = 0;
-    std::vector<RefGraph> refGraphs;
+    GraphCache<RefKey> refGraphs;
     // orbfe_track_initialization: extract -> SearchForInitialization(resident initial frame, frame).  A graph holds the
     // addresses of the initial frame it was captured for (named by its serial) and of these blocks.
     struct IniKey {
@@ -151,17 +175,12 @@ struct orbfe_handle {
         float minX, minY, invW, invH, nnRatio;
         unsigned long long frameSerial;
     };
-    struct IniGraph {
-        IniKey key;
-        hipGraphExec_t exec;
-    };
-    uint8_t* dIniIn = nullptr;    // [image]
-    uint8_t* hIniIn = nullptr;
-    uint8_t* dIniOut = nullptr;   // [n, status, n_matches | per-level | keypoints | descriptors | matches12 (iniCapN1)] + matcher scratch
-    uint8_t* hIniOut = nullptr;
+    // in:  [image]
+    // out: [n, status, n_matches | per-level | keypoints | descriptors | matches12 (iniCapN1)] + matcher scratch
+    ChainBlocks ini;
     int iniCapN1 = -1;
     size_t iniScratchBytes = 0;
-    std::vector<IniGraph> iniGraphs;
+    GraphCache<IniKey> iniGraphs;
     std::mutex mu;
     std::string err;
     // objects that keep a pointer to this handle: orbfe_destroy releases their device memory and orphans them (h = null), so
@@ -239,6 +258,38 @@ void fill_resize_table(std::vector<uint32_t>& t, size_t off, int srcN, int dstN)
     for (size_t x = (size_t)dstN; x < align_up((size_t)dstN, 4); x++) t[off + x] = t[off + dstN - 1];
 }
 
+// The caller holds h->mu (or is the handle's destruction), nothing that uses the blocks is in flight, and the graphs that
+// hold their addresses have been dropped.
+void chain_blocks_free(orbfe_handle* h, ChainBlocks& b)
+{
+    // the getters read level 0 of the last call through lastGray: forget a frame that lives in the block that goes away
+    // (they refuse frame >= lastBatch), whatever becomes of the call that is regrowing it
+    if (b.dIn && h->lastGray == b.dIn) {
+        h->lastGray = nullptr;
+        h->lastStride = 0;
+        h->lastPitch = h->lastBatch = 0;
+    }
+    if (b.dIn) (void)hipFree(b.dIn);
+    if (b.dOut) (void)hipFree(b.dOut);
+    if (b.hIn) (void)hipHostFree(b.hIn);
+    if (b.hOut) (void)hipHostFree(b.hOut);
+    b = ChainBlocks{};
+}
+
+// replaces the blocks by new ones of these sizes (only part of the result block is ever downloaded: hostOutBytes <= devOutBytes)
+int chain_blocks_alloc(orbfe_handle* h, ChainBlocks& b, size_t inBytes, size_t devOutBytes, size_t hostOutBytes, const char* who)
+{
+    chain_blocks_free(h, b);
+    if (hipMalloc(&b.dIn, inBytes) != hipSuccess || hipMalloc(&b.dOut, devOutBytes) != hipSuccess ||
+        hipHostMalloc(&b.hIn, inBytes) != hipSuccess || hipHostMalloc(&b.hOut, hostOutBytes) != hipSuccess) {
+        (void)hipGetLastError();
+        chain_blocks_free(h, b);
+        h->err = std::string(who) + ": allocation of the staging blocks failed";
+        return ORBFE_ERR_OUT_OF_MEMORY;
+    }
+    return ORBFE_OK;
+}
+
 void orphan_children(orbfe_handle* h);  // defined behind orbfe_map / orbfe_stream
 
 void destroy_impl(orbfe_handle* h)
@@ -254,25 +305,11 @@ void destroy_impl(orbfe_handle* h)
     if (h->evMatch) (void)hipEventDestroy(h->evMatch);
     h->match.busy = nullptr;
     match_scratch_free(h->match);
-    for (auto& g : h->trackGraphs)
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    h->trackGraphs.drop();
     match_scratch_free(h->trackMatch);
-    for (auto& g : h->refGraphs)
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    for (auto& g : h->iniGraphs)
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    if (h->dIniIn) (void)hipFree(h->dIniIn);
-    if (h->dIniOut) (void)hipFree(h->dIniOut);
-    if (h->hIniIn) (void)hipHostFree(h->hIniIn);
-    if (h->hIniOut) (void)hipHostFree(h->hIniOut);
-    if (h->dRefIn) (void)hipFree(h->dRefIn);
-    if (h->dRefOut) (void)hipFree(h->dRefOut);
-    if (h->hRefIn) (void)hipHostFree(h->hRefIn);
-    if (h->hRefOut) (void)hipHostFree(h->hRefOut);
-    if (h->dTrkIn) (void)hipFree(h->dTrkIn);
-    if (h->dTrkOut) (void)hipFree(h->dTrkOut);
-    if (h->hTrkIn) (void)hipHostFree(h->hTrkIn);
-    if (h->hTrkOut) (void)hipHostFree(h->hTrkOut);
+    h->refGraphs.drop();
+    h->iniGraphs.drop();
+    for (ChainBlocks* b : {&h->ini, &h->ref, &h->trk}) chain_blocks_free(h, *b);
     for (auto& g : h->graphs)
         if (g.second) (void)hipGraphExecDestroy(g.second);
     void* dptrs[] = {h->dP, h->ws, h->dCand, h->dNodeOf, h->dCounters, h->dLvlKp, h->dTileRows, h->dQtScratch, h->dTabs,
@@ -725,6 +762,10 @@ static int extract_host_enqueue(orbfe_handle* h, int batch, int inPitch, hipStre
     return ORBFE_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
 // Graphs are captured on a THROW-AWAY stream, never on the handle's (or a caller's) own.  On this runtime (ROCm 7.2) a
 // NULL-stream operation of any other thread of the process -- a plain hipMemcpy of the application -- that meets a capture in
 // flight fails with hipErrorStreamCaptureImplicit AND leaves the capturing stream unusable for good, whatever the capture mode
@@ -774,79 +815,176 @@ struct CaptureStream {
     }
 };
 
-static void graph_capture_failed(orbfe_handle* h)
+void graph_capture_failed(orbfe_handle* h)
 {
     (void)hipGetLastError();
     h->captureFailures++;
     if (++h->captureFailStreak >= 8) h->useGraph = false;  // eight in a row: this handle's captures keep failing
 }
 
-static void graph_capture_succeeded(orbfe_handle* h)
+void graph_capture_succeeded(orbfe_handle* h)
 {
     h->graphCaptures++;
     h->captureFailStreak = 0;  // an occasional foreign NULL-stream call over a long run never adds up to the limit
 }
 
+// One capture attempt: enqueue(stream) -> status, captured on a throw-away stream and instantiated.  Null when any step
+// failed; the caller then runs the same enqueue on plain launches, which returns the real error if the enqueue itself is
+// what failed.
+template <class Enqueue>
+hipGraphExec_t capture_graph(orbfe_handle* h, Enqueue& enqueue)
+{
+    int rc;
+    hipGraph_t graph = nullptr;
+    {
+        CaptureStream cs;
+        rc = cs.begin() ? enqueue(cs.s) : ORBFE_ERR_HIP;
+        graph = cs.end();
+    }
+    hipGraphExec_t exec = nullptr;
+    if (rc == ORBFE_OK && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) exec = nullptr;
+    if (graph) (void)hipGraphDestroy(graph);
+    if (exec)
+        graph_capture_succeeded(h);
+    else
+        graph_capture_failed(h);
+    return exec;
+}
+
+// Replay on s.  While a chain is captured the hand-over events stay outside the graph (extract_chain), so the wait and
+// the record go around the launch here, and so does what extract_chain records for the pyramid / candidate getters.
+int launch_graph(orbfe_handle* h, hipGraphExec_t exec, hipStream_t s, const uint8_t* dGray, size_t stride, int pitch, int batch)
+{
+    int rc = scratch_acquire(h, h->extractUsed, h->extractStream, h->evExtract, s);
+    if (rc != ORBFE_OK) return rc;
+    HIPCHK(h, hipGraphLaunch(exec, s));
+    rc = extract_scratch_release(h, s);
+    if (rc != ORBFE_OK) return rc;
+    h->lastGray = dGray;
+    h->lastStride = stride;
+    h->lastPitch = pitch;
+    h->lastBatch = batch;
+    return ORBFE_OK;
+}
+
 // extract_host_enqueue, replayed from a hipGraph when possible: every pointer behind the upload is owned by the
 // handle, so the enqueue sequence (the kernels of extract_chain, result copy) is captured once per (batch, input pitch) and
 // replayed with a single hipGraphLaunch
-static int extract_enqueue_replay(orbfe_handle* h, int batch, int inPitch, hipStream_t s)
+int extract_enqueue_replay(orbfe_handle* h, int batch, int inPitch, hipStream_t s)
 {
-    const size_t inFrame = (size_t)h->dInPitch * h->prm.image_height;
-    int rc = ORBFE_OK;
-    bool viaGraph = h->useGraph && !h->timing && batch < 4096;
-    if (viaGraph) {
-        // every pointer behind the upload is owned by the handle, so the enqueue sequence (kernels, result
-        // copy) is captured once per batch size and replayed with a single hipGraphLaunch
-        const int gkey = batch | (inPitch << 12);  // batch <= 4095 frames per call in graph mode, else plain launches
-        hipGraphExec_t& exec = h->graphs[gkey];
-        if (!exec) {
-            hipGraph_t graph = nullptr;
-            {
-                CaptureStream cs;
-                rc = cs.begin() ? extract_host_enqueue(h, batch, inPitch, cs.s) : ORBFE_ERR_HIP;
-                graph = cs.end();
-            }
-            if (rc != ORBFE_OK || !graph) {
-                rc = ORBFE_OK;
-                if (graph) (void)hipGraphDestroy(graph);
-                h->graphs.erase(gkey);
-                graph_capture_failed(h);
-                viaGraph = false;  // plain launches below
-            } else {
-                const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-                (void)hipGraphDestroy(graph);
-                if (ei != hipSuccess) {
-                    h->graphs.erase(gkey);
-                    graph_capture_failed(h);
-                    viaGraph = false;
-                } else {
-                    graph_capture_succeeded(h);
-                }
-            }
-        }
-        if (viaGraph) {
-            {
-                const int rca = scratch_acquire(h, h->extractUsed, h->extractStream, h->evExtract, s);
-                if (rca != ORBFE_OK) return rca;
-            }
-            HIPCHK(h, hipGraphLaunch(h->graphs[gkey], s));
-            {
-                const int rcr = extract_scratch_release(h, s);
-                if (rcr != ORBFE_OK) return rcr;
-            }
-            h->lastGray = h->dIn;  // what extract_chain records on a plain launch (pyramid / candidate getters)
-            h->lastStride = inFrame;
-            h->lastPitch = inPitch;
-            h->lastBatch = batch;
+    auto enqueue = [&](hipStream_t q) { return extract_host_enqueue(h, batch, inPitch, q); };
+    hipGraphExec_t exec = nullptr;
+    if (h->useGraph && !h->timing && batch < 4096) {  // batch <= 4095 frames per call in graph mode, else plain launches
+        const int gkey = batch | (inPitch << 12);
+        const auto it = h->graphs.find(gkey);
+        if (it != h->graphs.end())
+            exec = it->second;
+        else if ((exec = capture_graph(h, enqueue)))
+            h->graphs[gkey] = exec;
+    }
+    if (!exec) return enqueue(s);
+    return launch_graph(h, exec, s, h->dIn, (size_t)h->dInPitch * h->prm.image_height, inPitch, batch);
+}
+
+// Single-frame upload into blk.dIn, with [smallBegin, smallEnd) of blk.hIn -- what the chain staged behind the frame, or
+// nothing -- going up too.  Pinned sources (the reference hands over cv::cuda::HostMem, include/ORBextractor.h:62) with a
+// dword-aligned pitch that fits the staging rows are copied by the DMA engine straight from the caller's buffer, followed
+// by the small range; everything else goes through the pinned mirror, where frame and small range are ONE copy.
+// *inPitch: the pitch of the frame as it lies in blk.dIn.
+int upload_frame(orbfe_handle* h, const ChainBlocks& blk, const uint8_t* gray, int pitch, size_t smallBegin, size_t smallEnd,
+                 hipStream_t s, int* inPitch)
+{
+    const int W = h->prm.image_width, H = h->prm.image_height;
+    const bool keepPitch = pitch <= h->dInPitch && (pitch & 3) == 0;  // level 0 is read with an arbitrary dword-aligned pitch
+    bool direct = keepPitch && (reinterpret_cast<uintptr_t>(gray) & 3u) == 0;
+    if (direct) {
+        hipPointerAttribute_t attr;
+        if (hipPointerGetAttributes(&attr, gray) != hipSuccess || attr.type != hipMemoryTypeHost) {
+            (void)hipGetLastError();
+            direct = false;
         }
     }
-    if (!viaGraph) {
-        rc = extract_host_enqueue(h, batch, inPitch, s);
-        if (rc != ORBFE_OK) return rc;
+    *inPitch = keepPitch ? pitch : h->dInPitch;
+    const size_t frameBytes = (size_t)*inPitch * (H - 1) + (size_t)W;
+    if (direct) {
+        HIPCHK(h, hipMemcpyAsync(blk.dIn, gray, frameBytes, hipMemcpyHostToDevice, s));
+        if (smallEnd > smallBegin)
+            HIPCHK(h, hipMemcpyAsync(blk.dIn + smallBegin, blk.hIn + smallBegin, smallEnd - smallBegin, hipMemcpyHostToDevice, s));
+        return ORBFE_OK;
+    }
+    if (keepPitch)  // the frame is one contiguous copy
+        memcpy(blk.hIn, gray, frameBytes);
+    else
+        for (int y = 0; y < H; y++) memcpy(blk.hIn + (size_t)y * *inPitch, gray + (size_t)y * pitch, (size_t)W);
+    HIPCHK(h, hipMemcpyAsync(blk.dIn, blk.hIn, smallEnd > smallBegin ? smallEnd : frameBytes, hipMemcpyHostToDevice, s));
+    return ORBFE_OK;
+}
+
+// What every chain does behind its upload: replay the graph of `key` -- capturing it first if need be -- or, with graphs
+// off or after a failed capture, run the same enqueue(stream) -> status on plain launches; wait; check the guard word of
+// the downloaded head [n, status, n_matches].
+template <class Key, class Enqueue>
+int chain_submit(orbfe_handle* h, GraphCache<Key>& cache, size_t bound, const Key& key, const ChainBlocks& blk, size_t inFrame,
+                 int inPitch, hipStream_t s, Enqueue enqueue, const char* who)
+{
+    hipGraphExec_t exec = nullptr;
+    if (h->useGraph && !h->timing) {
+        exec = cache.find(key);
+        if (!exec && (exec = capture_graph(h, enqueue))) cache.insert(key, exec, bound);
+    }
+    const int rc = exec ? launch_graph(h, exec, s, blk.dIn, inFrame, inPitch, 1) : enqueue(s);
+    if (rc != ORBFE_OK) return rc;
+    HIPCHK(h, hipStreamSynchronize(s));
+    const int status = reinterpret_cast<const int*>(blk.hOut)[1];
+    if (status) {
+        char buf[112];
+        snprintf(buf, sizeof buf, "device guard flags 0x%x in %s", (unsigned)status, who);
+        h->err = buf;
+        return ORBFE_ERR_INTERNAL;
     }
     return ORBFE_OK;
 }
+
+// What every chain's blocks begin with: the frame in the input block; [n, status, n_matches] at 0 of the result block,
+// then the per-level counts, the keypoints and the descriptors.  A chain's layout continues behind them with take256().
+struct ChainPrefix {
+    size_t inFrame, oPer, oKp, oDesc;
+};
+
+size_t take256(size_t& off, size_t bytes)
+{
+    const size_t o = off;
+    off = align_up(off + bytes, 256);
+    return o;
+}
+
+// -> the offset at which the chain's own part of the result block starts
+size_t chain_prefix_layout(const orbfe_handle* h, ChainPrefix& L)
+{
+    const size_t cap = (size_t)h->P.kpCapFrame;
+    L.inFrame = align_up((size_t)h->dInPitch * h->prm.image_height, 256);
+    size_t off = 256;
+    L.oPer = take256(off, (size_t)h->nLevels * sizeof(int));
+    L.oKp = take256(off, cap * sizeof(orbfe_keypoint));
+    L.oDesc = take256(off, cap * ORBFE_DESC_BYTES);
+    return off;
+}
+
+// hand-over of that prefix out of the pinned result block; -> n
+int chain_prefix_copy_out(const orbfe_handle* h, const uint8_t* hOut, const ChainPrefix& L, orbfe_keypoint* kp_out, uint8_t* desc_out,
+                          int* n_out, int* per_level)
+{
+    const int n = reinterpret_cast<const int*>(hOut)[0];
+    *n_out = n;
+    memcpy(kp_out, hOut + L.oKp, (size_t)n * sizeof(orbfe_keypoint));
+    memcpy(desc_out, hOut + L.oDesc, (size_t)n * ORBFE_DESC_BYTES);
+    if (per_level) memcpy(per_level, hOut + L.oPer, (size_t)h->nLevels * sizeof(int));
+    return n;
+}
+
+}  // namespace
+
+extern "C" {
 
 int orbfe_extract_batch(orbfe_handle* h, const uint8_t* const* grays, int pitch, int batch, orbfe_keypoint* kp_out,
                         uint8_t* desc_out, int* n_out, int* per_level)
@@ -931,60 +1069,37 @@ int track_bucket(int M)
     return std::max(g, (M + g - 1) / g * g);
 }
 
-struct TrackLayout {
-    size_t inFrame, oFr, oPts, oMpDesc, inBytes;                              // input block
-    size_t oPer, oKp, oDesc, oMatch, oMps, oXr, outBytes;                     // result block ([n, status, n_matches] at 0)
+struct TrackLayout : ChainPrefix {
+    size_t oFr, oPts, oMpDesc, inBytes;  // input block
+    size_t oMatch, oMps, oXr, outBytes;  // result block
 };
 
 TrackLayout track_layout(const orbfe_handle* h, int Mb)
 {
     TrackLayout L{};
-    const size_t cap = (size_t)h->P.kpCapFrame;
-    L.inFrame = align_up((size_t)h->dInPitch * h->prm.image_height, 256);
+    size_t off = chain_prefix_layout(h, L);
     L.oFr = L.inFrame;
     L.oPts = L.oFr + align_up(sizeof(orbfe_frustum), 256);
     L.oMpDesc = L.oPts + (size_t)Mb * sizeof(orbfe_world_point);
     L.inBytes = L.oMpDesc + (size_t)Mb * ORBFE_DESC_BYTES;
-    size_t off = 256;
-    auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
-    L.oPer = take((size_t)h->nLevels * sizeof(int));
-    L.oKp = take(cap * sizeof(orbfe_keypoint));
-    L.oDesc = take(cap * ORBFE_DESC_BYTES);
-    L.oMatch = take(cap * sizeof(int));
-    L.oMps = take((size_t)Mb * sizeof(orbfe_map_point));
-    L.oXr = take((size_t)Mb * sizeof(float));
+    L.oMatch = take256(off, (size_t)h->P.kpCapFrame * sizeof(int));
+    L.oMps = take256(off, (size_t)Mb * sizeof(orbfe_map_point));
+    L.oXr = take256(off, (size_t)Mb * sizeof(float));
     L.outBytes = off;
     return L;
-}
-
-void track_drop_graphs(orbfe_handle* h)
-{
-    for (auto& g : h->trackGraphs)
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    h->trackGraphs.clear();
 }
 
 // (re)allocate the blocks for Mb map points; the caller holds h->mu and nothing of this path is in flight
 int track_reserve(orbfe_handle* h, int Mb)
 {
     if (Mb <= h->trkCapM) return ORBFE_OK;
-    track_drop_graphs(h);
-    if (h->dTrkIn) (void)hipFree(h->dTrkIn);
-    if (h->dTrkOut) (void)hipFree(h->dTrkOut);
-    if (h->hTrkIn) (void)hipHostFree(h->hTrkIn);
-    if (h->hTrkOut) (void)hipHostFree(h->hTrkOut);
-    h->dTrkIn = h->dTrkOut = h->hTrkIn = h->hTrkOut = nullptr;
+    h->trackGraphs.drop();
     h->trkCapM = 0;
     const int capM = Mb + Mb / 2;  // head-room: a growing local map does not reallocate (and re-capture) at every bucket
     const TrackLayout L = track_layout(h, capM);
-    if (hipMalloc(&h->dTrkIn, L.inBytes) != hipSuccess || hipMalloc(&h->dTrkOut, L.outBytes) != hipSuccess ||
-        hipHostMalloc(&h->hTrkIn, L.inBytes) != hipSuccess || hipHostMalloc(&h->hTrkOut, L.outBytes) != hipSuccess) {
-        (void)hipGetLastError();
-        h->err = "orbfe_track_frame: allocation of the staging blocks failed";
-        return ORBFE_ERR_OUT_OF_MEMORY;
-    }
-    h->trkCapM = capM;
-    return ORBFE_OK;
+    const int rc = chain_blocks_alloc(h, h->trk, L.inBytes, L.outBytes, L.outBytes, "orbfe_track_frame");
+    if (rc == ORBFE_OK) h->trkCapM = capM;
+    return rc;
 }
 
 // the device side of one call, enqueued on s (directly, or under stream capture): extraction chain on the uploaded
@@ -992,25 +1107,25 @@ int track_reserve(orbfe_handle* h, int Mb)
 // download of the result block
 int track_enqueue(orbfe_handle* h, const TrackLayout& L, int Mb, int inPitch, proj::ProjArgs& A, const orbfe_map* map, hipStream_t s)
 {
-    int* dHead = reinterpret_cast<int*>(h->dTrkOut);  // [n, status, n_matches]
-    int rc = extract_chain(h, h->dTrkIn, L.inFrame, inPitch, 1, reinterpret_cast<orbfe_keypoint*>(h->dTrkOut + L.oKp),
-                           h->dTrkOut + L.oDesc, dHead, reinterpret_cast<int*>(h->dTrkOut + L.oPer), dHead + 1, s);
+    int* dHead = reinterpret_cast<int*>(h->trk.dOut);  // [n, status, n_matches]
+    int rc = extract_chain(h, h->trk.dIn, L.inFrame, inPitch, 1, reinterpret_cast<orbfe_keypoint*>(h->trk.dOut + L.oKp),
+                           h->trk.dOut + L.oDesc, dHead, reinterpret_cast<int*>(h->trk.dOut + L.oPer), dHead + 1, s);
     if (rc != ORBFE_OK) return rc;
     std::string err;
-    const orbfe_frustum* dF = reinterpret_cast<const orbfe_frustum*>(h->dTrkIn + L.oFr);
-    orbfe_map_point* dMps = reinterpret_cast<orbfe_map_point*>(h->dTrkOut + L.oMps);
-    float* dXr = reinterpret_cast<float*>(h->dTrkOut + L.oXr);
+    const orbfe_frustum* dF = reinterpret_cast<const orbfe_frustum*>(h->trk.dIn + L.oFr);
+    orbfe_map_point* dMps = reinterpret_cast<orbfe_map_point*>(h->trk.dOut + L.oMps);
+    float* dXr = reinterpret_cast<float*>(h->trk.dOut + L.oXr);
     if (map)  // the block carries ids (at the points' offset): gather record + descriptor from the resident map, then project
-        rc = frustum_gather_launch(s, 1, dF, reinterpret_cast<const int*>(h->dTrkIn + L.oPts), Mb, map->cap, map->dPts, map->dDesc, dMps,
-                                   h->dTrkIn + L.oMpDesc, dXr, err);
+        rc = frustum_gather_launch(s, 1, dF, reinterpret_cast<const int*>(h->trk.dIn + L.oPts), Mb, map->cap, map->dPts, map->dDesc, dMps,
+                                   h->trk.dIn + L.oMpDesc, dXr, err);
     else
-        rc = frustum_launch_dev(s, dF, Mb, reinterpret_cast<const orbfe_world_point*>(h->dTrkIn + L.oPts), dMps, dXr, err);
+        rc = frustum_launch_dev(s, dF, Mb, reinterpret_cast<const orbfe_world_point*>(h->trk.dIn + L.oPts), dMps, dXr, err);
     if (rc == ORBFE_OK) rc = proj::proj_launch(s, A, err);
     if (rc != ORBFE_OK) {
         h->err = err;
         return rc;
     }
-    HIPCHK(h, hipMemcpyAsync(h->hTrkOut, h->dTrkOut, L.outBytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(h->trk.hOut, h->trk.dOut, L.outBytes, hipMemcpyDeviceToHost, s));
     return ORBFE_OK;
 }
 
@@ -1037,7 +1152,7 @@ static int track_frame_impl(orbfe_handle* h, const uint8_t* gray, int pitch, con
         return ORBFE_ERR_UNSUPPORTED;
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    const int W = h->prm.image_width, H = h->prm.image_height, nL = h->nLevels;
+    const int nL = h->nLevels;
     const int cap = h->P.kpCapFrame;
     const int Mb = track_bucket(M);
     int rc = track_reserve(h, Mb);
@@ -1049,15 +1164,15 @@ static int track_frame_impl(orbfe_handle* h, const uint8_t* gray, int pitch, con
     A.B = 1; A.M = Mb; A.kpStride = cap;
     A.g = proj::GridDesc{tp->grid_cols, tp->grid_rows, tp->min_x, tp->min_y, tp->grid_inv_w, tp->grid_inv_h};
     A.th = tp->th; A.thFar = tp->th_far_points; A.nnRatio = tp->nn_ratio; A.farPoints = tp->far_points; A.bFactor = tp->th != 1.0;
-    A.kp = reinterpret_cast<const orbfe_keypoint*>(h->dTrkOut + L.oKp);
-    A.desc = h->dTrkOut + L.oDesc;
-    A.nKp = reinterpret_cast<const int*>(h->dTrkOut);
-    A.mps = reinterpret_cast<const orbfe_map_point*>(h->dTrkOut + L.oMps);
-    A.mpDesc = h->dTrkIn + L.oMpDesc;
+    A.kp = reinterpret_cast<const orbfe_keypoint*>(h->trk.dOut + L.oKp);
+    A.desc = h->trk.dOut + L.oDesc;
+    A.nKp = reinterpret_cast<const int*>(h->trk.dOut);
+    A.mps = reinterpret_cast<const orbfe_map_point*>(h->trk.dOut + L.oMps);
+    A.mpDesc = h->trk.dIn + L.oMpDesc;
     A.initObs = nullptr;
     A.scaleFactors = h->dSf; A.nLevels = nL;
-    A.matchOut = reinterpret_cast<int*>(h->dTrkOut + L.oMatch);
-    A.nMatches = reinterpret_cast<int*>(h->dTrkOut) + 2;
+    A.matchOut = reinterpret_cast<int*>(h->trk.dOut + L.oMatch);
+    A.nMatches = reinterpret_cast<int*>(h->trk.dOut) + 2;
     {
         std::string err;
         void* before = h->trackMatch.d;
@@ -1066,117 +1181,51 @@ static int track_frame_impl(orbfe_handle* h, const uint8_t* gray, int pitch, con
             h->err = err;
             return rc;
         }
-        if (before && h->trackMatch.d != before) track_drop_graphs(h);  // the arena moved: graphs hold its old address
+        if (before && h->trackMatch.d != before) h->trackGraphs.drop();  // the arena moved: graphs hold its old address
     }
 
     // ---- stage the small block: [frustum | points | descriptors] with the padding records marked bad, or -- resident map --
     //      [frustum | ids] with the padding ids outside the map (the gather kernel turns those into bad records) ----
-    memcpy(h->hTrkIn + L.oFr, frustum, sizeof(orbfe_frustum));
+    memcpy(h->trk.hIn + L.oFr, frustum, sizeof(orbfe_frustum));
     size_t smallEnd;  // end of what has to go up behind the frame
     if (map) {
-        int* hid = reinterpret_cast<int*>(h->hTrkIn + L.oPts);
+        int* hid = reinterpret_cast<int*>(h->trk.hIn + L.oPts);
         if (M) memcpy(hid, ids, (size_t)M * sizeof(int));
         for (int i = M; i < Mb; i++) hid[i] = 0x7fffffff;
         smallEnd = L.oPts + (size_t)Mb * sizeof(int);
     } else {
-        if (M) memcpy(h->hTrkIn + L.oPts, points, (size_t)M * sizeof(orbfe_world_point));
+        if (M) memcpy(h->trk.hIn + L.oPts, points, (size_t)M * sizeof(orbfe_world_point));
         orbfe_world_point pad{};
         pad.bad = 1;
         pad.skip = 1;
-        orbfe_world_point* hp = reinterpret_cast<orbfe_world_point*>(h->hTrkIn + L.oPts);
+        orbfe_world_point* hp = reinterpret_cast<orbfe_world_point*>(h->trk.hIn + L.oPts);
         for (int i = M; i < Mb; i++) hp[i] = pad;
-        if (M) memcpy(h->hTrkIn + L.oMpDesc, mp_desc, (size_t)M * ORBFE_DESC_BYTES);
-        if (Mb > M) memset(h->hTrkIn + L.oMpDesc + (size_t)M * ORBFE_DESC_BYTES, 0, (size_t)(Mb - M) * ORBFE_DESC_BYTES);
+        if (M) memcpy(h->trk.hIn + L.oMpDesc, mp_desc, (size_t)M * ORBFE_DESC_BYTES);
+        if (Mb > M) memset(h->trk.hIn + L.oMpDesc + (size_t)M * ORBFE_DESC_BYTES, 0, (size_t)(Mb - M) * ORBFE_DESC_BYTES);
         smallEnd = L.inBytes;
     }
 
-    // ---- upload: pinned frames straight from the caller's buffer + the small block; pageable ones through the
-    //      pinned mirror, where frame and small block are ONE copy ----
-    bool direct = pitch <= h->dInPitch && (pitch & 3) == 0 && (reinterpret_cast<uintptr_t>(gray) & 3u) == 0;
-    if (direct) {
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, gray) != hipSuccess || attr.type != hipMemoryTypeHost) {
-            (void)hipGetLastError();
-            direct = false;
-        }
-    }
+    // ---- upload: the frame with the small block behind it ----
     int inPitch;
-    if (direct) {
-        inPitch = pitch;
-        HIPCHK(h, hipMemcpyAsync(h->dTrkIn, gray, (size_t)pitch * (H - 1) + (size_t)W, hipMemcpyHostToDevice, s));
-        HIPCHK(h, hipMemcpyAsync(h->dTrkIn + L.oFr, h->hTrkIn + L.oFr, smallEnd - L.oFr, hipMemcpyHostToDevice, s));
-    } else {
-        if ((pitch & 3) == 0 && pitch <= h->dInPitch) {  // a dword-aligned pitch is kept: the frame is one contiguous copy
-            inPitch = pitch;
-            memcpy(h->hTrkIn, gray, (size_t)pitch * (H - 1) + (size_t)W);
-        } else {
-            inPitch = h->dInPitch;
-            for (int y = 0; y < H; y++) memcpy(h->hTrkIn + (size_t)y * inPitch, gray + (size_t)y * pitch, (size_t)W);
-        }
-        HIPCHK(h, hipMemcpyAsync(h->dTrkIn, h->hTrkIn, smallEnd, hipMemcpyHostToDevice, s));
-    }
+    rc = upload_frame(h, h->trk, gray, pitch, L.oFr, smallEnd, s, &inPitch);
+    if (rc != ORBFE_OK) return rc;
 
-    // ---- kernels + download: replay the graph of this (bucket, pitch, parameters), capturing it first if needed ----
-    bool viaGraph = h->useGraph && !h->timing;
-    if (viaGraph) {
-        const orbfe_handle::TrackKey key{Mb, inPitch, tp->grid_cols, tp->grid_rows, tp->far_points, tp->min_x, tp->min_y,
-                                         tp->grid_inv_w, tp->grid_inv_h, tp->th, tp->nn_ratio, tp->th_far_points, map};
-        hipGraphExec_t exec = nullptr;
-        for (auto& g : h->trackGraphs)
-            if (memcmp(&g.key, &key, sizeof key) == 0) exec = g.exec;
-        if (!exec) {
-            hipGraph_t graph = nullptr;
-            {
-                CaptureStream cs;
-                rc = cs.begin() ? track_enqueue(h, L, Mb, inPitch, A, map, cs.s) : ORBFE_ERR_HIP;
-                graph = cs.end();
-            }
-            if (rc == ORBFE_OK && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) exec = nullptr;
-            if (graph) (void)hipGraphDestroy(graph);
-            if (!exec) {
-                graph_capture_failed(h);  // plain launches for this call
-                viaGraph = false;
-            } else {
-                graph_capture_succeeded(h);
-                if (h->trackGraphs.size() >= 64) track_drop_graphs(h);  // a caller cycling through parameters: bounded cache
-                h->trackGraphs.push_back({key, exec});
-            }
-        }
-        if (viaGraph) {
-            rc = scratch_acquire(h, h->extractUsed, h->extractStream, h->evExtract, s);
-            if (rc != ORBFE_OK) return rc;
-            HIPCHK(h, hipGraphLaunch(exec, s));
-            rc = extract_scratch_release(h, s);
-            if (rc != ORBFE_OK) return rc;
-            h->lastGray = h->dTrkIn;
-            h->lastStride = L.inFrame;
-            h->lastPitch = inPitch;
-            h->lastBatch = 1;
-        }
-    }
-    if (!viaGraph) {
-        rc = track_enqueue(h, L, Mb, inPitch, A, map, s);
-        if (rc != ORBFE_OK) return rc;
-    }
-    HIPCHK(h, hipStreamSynchronize(s));
+    // ---- kernels + download: the graph of this (bucket, pitch, parameters) ----
+    orbfe_handle::TrackKey key;
+    memset(&key, 0, sizeof key);
+    key.Mb = Mb; key.inPitch = inPitch; key.gridCols = tp->grid_cols; key.gridRows = tp->grid_rows; key.farPoints = tp->far_points;
+    key.minX = tp->min_x; key.minY = tp->min_y; key.invW = tp->grid_inv_w; key.invH = tp->grid_inv_h; key.th = tp->th;
+    key.nnRatio = tp->nn_ratio; key.thFar = tp->th_far_points; key.map = map;
+    rc = chain_submit(h, h->trackGraphs, 64, key, h->trk, L.inFrame, inPitch, s,
+                      [&](hipStream_t q) { return track_enqueue(h, L, Mb, inPitch, A, map, q); }, "orbfe_track_frame");
+    if (rc != ORBFE_OK) return rc;
 
     // ---- hand over ----
-    const int* head = reinterpret_cast<const int*>(h->hTrkOut);
-    if (head[1]) {
-        char buf[96];
-        snprintf(buf, sizeof buf, "device guard flags 0x%x in orbfe_track_frame", (unsigned)head[1]);
-        h->err = buf;
-        return ORBFE_ERR_INTERNAL;
-    }
-    const int n = head[0];
-    *n_out = n;
-    *n_matches = n > 0 ? head[2] : 0;
-    memcpy(kp_out, h->hTrkOut + L.oKp, (size_t)n * sizeof(orbfe_keypoint));
-    memcpy(desc_out, h->hTrkOut + L.oDesc, (size_t)n * ORBFE_DESC_BYTES);
-    memcpy(match_out, h->hTrkOut + L.oMatch, (size_t)n * sizeof(int));
-    if (per_level) memcpy(per_level, h->hTrkOut + L.oPer, (size_t)nL * sizeof(int));
-    if (mp_out && M) memcpy(mp_out, h->hTrkOut + L.oMps, (size_t)M * sizeof(orbfe_map_point));
-    if (proj_xr_out && M) memcpy(proj_xr_out, h->hTrkOut + L.oXr, (size_t)M * sizeof(float));
+    const int n = chain_prefix_copy_out(h, h->trk.hOut, L, kp_out, desc_out, n_out, per_level);
+    *n_matches = n > 0 ? reinterpret_cast<const int*>(h->trk.hOut)[2] : 0;
+    memcpy(match_out, h->trk.hOut + L.oMatch, (size_t)n * sizeof(int));
+    if (mp_out && M) memcpy(mp_out, h->trk.hOut + L.oMps, (size_t)M * sizeof(orbfe_map_point));
+    if (proj_xr_out && M) memcpy(proj_xr_out, h->trk.hOut + L.oXr, (size_t)M * sizeof(float));
     return ORBFE_OK;
 }
 
@@ -1794,7 +1843,7 @@ static void map_release(orbfe_map* m)
     orbfe_handle* h = m->h;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    track_drop_graphs(h);  // graphs of orbfe_track_frame_map hold this map's addresses
+    h->trackGraphs.drop();  // graphs of orbfe_track_frame_map hold this map's addresses
     for (orbfe_stream* st : h->rings)
         if (st->map == m) {  // a ring that was given this map: its later track submissions are refused, not served from freed memory
             st->map = nullptr;
@@ -2742,65 +2791,43 @@ int orbfe_match_bow(orbfe_handle* h, int G, const int* kf_off, const int* kf_idx
 // ---------------------------------------------------------------------------------------------
 namespace {
 
-struct RefLayout {
-    size_t inFrame, oRef, oFlags, inBytes;
-    size_t oPer, oKp, oDesc, oMatch, oBow, oLeaf, outBytes /* what is downloaded */, oBin, oGrp, oFIdx, oFCnt, oFOff, devBytes;
+struct RefLayout : ChainPrefix {
+    size_t oRef, oFlags, inBytes;
+    size_t oMatch, oBow, oLeaf, outBytes /* what is downloaded */, oBin, oGrp, oFIdx, oFCnt, oFOff, devBytes;
 };
 
 RefLayout ref_layout(const orbfe_handle* h, int capFlags)
 {
     RefLayout L{};
     const size_t cap = (size_t)h->P.kpCapFrame;
-    L.inFrame = align_up((size_t)h->dInPitch * h->prm.image_height, 256);
+    size_t off = chain_prefix_layout(h, L);
     L.oRef = L.inFrame;
     L.oFlags = L.oRef + align_up(sizeof(BowKfRef), 256);
     L.inBytes = L.oFlags + align_up((size_t)capFlags, 256);
-    size_t off = 256;
-    auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
-    L.oPer = take((size_t)h->nLevels * sizeof(int));
-    L.oKp = take(cap * sizeof(orbfe_keypoint));
-    L.oDesc = take(cap * ORBFE_DESC_BYTES);
-    L.oMatch = take(cap * sizeof(int));
-    L.oBow = take(cap * 2 * sizeof(int));
-    L.oLeaf = take(cap * sizeof(int));
+    L.oMatch = take256(off, cap * sizeof(int));
+    L.oBow = take256(off, cap * 2 * sizeof(int));
+    L.oLeaf = take256(off, cap * sizeof(int));
     L.outBytes = off;
-    L.oBin = take(cap * sizeof(int));
+    L.oBin = take256(off, cap * sizeof(int));
     // the per-node frame lists of frames above 7168 features (bow_track_launch): a key frame has at most capFlags nodes
-    L.oGrp = take(cap * sizeof(int));
-    L.oFIdx = take(cap * sizeof(int));
-    L.oFCnt = take((size_t)capFlags * sizeof(int));
-    L.oFOff = take(((size_t)capFlags + 1) * sizeof(int));
+    L.oGrp = take256(off, cap * sizeof(int));
+    L.oFIdx = take256(off, cap * sizeof(int));
+    L.oFCnt = take256(off, (size_t)capFlags * sizeof(int));
+    L.oFOff = take256(off, ((size_t)capFlags + 1) * sizeof(int));
     L.devBytes = off;
     return L;
 }
 
-void ref_drop_graphs(orbfe_handle* h)
-{
-    for (auto& g : h->refGraphs)
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    h->refGraphs.clear();
-}
-
 int ref_reserve(orbfe_handle* h, int nFlags)
 {
-    if (h->dRefIn && nFlags <= h->refCapFlags) return ORBFE_OK;
-    ref_drop_graphs(h);
-    if (h->dRefIn) (void)hipFree(h->dRefIn);
-    if (h->dRefOut) (void)hipFree(h->dRefOut);
-    if (h->hRefIn) (void)hipHostFree(h->hRefIn);
-    if (h->hRefOut) (void)hipHostFree(h->hRefOut);
-    h->dRefIn = h->dRefOut = h->hRefIn = h->hRefOut = nullptr;
+    if (h->ref.dIn && nFlags <= h->refCapFlags) return ORBFE_OK;
+    h->refGraphs.drop();
     h->refCapFlags = 0;
     const int capFlags = std::max(4096, nFlags + nFlags / 2);
     const RefLayout L = ref_layout(h, capFlags);
-    if (hipMalloc(&h->dRefIn, L.inBytes) != hipSuccess || hipMalloc(&h->dRefOut, L.devBytes) != hipSuccess ||
-        hipHostMalloc(&h->hRefIn, L.inBytes) != hipSuccess || hipHostMalloc(&h->hRefOut, L.outBytes) != hipSuccess) {
-        (void)hipGetLastError();
-        h->err = "orbfe_track_reference_keyframe: allocation of the staging blocks failed";
-        return ORBFE_ERR_OUT_OF_MEMORY;
-    }
-    h->refCapFlags = capFlags;
-    return ORBFE_OK;
+    const int rc = chain_blocks_alloc(h, h->ref, L.inBytes, L.devBytes, L.outBytes, "orbfe_track_reference_keyframe");
+    if (rc == ORBFE_OK) h->refCapFlags = capFlags;
+    return rc;
 }
 
 // the device side of one call, enqueued on s (directly, or under stream capture)
@@ -2808,35 +2835,35 @@ int ref_enqueue(orbfe_handle* h, const RefLayout& L, int inPitch, const orbfe::V
                 hipStream_t s)
 {
     const int cap = h->P.kpCapFrame;
-    int* dHead = reinterpret_cast<int*>(h->dRefOut);  // [n, status, n_matches]
-    orbfe_keypoint* dKp = reinterpret_cast<orbfe_keypoint*>(h->dRefOut + L.oKp);
-    int rc = extract_chain(h, h->dRefIn, L.inFrame, inPitch, 1, dKp, h->dRefOut + L.oDesc, dHead, reinterpret_cast<int*>(h->dRefOut + L.oPer),
+    int* dHead = reinterpret_cast<int*>(h->ref.dOut);  // [n, status, n_matches]
+    orbfe_keypoint* dKp = reinterpret_cast<orbfe_keypoint*>(h->ref.dOut + L.oKp);
+    int rc = extract_chain(h, h->ref.dIn, L.inFrame, inPitch, 1, dKp, h->ref.dOut + L.oDesc, dHead, reinterpret_cast<int*>(h->ref.dOut + L.oPer),
                            dHead + 1, s);
     if (rc != ORBFE_OK) return rc;
     std::string err;
-    int* dBow = reinterpret_cast<int*>(h->dRefOut + L.oBow);
-    rc = vocab_transform_launch_dev(v, s, h->dRefOut + L.oDesc, dHead, cap, levelsup, dBow, reinterpret_cast<int*>(h->dRefOut + L.oLeaf),
-                                    reinterpret_cast<int*>(h->dRefOut + L.oMatch), err);
+    int* dBow = reinterpret_cast<int*>(h->ref.dOut + L.oBow);
+    rc = vocab_transform_launch_dev(v, s, h->ref.dOut + L.oDesc, dHead, cap, levelsup, dBow, reinterpret_cast<int*>(h->ref.dOut + L.oLeaf),
+                                    reinterpret_cast<int*>(h->ref.dOut + L.oMatch), err);
     if (rc == ORBFE_OK) {
         BowTrackArgs A{};
-        A.ref = reinterpret_cast<const BowKfRef*>(h->dRefIn + L.oRef);
-        A.kfHasMP = h->dRefIn + L.oFlags;
+        A.ref = reinterpret_cast<const BowKfRef*>(h->ref.dIn + L.oRef);
+        A.kfHasMP = h->ref.dIn + L.oFlags;
         A.fKp = dKp;
-        A.fDesc = h->dRefOut + L.oDesc;
+        A.fDesc = h->ref.dOut + L.oDesc;
         A.fBow = dBow;
-        A.fLeaf = reinterpret_cast<const int*>(h->dRefOut + L.oLeaf);
+        A.fLeaf = reinterpret_cast<const int*>(h->ref.dOut + L.oLeaf);
         A.weight = v->dWeight;
         A.nF = dHead;
         A.cap = cap;
         A.nnRatio = nnRatio;
         A.checkOrientation = checkOri;
-        A.matchOut = reinterpret_cast<int*>(h->dRefOut + L.oMatch);
-        A.binOf = reinterpret_cast<int*>(h->dRefOut + L.oBin);
+        A.matchOut = reinterpret_cast<int*>(h->ref.dOut + L.oMatch);
+        A.binOf = reinterpret_cast<int*>(h->ref.dOut + L.oBin);
         A.nMatches = dHead + 2;
-        A.fGrp = reinterpret_cast<int*>(h->dRefOut + L.oGrp);
-        A.fIdx = reinterpret_cast<int*>(h->dRefOut + L.oFIdx);
-        A.fCnt = reinterpret_cast<int*>(h->dRefOut + L.oFCnt);
-        A.fOff = reinterpret_cast<int*>(h->dRefOut + L.oFOff);
+        A.fGrp = reinterpret_cast<int*>(h->ref.dOut + L.oGrp);
+        A.fIdx = reinterpret_cast<int*>(h->ref.dOut + L.oFIdx);
+        A.fCnt = reinterpret_cast<int*>(h->ref.dOut + L.oFCnt);
+        A.fOff = reinterpret_cast<int*>(h->ref.dOut + L.oFOff);
         A.capGroups = h->refCapFlags;
         rc = bow_track_launch(s, A, err);
     }
@@ -2844,7 +2871,7 @@ int ref_enqueue(orbfe_handle* h, const RefLayout& L, int inPitch, const orbfe::V
         h->err = err;
         return rc;
     }
-    HIPCHK(h, hipMemcpyAsync(h->hRefOut, h->dRefOut, L.outBytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(h->ref.hOut, h->ref.dOut, L.outBytes, hipMemcpyDeviceToHost, s));
     return ORBFE_OK;
 }
 
@@ -2866,105 +2893,37 @@ extern "C" int orbfe_track_reference_keyframe(orbfe_handle* h, const uint8_t* gr
     if (h->P.kpCapFrame >= (1 << 20)) return ORBFE_ERR_UNSUPPORTED;
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    const int W = h->prm.image_width, H = h->prm.image_height, nL = h->nLevels;
     int rc = ref_reserve(h, K->n);
     if (rc != ORBFE_OK) return rc;
     const RefLayout L = ref_layout(h, h->refCapFlags);
 
     // ---- the small block: which key frame (addresses of its resident arrays) + its flags as they stand now ----
     BowKfRef R{K->desc, K->kp, K->order, K->nodeList, K->nodeOff, K->G, K->n};
-    memcpy(h->hRefIn + L.oRef, &R, sizeof R);
-    if (K->n) memcpy(h->hRefIn + L.oFlags, kf_has_mp, (size_t)K->n);
+    memcpy(h->ref.hIn + L.oRef, &R, sizeof R);
+    if (K->n) memcpy(h->ref.hIn + L.oFlags, kf_has_mp, (size_t)K->n);
     const size_t smallEnd = L.oFlags + (size_t)K->n;
 
-    // ---- upload (as orbfe_track_frame): pinned frames straight from the caller's buffer, pageable ones through the mirror ----
-    bool direct = pitch <= h->dInPitch && (pitch & 3) == 0 && (reinterpret_cast<uintptr_t>(gray) & 3u) == 0;
-    if (direct) {
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, gray) != hipSuccess || attr.type != hipMemoryTypeHost) {
-            (void)hipGetLastError();
-            direct = false;
-        }
-    }
+    // ---- upload: the frame with the small block behind it ----
     int inPitch;
-    if (direct) {
-        inPitch = pitch;
-        HIPCHK(h, hipMemcpyAsync(h->dRefIn, gray, (size_t)pitch * (H - 1) + (size_t)W, hipMemcpyHostToDevice, s));
-        HIPCHK(h, hipMemcpyAsync(h->dRefIn + L.oRef, h->hRefIn + L.oRef, smallEnd - L.oRef, hipMemcpyHostToDevice, s));
-    } else {
-        if ((pitch & 3) == 0 && pitch <= h->dInPitch) {
-            inPitch = pitch;
-            memcpy(h->hRefIn, gray, (size_t)pitch * (H - 1) + (size_t)W);
-        } else {
-            inPitch = h->dInPitch;
-            for (int y = 0; y < H; y++) memcpy(h->hRefIn + (size_t)y * inPitch, gray + (size_t)y * pitch, (size_t)W);
-        }
-        HIPCHK(h, hipMemcpyAsync(h->dRefIn, h->hRefIn, smallEnd, hipMemcpyHostToDevice, s));
-    }
+    rc = upload_frame(h, h->ref, gray, pitch, L.oRef, smallEnd, s, &inPitch);
+    if (rc != ORBFE_OK) return rc;
 
-    // ---- kernels + download: replay the graph of this (pitch, vocabulary, parameters), capturing it first if needed ----
-    bool viaGraph = h->useGraph && !h->timing;
-    if (viaGraph) {
-        orbfe_handle::RefKey key;
-        memset(&key, 0, sizeof key);
-        key.inPitch = inPitch; key.levelsup = levelsup; key.checkOri = check_orientation; key.nnRatio = nn_ratio;
-        key.vocabSerial = vocab->serial;
-        hipGraphExec_t exec = nullptr;
-        for (auto& g : h->refGraphs)
-            if (memcmp(&g.key, &key, sizeof key) == 0) exec = g.exec;
-        if (!exec) {
-            hipGraph_t graph = nullptr;
-            {
-                CaptureStream cs;
-                rc = cs.begin() ? ref_enqueue(h, L, inPitch, vocab->v, levelsup, nn_ratio, check_orientation, cs.s) : ORBFE_ERR_HIP;
-                graph = cs.end();
-            }
-            if (rc == ORBFE_OK && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) exec = nullptr;
-            if (graph) (void)hipGraphDestroy(graph);
-            if (!exec) {
-                graph_capture_failed(h);  // plain launches for this call
-                viaGraph = false;
-            } else {
-                graph_capture_succeeded(h);
-                if (h->refGraphs.size() >= 16) ref_drop_graphs(h);  // vocabularies / parameters cycling: bounded cache
-                h->refGraphs.push_back({key, exec});
-            }
-        }
-        if (viaGraph) {
-            rc = scratch_acquire(h, h->extractUsed, h->extractStream, h->evExtract, s);
-            if (rc != ORBFE_OK) return rc;
-            HIPCHK(h, hipGraphLaunch(exec, s));
-            rc = extract_scratch_release(h, s);
-            if (rc != ORBFE_OK) return rc;
-            h->lastGray = h->dRefIn;
-            h->lastStride = L.inFrame;
-            h->lastPitch = inPitch;
-            h->lastBatch = 1;
-        }
-    }
-    if (!viaGraph) {
-        rc = ref_enqueue(h, L, inPitch, vocab->v, levelsup, nn_ratio, check_orientation, s);
-        if (rc != ORBFE_OK) return rc;
-    }
-    HIPCHK(h, hipStreamSynchronize(s));
+    // ---- kernels + download: the graph of this (pitch, vocabulary, parameters) ----
+    orbfe_handle::RefKey key;
+    memset(&key, 0, sizeof key);
+    key.inPitch = inPitch; key.levelsup = levelsup; key.checkOri = check_orientation; key.nnRatio = nn_ratio;
+    key.vocabSerial = vocab->serial;
+    rc = chain_submit(h, h->refGraphs, 16, key, h->ref, L.inFrame, inPitch, s,
+                      [&](hipStream_t q) { return ref_enqueue(h, L, inPitch, vocab->v, levelsup, nn_ratio, check_orientation, q); },
+                      "orbfe_track_reference_keyframe");
+    if (rc != ORBFE_OK) return rc;
 
     // ---- hand over ----
-    const int* head = reinterpret_cast<const int*>(h->hRefOut);
-    if (head[1]) {
-        char buf[112];
-        snprintf(buf, sizeof buf, "device guard flags 0x%x in orbfe_track_reference_keyframe", (unsigned)head[1]);
-        h->err = buf;
-        return ORBFE_ERR_INTERNAL;
-    }
-    const int n = head[0];
-    *n_out = n;
-    *n_matches = n > 0 ? head[2] : 0;
-    memcpy(kp_out, h->hRefOut + L.oKp, (size_t)n * sizeof(orbfe_keypoint));
-    memcpy(desc_out, h->hRefOut + L.oDesc, (size_t)n * ORBFE_DESC_BYTES);
-    memcpy(match_out, h->hRefOut + L.oMatch, (size_t)n * sizeof(int));
-    if (per_level) memcpy(per_level, h->hRefOut + L.oPer, (size_t)nL * sizeof(int));
-    const int* bow = reinterpret_cast<const int*>(h->hRefOut + L.oBow);
-    const int* leaf = reinterpret_cast<const int*>(h->hRefOut + L.oLeaf);
+    const int n = chain_prefix_copy_out(h, h->ref.hOut, L, kp_out, desc_out, n_out, per_level);
+    *n_matches = n > 0 ? reinterpret_cast<const int*>(h->ref.hOut)[2] : 0;
+    memcpy(match_out, h->ref.hOut + L.oMatch, (size_t)n * sizeof(int));
+    const int* bow = reinterpret_cast<const int*>(h->ref.hOut + L.oBow);
+    const int* leaf = reinterpret_cast<const int*>(h->ref.hOut + L.oLeaf);
     for (int i = 0; i < n; i++) {
         word_id_out[i] = bow[2 * i];
         node_id_out[i] = bow[2 * i + 1];
@@ -3039,56 +2998,34 @@ extern "C" int orbfe_init_frame_size(const orbfe_init_frame* f) { return f ? f->
 
 namespace {
 
-struct IniLayout {
-    size_t inFrame, inBytes;
-    size_t oPer, oKp, oDesc, oMatch, outBytes /* what is downloaded */, oScratch, devBytes;
+struct IniLayout : ChainPrefix {
+    size_t inBytes;
+    size_t oMatch, outBytes /* what is downloaded */, oScratch, devBytes;
 };
 
 IniLayout ini_layout(const orbfe_handle* h, int capN1, size_t scratchBytes)
 {
     IniLayout L{};
-    const size_t cap = (size_t)h->P.kpCapFrame;
-    L.inFrame = align_up((size_t)h->dInPitch * h->prm.image_height, 256);
+    size_t off = chain_prefix_layout(h, L);
     L.inBytes = L.inFrame;
-    size_t off = 256;
-    auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
-    L.oPer = take((size_t)h->nLevels * sizeof(int));
-    L.oKp = take(cap * sizeof(orbfe_keypoint));
-    L.oDesc = take(cap * ORBFE_DESC_BYTES);
-    L.oMatch = take((size_t)std::max(capN1, 1) * sizeof(int));
+    L.oMatch = take256(off, (size_t)std::max(capN1, 1) * sizeof(int));
     L.outBytes = off;
-    L.oScratch = take(scratchBytes);
+    L.oScratch = take256(off, scratchBytes);
     L.devBytes = off;
     return L;
 }
 
-void ini_drop_graphs(orbfe_handle* h)
-{
-    for (auto& g : h->iniGraphs)
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    h->iniGraphs.clear();
-}
-
 int ini_reserve(orbfe_handle* h, int n1, size_t scratchBytes)
 {
-    if (h->dIniIn && n1 <= h->iniCapN1 && scratchBytes <= h->iniScratchBytes) return ORBFE_OK;
-    ini_drop_graphs(h);
-    if (h->dIniIn) (void)hipFree(h->dIniIn);
-    if (h->dIniOut) (void)hipFree(h->dIniOut);
-    if (h->hIniIn) (void)hipHostFree(h->hIniIn);
-    if (h->hIniOut) (void)hipHostFree(h->hIniOut);
-    h->dIniIn = h->dIniOut = h->hIniIn = h->hIniOut = nullptr;
+    if (h->ini.dIn && n1 <= h->iniCapN1 && scratchBytes <= h->iniScratchBytes) return ORBFE_OK;
+    h->iniGraphs.drop();
     h->iniCapN1 = -1;
     h->iniScratchBytes = 0;
     const int capN1 = std::max(n1 + n1 / 2, h->P.kpCapFrame);  // the initial frame is a frame of this extractor: <= kpCapFrame keypoints
     const size_t capScratch = std::max(scratchBytes + scratchBytes / 2, init_track_scratch_bytes(capN1, std::min(capN1, 1024), h->P.kpCapFrame));
     const IniLayout L = ini_layout(h, capN1, capScratch);
-    if (hipMalloc(&h->dIniIn, L.inBytes) != hipSuccess || hipMalloc(&h->dIniOut, L.devBytes) != hipSuccess ||
-        hipHostMalloc(&h->hIniIn, L.inBytes) != hipSuccess || hipHostMalloc(&h->hIniOut, L.outBytes) != hipSuccess) {
-        (void)hipGetLastError();
-        h->err = "orbfe_track_initialization: allocation of the staging blocks failed";
-        return ORBFE_ERR_OUT_OF_MEMORY;
-    }
+    const int rc = chain_blocks_alloc(h, h->ini, L.inBytes, L.devBytes, L.outBytes, "orbfe_track_initialization");
+    if (rc != ORBFE_OK) return rc;
     h->iniCapN1 = capN1;
     h->iniScratchBytes = capScratch;
     return ORBFE_OK;
@@ -3099,22 +3036,22 @@ int ini_enqueue(orbfe_handle* h, const IniLayout& L, int inPitch, const orbfe_in
                 float nnRatio, int checkOri, hipStream_t s)
 {
     const int cap = h->P.kpCapFrame;
-    int* dHead = reinterpret_cast<int*>(h->dIniOut);  // [n, status, n_matches]
-    orbfe_keypoint* dKp = reinterpret_cast<orbfe_keypoint*>(h->dIniOut + L.oKp);
-    int rc = extract_chain(h, h->dIniIn, L.inFrame, inPitch, 1, dKp, h->dIniOut + L.oDesc, dHead, reinterpret_cast<int*>(h->dIniOut + L.oPer),
+    int* dHead = reinterpret_cast<int*>(h->ini.dOut);  // [n, status, n_matches]
+    orbfe_keypoint* dKp = reinterpret_cast<orbfe_keypoint*>(h->ini.dOut + L.oKp);
+    int rc = extract_chain(h, h->ini.dIn, L.inFrame, inPitch, 1, dKp, h->ini.dOut + L.oDesc, dHead, reinterpret_cast<int*>(h->ini.dOut + L.oPer),
                            dHead + 1, s);
     if (rc != ORBFE_OK) return rc;
     std::string err;
-    rc = init_track_launch(s, f1->n, f1->n0, f1->kp, f1->desc, f1->list0, dKp, h->dIniOut + L.oDesc, dHead, cap, tp->grid_cols, tp->grid_rows,
+    rc = init_track_launch(s, f1->n, f1->n0, f1->kp, f1->desc, f1->list0, dKp, h->ini.dOut + L.oDesc, dHead, cap, tp->grid_cols, tp->grid_rows,
                            tp->min_x, tp->min_y, tp->grid_inv_w, tp->grid_inv_h, window, nnRatio, checkOri,
-                           reinterpret_cast<int*>(h->dIniOut + L.oMatch), dHead + 2, h->dIniOut + L.oScratch, err);
+                           reinterpret_cast<int*>(h->ini.dOut + L.oMatch), dHead + 2, h->ini.dOut + L.oScratch, err);
     if (rc != ORBFE_OK) {
         h->err = err;
         return rc;
     }
     // [head | per-level | keypoints | descriptors | matches12 of THIS initial frame]: the block is laid out for iniCapN1 entries,
     // the copy stops behind the n1 that exist
-    HIPCHK(h, hipMemcpyAsync(h->hIniOut, h->dIniOut, L.oMatch + (size_t)std::max(f1->n, 1) * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(h->ini.hOut, h->ini.dOut, L.oMatch + (size_t)std::max(f1->n, 1) * sizeof(int), hipMemcpyDeviceToHost, s));
     return ORBFE_OK;
 }
 
@@ -3137,98 +3074,31 @@ extern "C" int orbfe_track_initialization(orbfe_handle* h, const uint8_t* gray, 
     if (h->P.kpCapFrame >= (1 << 20) || tp->grid_cols > 65535 || tp->grid_rows > 32767) return ORBFE_ERR_UNSUPPORTED;
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    const int W = h->prm.image_width, H = h->prm.image_height, nL = h->nLevels;
     int rc = ini_reserve(h, f1->n, init_track_scratch_bytes(f1->n, f1->n0, h->P.kpCapFrame));
     if (rc != ORBFE_OK) return rc;
     const IniLayout L = ini_layout(h, h->iniCapN1, h->iniScratchBytes);
 
-    // ---- upload (as orbfe_track_frame): pinned frames straight from the caller's buffer, pageable ones through the mirror ----
-    bool direct = pitch <= h->dInPitch && (pitch & 3) == 0 && (reinterpret_cast<uintptr_t>(gray) & 3u) == 0;
-    if (direct) {
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, gray) != hipSuccess || attr.type != hipMemoryTypeHost) {
-            (void)hipGetLastError();
-            direct = false;
-        }
-    }
+    // ---- upload: the frame alone ----
     int inPitch;
-    if (direct) {
-        inPitch = pitch;
-        HIPCHK(h, hipMemcpyAsync(h->dIniIn, gray, (size_t)pitch * (H - 1) + (size_t)W, hipMemcpyHostToDevice, s));
-    } else {
-        if ((pitch & 3) == 0 && pitch <= h->dInPitch) {
-            inPitch = pitch;
-            memcpy(h->hIniIn, gray, (size_t)pitch * (H - 1) + (size_t)W);
-        } else {
-            inPitch = h->dInPitch;
-            for (int y = 0; y < H; y++) memcpy(h->hIniIn + (size_t)y * inPitch, gray + (size_t)y * pitch, (size_t)W);
-        }
-        HIPCHK(h, hipMemcpyAsync(h->dIniIn, h->hIniIn, (size_t)inPitch * (H - 1) + (size_t)W, hipMemcpyHostToDevice, s));
-    }
+    rc = upload_frame(h, h->ini, gray, pitch, 0, 0, s, &inPitch);
+    if (rc != ORBFE_OK) return rc;
 
-    // ---- kernels + download: replay the graph of this (initial frame, pitch, parameters), capturing it first if needed ----
-    bool viaGraph = h->useGraph && !h->timing;
-    if (viaGraph) {
-        orbfe_handle::IniKey key;
-        memset(&key, 0, sizeof key);
-        key.inPitch = inPitch; key.gridCols = tp->grid_cols; key.gridRows = tp->grid_rows; key.window = window_size;
-        key.checkOri = check_orientation; key.minX = tp->min_x; key.minY = tp->min_y; key.invW = tp->grid_inv_w; key.invH = tp->grid_inv_h;
-        key.nnRatio = nn_ratio; key.frameSerial = f1->serial;
-        hipGraphExec_t exec = nullptr;
-        for (auto& g : h->iniGraphs)
-            if (memcmp(&g.key, &key, sizeof key) == 0) exec = g.exec;
-        if (!exec) {
-            hipGraph_t graph = nullptr;
-            {
-                CaptureStream cs;
-                rc = cs.begin() ? ini_enqueue(h, L, inPitch, f1, tp, window_size, nn_ratio, check_orientation, cs.s) : ORBFE_ERR_HIP;
-                graph = cs.end();
-            }
-            if (rc == ORBFE_OK && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) exec = nullptr;
-            if (graph) (void)hipGraphDestroy(graph);
-            if (!exec) {
-                graph_capture_failed(h);  // plain launches for this call
-                viaGraph = false;
-            } else {
-                graph_capture_succeeded(h);
-                if (h->iniGraphs.size() >= 8) ini_drop_graphs(h);  // initial frames come and go (:569-602): bounded cache
-                h->iniGraphs.push_back({key, exec});
-            }
-        }
-        if (viaGraph) {
-            rc = scratch_acquire(h, h->extractUsed, h->extractStream, h->evExtract, s);
-            if (rc != ORBFE_OK) return rc;
-            HIPCHK(h, hipGraphLaunch(exec, s));
-            rc = extract_scratch_release(h, s);
-            if (rc != ORBFE_OK) return rc;
-            h->lastGray = h->dIniIn;
-            h->lastStride = L.inFrame;
-            h->lastPitch = inPitch;
-            h->lastBatch = 1;
-        }
-    }
-    if (!viaGraph) {
-        rc = ini_enqueue(h, L, inPitch, f1, tp, window_size, nn_ratio, check_orientation, s);
-        if (rc != ORBFE_OK) return rc;
-    }
-    HIPCHK(h, hipStreamSynchronize(s));
+    // ---- kernels + download: the graph of this (initial frame, pitch, parameters) ----
+    orbfe_handle::IniKey key;
+    memset(&key, 0, sizeof key);
+    key.inPitch = inPitch; key.gridCols = tp->grid_cols; key.gridRows = tp->grid_rows; key.window = window_size;
+    key.checkOri = check_orientation; key.minX = tp->min_x; key.minY = tp->min_y; key.invW = tp->grid_inv_w; key.invH = tp->grid_inv_h;
+    key.nnRatio = nn_ratio; key.frameSerial = f1->serial;
+    rc = chain_submit(h, h->iniGraphs, 8, key, h->ini, L.inFrame, inPitch, s,  // initial frames come and go (:569-602)
+                      [&](hipStream_t q) { return ini_enqueue(h, L, inPitch, f1, tp, window_size, nn_ratio, check_orientation, q); },
+                      "orbfe_track_initialization");
+    if (rc != ORBFE_OK) return rc;
 
     // ---- hand over ----
-    const int* head = reinterpret_cast<const int*>(h->hIniOut);
-    if (head[1]) {
-        char buf[112];
-        snprintf(buf, sizeof buf, "device guard flags 0x%x in orbfe_track_initialization", (unsigned)head[1]);
-        h->err = buf;
-        return ORBFE_ERR_INTERNAL;
-    }
-    const int n = head[0];
-    *n_out = n;
-    memcpy(kp_out, h->hIniOut + L.oKp, (size_t)n * sizeof(orbfe_keypoint));
-    memcpy(desc_out, h->hIniOut + L.oDesc, (size_t)n * ORBFE_DESC_BYTES);
-    if (per_level) memcpy(per_level, h->hIniOut + L.oPer, (size_t)nL * sizeof(int));
+    const int n = chain_prefix_copy_out(h, h->ini.hOut, L, kp_out, desc_out, n_out, per_level);
     if (n > 0 && f1->n > 0) {
-        *n_matches = head[2];
-        memcpy(matches12_out, h->hIniOut + L.oMatch, (size_t)f1->n * sizeof(int));
+        *n_matches = reinterpret_cast<const int*>(h->ini.hOut)[2];
+        memcpy(matches12_out, h->ini.hOut + L.oMatch, (size_t)f1->n * sizeof(int));
     } else {  // the reference returns early on either empty frame (vnMatches12 all -1)
         *n_matches = 0;
         for (int i = 0; i < f1->n; i++) matches12_out[i] = -1;
