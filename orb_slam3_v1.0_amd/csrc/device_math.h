@@ -126,6 +126,30 @@ __device__ __forceinline__ float spec_logf(float x)
     return ef * 0x1.62ep-1f + (r + ef * 0x1.0bfbe8p-15f);
 }
 
+// MapPoint::PredictScale (src/MapPoint.cc:580-612) on the pinned logarithm, SPEC DECISION S8
+__device__ __forceinline__ int predict_scale(float maxDistance, float dist, float logScaleFactor, int nLevels)
+{
+    const float ratio = __fdiv_rn(maxDistance, dist);
+    const float q = __fdiv_rn(spec_logf(ratio), logScaleFactor);
+    int lvl;
+    if (!(q > 0.0f)) lvl = 0;
+    else if (q >= (float)nLevels) lvl = nLevels - 1;
+    else {
+        lvl = (int)ceilf(q);
+        if (lvl >= nLevels) lvl = nLevels - 1;
+    }
+    return lvl;
+}
+
+// R * (X, Y, Z) + t for a row-major 3 x 3 R, in the parenthesisation SPEC DECISION S8 pins: ((r0 X + r1 Y) + r2 Z) + t
+__device__ __forceinline__ void rigid_transform(const float (&R)[9], const float (&t)[3], float X, float Y, float Z, float& x,
+                                                float& y, float& z)
+{
+    x = ((R[0] * X + R[1] * Y) + R[2] * Z) + t[0];
+    y = ((R[3] * X + R[4] * Y) + R[5] * Z) + t[1];
+    z = ((R[6] * X + R[7] * Y) + R[8] * Z) + t[2];
+}
+
 // GeometricCamera::project of the two camera models (src/CameraModels/Pinhole.cpp:41-47,
 // src/CameraModels/KannalaBrandt8.cpp:66-83), same operation sequence as oracle/match_oracle.c camera_project.
 // `Frustum` is orbfe_frustum (include/orbfe.h); a template keeps this header free of the C ABI include.

@@ -37,9 +37,8 @@ __device__ __forceinline__ void frustum_point(const orbfe_frustum& F, int i, con
     do {
         if (p.skip || p.bad) break;  // src/Tracking.cc:1066-1069
         const float X = p.x, Y = p.y, Z = p.z;
-        const float pcx = ((F.rcw[0] * X + F.rcw[1] * Y) + F.rcw[2] * Z) + F.tcw[0];  // :282
-        const float pcy = ((F.rcw[3] * X + F.rcw[4] * Y) + F.rcw[5] * Z) + F.tcw[1];
-        const float pcz = ((F.rcw[6] * X + F.rcw[7] * Y) + F.rcw[8] * Z) + F.tcw[2];
+        float pcx, pcy, pcz;
+        rigid_transform(F.rcw, F.tcw, X, Y, Z, pcx, pcy, pcz);  // :282
         const float pcDist = sqrtf((pcx * pcx + pcy * pcy) + pcz * pcz);
         const float invz = __fdiv_rn(1.0f, pcz);
         if (pcz < 0.0f) break;  // :288
@@ -53,17 +52,8 @@ __device__ __forceinline__ void frustum_point(const orbfe_frustum& F, int i, con
         const float ox = X - F.twc[0], oy = Y - F.twc[1], oz = Z - F.twc[2];
         const float dist = sqrtf((ox * ox + oy * oy) + oz * oz);
         if (dist < minD || dist > maxD) break;
-        const float ratio = __fdiv_rn(p.max_distance, dist);
-        const float q = __fdiv_rn(spec_logf(ratio), F.log_scale_factor);
-        int nScale;
-        if (!(q > 0.0f)) nScale = 0;
-        else if (q >= (float)F.n_levels) nScale = F.n_levels - 1;
-        else {
-            nScale = (int)ceilf(q);
-            if (nScale >= F.n_levels) nScale = F.n_levels - 1;
-        }
         o.in_view = 1;
-        o.level = nScale;
+        o.level = predict_scale(p.max_distance, dist, F.log_scale_factor, F.n_levels);
         o.view_cos = 1.0f;  // :316: the normal test is disabled in this fork
         o.track_depth = pcDist;
         xr = u - F.mbf * invz;

@@ -1,5 +1,5 @@
-// kernels_match_bow.hip -- ORBmatcher::SearchByBoW on gfx950 (src/ORBmatcher.cc:133-327 incl.
-// ComputeThreeMaxima :1328-1370).  A frame feature belongs to exactly one vocabulary node, so the
+// kernels_match_bow.hip -- ORBmatcher::SearchByBoW on gfx950 (src/ORBmatcher.cc:133-327).
+// A frame feature belongs to exactly one vocabulary node, so the
 // greedy "already matched" skips (:188) never cross nodes: one wave walks the key-frame features of
 // a node sequentially and scans the node's frame features in parallel (top-2 under the total order
 // (distance, position in the node's list)); a single block then applies the rotation histogram.
@@ -46,7 +46,6 @@ __device__ __forceinline__ void bow_walk_node(const int* __restrict__ kfIdx, int
                                               const uint8_t* __restrict__ fDesc, int nLeftArg, float nnRatio, int checkOrientation,
                                               int* matchOut, int* binOf, AngKF kfAngle, AngF fAngle, int lane)
 {
-    const float factor = 1.0f / ORBFE_HISTO_LENGTH;
     for (int iKF = k0; iKF < k1e; iKF++) {  // sequential: later KF features skip matched frame features (:188)
         const int realIdxKF = kfIdx[iKF];
         if (!kfHasMP[realIdxKF]) continue;
@@ -83,13 +82,7 @@ __device__ __forceinline__ void bow_walk_node(const int* __restrict__ kfIdx, int
                 const int bestIdxF = kByIndex ? (int)(k1 & 0xffffffffu) : (int)fList[(int)(k1 & 0xffffffffu)];
                 if (lane == 0) {
                     matchOut[bestIdxF] = realIdxKF;
-                    if (checkOrientation) {
-                        float rot = kfAngle(realIdxKF) - fAngle(bestIdxF);
-                        if (rot < 0.0) rot = rot + 360.0f;
-                        int bin = (int)roundf(rot * factor);
-                        if (bin == ORBFE_HISTO_LENGTH) bin = 0;
-                        binOf[bestIdxF] = bin;
-                    }
+                    if (checkOrientation) binOf[bestIdxF] = rotation_bin(kfAngle(realIdxKF), fAngle(bestIdxF));
                 }
                 wrote = true;
             }
@@ -98,13 +91,7 @@ __device__ __forceinline__ void bow_walk_node(const int* __restrict__ kfIdx, int
                 const int bestIdxFR = kByIndex ? (int)(r1 & 0xffffffffu) : (int)fList[(int)(r1 & 0xffffffffu)];
                 if (lane == 0) {
                     matchOut[bestIdxFR] = realIdxKF;
-                    if (checkOrientation) {
-                        float rot = kfAngle(realIdxKF) - fAngle(bestIdxFR);
-                        if (rot < 0.0) rot = rot + 360.0f;
-                        int bin = (int)roundf(rot * factor);
-                        if (bin == ORBFE_HISTO_LENGTH) bin = 0;
-                        binOf[bestIdxFR] = bin;
-                    }
+                    if (checkOrientation) binOf[bestIdxFR] = rotation_bin(kfAngle(realIdxKF), fAngle(bestIdxFR));
                 }
                 wrote = true;
             }
@@ -124,52 +111,12 @@ __global__ __launch_bounds__(256) void bow_match_kernel(BowArgs A)
                   [&](int i) { return A.fAngle[i]; }, lane);
 }
 
-// rotation-histogram filter (:304-322) + count; single block
+// rotation filter (match_common.h) over the frame's features; single block
 __device__ __forceinline__ void bow_finalize_block(int* matchOut, const int* binOf, int nF, int checkOrientation, int* nMatches)
 {
-    __shared__ int hist[ORBFE_HISTO_LENGTH];
-    __shared__ int sInd[3];
-    __shared__ int sCount;
-    const int tid = threadIdx.x;
-    if (tid < ORBFE_HISTO_LENGTH) hist[tid] = 0;
-    if (tid == 0) sCount = 0;
-    __syncthreads();
-    int local = 0;
-    for (int j = tid; j < nF; j += blockDim.x)
-        if (matchOut[j] >= 0) {
-            local++;
-            if (checkOrientation) atomicAdd(&hist[binOf[j]], 1);
-        }
-    __syncthreads();
-    if (tid == 0) {
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        if (checkOrientation) {  // ComputeThreeMaxima :1328-1370
-            int max1 = 0, max2 = 0, max3 = 0;
-            for (int i = 0; i < ORBFE_HISTO_LENGTH; i++) {
-                const int s = hist[i];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-                else if (s > max3) { max3 = s; ind3 = i; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) { ind3 = -1; }
-        }
-        sInd[0] = ind1; sInd[1] = ind2; sInd[2] = ind3;
-    }
-    __syncthreads();
-    if (checkOrientation) {
-        for (int j = tid; j < nF; j += blockDim.x)
-            if (matchOut[j] >= 0) {
-                const int b = binOf[j];
-                if (b != sInd[0] && b != sInd[1] && b != sInd[2]) {
-                    matchOut[j] = -1;
-                    local--;
-                }
-            }
-    }
-    if (local) atomicAdd(&sCount, local);
-    __syncthreads();
-    if (tid == 0) *nMatches = sCount;
+    rotation_filter_block(
+        nF, checkOrientation, [&](int j) { return matchOut[j] >= 0; }, [&](int j) { return binOf[j]; },
+        [&](int j) { matchOut[j] = -1; }, nMatches);
 }
 
 __global__ __launch_bounds__(256) void bow_finalize_kernel(BowArgs A)
@@ -186,37 +133,6 @@ __global__ __launch_bounds__(256) void bow_finalize_kernel(BowArgs A)
 // A node the frame has no feature in is left after the collection (the lockstep walk of the two FeatureVectors,
 // :150-165, only stops at shared nodes).
 // ------------------------------------------------------------------------------------------------
-// wave64 minimum with DPP row operations (one VALU instruction per step instead of an LDS permute): quad swaps, row
-// half-mirror and mirror leave every lane of a 16-lane row with the row minimum; row_bcast 15 / 31 fold the rows into lane
-// 63, which is read back as a scalar.  Lanes a row mask leaves out receive the identity.
-__device__ __forceinline__ unsigned wave_min_u32(unsigned v)
-{
-    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
-    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
-    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x141, 0xF, 0xF, false));  // row_half_mirror
-    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x140, 0xF, 0xF, false));  // row_mirror
-    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x142, 0xA, 0xF, false));  // row_bcast:15 into rows 1 and 3
-    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x143, 0xC, 0xF, false));  // row_bcast:31 into rows 2 and 3
-    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-
-// wave-wide top-2 of per-lane (smallest, second smallest) pairs of 32-bit keys, distinct except for the "none" value:
-// the minimum, then the minimum with its owner's smallest key replaced by that lane's second
-__device__ __forceinline__ void wave_top2_u32(unsigned& k1, unsigned& k2)
-{
-    const unsigned m1 = wave_min_u32(k1);
-    const unsigned m2 = wave_min_u32(k1 == m1 ? k2 : k1);
-    k1 = m1;
-    k2 = m2;
-}
-
-__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v, int l)
-{
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
-    return ((unsigned long long)hi << 32) | lo;
-}
-
 // One wave per block, one vocabulary node of the key frame at a time.  The node ids of the frame's features are staged in
 // LDS once per block.  For a node the wave gathers the frame side -- descriptors and orientations: the first 64 features in
 // registers, the rest in LDS (two 16-byte halves, each its own array: conflict-free b128 reads); "matched" as a bit per
@@ -318,13 +234,7 @@ __global__ __launch_bounds__(64) void bow_track_kernel(BowTrackArgs A)
                             taken |= 1u << c;
                             const int bestIdxF = c == 0 ? idx0 : (int)list[pos];
                             A.matchOut[bestIdxF] = realIdxKF;
-                            if (A.checkOrientation) {
-                                float rot = angKF - (c == 0 ? ang0 : sAng[pos]);
-                                if (rot < 0.0) rot = rot + 360.0f;
-                                int bin = (int)roundf(rot * (1.0f / ORBFE_HISTO_LENGTH));
-                                if (bin == ORBFE_HISTO_LENGTH) bin = 0;
-                                A.binOf[bestIdxF] = bin;
-                            }
+                            if (A.checkOrientation) A.binOf[bestIdxF] = rotation_bin(angKF, c == 0 ? ang0 : sAng[pos]);
                         }
                     }
                 }

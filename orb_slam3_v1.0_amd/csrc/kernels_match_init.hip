@@ -119,7 +119,6 @@ __global__ __launch_bounds__(kInitThreads) void init_match_kernel(InitArgs A)
     }
     const int n0 = sN0;
     int* mdist = LDS ? S.dist : A.matchedDist;
-    const float factor = 1.0f / ORBFE_HISTO_LENGTH;
 
     for (int t = 0; t < n0; t++) {
         const int i1 = A.list0[t];
@@ -163,8 +162,7 @@ __global__ __launch_bounds__(kInitThreads) void init_match_kernel(InitArgs A)
                 if (!(fabsf(dx) < r && fabsf(dy) < r)) continue;
                 int dist;
                 if (LDS)
-                    dist = __popcll(S.desc[j][0] ^ d4[0]) + __popcll(S.desc[j][1] ^ d4[1]) + __popcll(S.desc[j][2] ^ d4[2]) +
-                           __popcll(S.desc[j][3] ^ d4[3]);
+                    dist = hamming256(S.desc[j], d4[0], d4[1], d4[2], d4[3]);
                 else
                     dist = hamming256(reinterpret_cast<const uint2*>(A.desc2 + (size_t)j * 32), d4);
                 if (mdist[j] <= dist) continue;  // :368-369
@@ -191,10 +189,7 @@ __global__ __launch_bounds__(kInitThreads) void init_match_kernel(InitArgs A)
                     mdist[bestIdx2] = bestDist;
                     sNm++;
                     if (A.checkOrientation) {
-                        float rot = k1p.angle - A.kp2[bestIdx2].angle;
-                        if (rot < 0.0) rot = rot + 360.0f;
-                        int bin = (int)roundf(rot * factor);
-                        if (bin == ORBFE_HISTO_LENGTH) bin = 0;
+                        const int bin = rotation_bin(k1p.angle, A.kp2[bestIdx2].angle);
                         sHist[bin]++;
                         A.binOf[i1] = bin;
                     }
@@ -204,20 +199,9 @@ __global__ __launch_bounds__(kInitThreads) void init_match_kernel(InitArgs A)
         __syncthreads();
     }
 
-    // ---- rotation histogram filter (:411-435; ComputeThreeMaxima :1328-1370) ----
+    // ---- rotation histogram filter (:411-435) ----
     if (A.checkOrientation) {
-        if (tid == 0) {
-            int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-            for (int i = 0; i < ORBFE_HISTO_LENGTH; i++) {
-                const int s = sHist[i];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-                else if (s > max3) { max3 = s; ind3 = i; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) { ind3 = -1; }
-            sInd[0] = ind1; sInd[1] = ind2; sInd[2] = ind3;
-        }
+        if (tid == 0) three_maxima(sHist, sInd[0], sInd[1], sInd[2]);
         __syncthreads();
         for (int i = tid; i < n1; i += kInitThreads) {
             const int b = A.binOf[i];
@@ -250,13 +234,6 @@ struct InitRowHdr {
     int cnt, pad;
     unsigned long long top[4];  // the row's smallest keys, ascending, kKeyNone-padded
 };
-
-__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v, int l)
-{
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
-    return ((unsigned long long)hi << 32) | lo;
-}
 
 __global__ __launch_bounds__(256) void init_cand_kernel(InitArgs A, int n0)
 {
@@ -305,8 +282,7 @@ __global__ __launch_bounds__(256) void init_cand_kernel(InitArgs A, int n0)
                 const float dx = k.x - x, dy = k.y - y;
                 if (!(fabsf(dx) < r && fabsf(dy) < r)) ok = false;
                 if (ok) {
-                    const unsigned long long* kd = reinterpret_cast<const unsigned long long*>(A.desc2 + (size_t)j * 32);
-                    const int dist = __popcll(kd[0] ^ d0) + __popcll(kd[1] ^ d1) + __popcll(kd[2] ^ d2) + __popcll(kd[3] ^ d3);
+                    const int dist = hamming256(reinterpret_cast<const unsigned long long*>(A.desc2 + (size_t)j * 32), d0, d1, d2, d3);
                     key = ((unsigned long long)dist << 52) | ((unsigned long long)cx << 36) | ((unsigned long long)cy << 20) |
                           (unsigned long long)j;
                 }
@@ -472,32 +448,17 @@ __global__ __launch_bounds__(kInitThreads) void init_order_kernel(InitArgs A, in
     }
     __syncthreads();
 
-    // ---- rotation histogram over every accept (:395-405), ComputeThreeMaxima (:1328-1370) ----
+    // ---- rotation histogram over every accept (:395-405) ----
     if (A.checkOrientation) {
-        const float factor = 1.0f / ORBFE_HISTO_LENGTH;
         for (int t = tid; t < n0; t += kInitThreads) {
             const int j = T.acc[t];
             if (j < 0) continue;
-            float rot = T.angle1[t] - T.angle2[j];
-            if (rot < 0.0) rot = rot + 360.0f;
-            int bin = (int)roundf(rot * factor);
-            if (bin == ORBFE_HISTO_LENGTH) bin = 0;
+            const int bin = rotation_bin(T.angle1[t], T.angle2[j]);
             atomicAdd(&sHist[bin], 1);
             T.off[t] = bin;  // (the row offsets are no longer needed)
         }
         __syncthreads();
-        if (tid == 0) {
-            int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-            for (int i = 0; i < ORBFE_HISTO_LENGTH; i++) {
-                const int s = sHist[i];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-                else if (s > max3) { max3 = s; ind3 = i; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) { ind3 = -1; }
-            sInd[0] = ind1; sInd[1] = ind2; sInd[2] = ind3;
-        }
+        if (tid == 0) three_maxima(sHist, sInd[0], sInd[1], sInd[2]);
         __syncthreads();
     }
     // ---- vnMatches12 and the count: keypoint j of frame 2 belongs to the row that owns it in the end, unless the rotation

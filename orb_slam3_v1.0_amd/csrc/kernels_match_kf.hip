@@ -67,9 +67,8 @@ __device__ __forceinline__ void fuse_walk(const ProjArgs& A, const orbfe_frustum
     do {
         if (skipped || (!GATHER && p.skip) || p.bad) break;  // :706-721 (a resident entry's own skip member is per frame: ignored)
         const float X = p.x, Y = p.y, Z = p.z;
-        const float pcx = ((F.rcw[0] * X + F.rcw[1] * Y) + F.rcw[2] * Z) + F.tcw[0];
-        const float pcy = ((F.rcw[3] * X + F.rcw[4] * Y) + F.rcw[5] * Z) + F.tcw[1];
-        const float pcz = ((F.rcw[6] * X + F.rcw[7] * Y) + F.rcw[8] * Z) + F.tcw[2];
+        float pcx, pcy, pcz;
+        rigid_transform(F.rcw, F.tcw, X, Y, Z, pcx, pcy, pcz);
         if (pcz < 0.0f) break;  // :725
         const float invz = 1.0f / pcz;
         float u, v;
@@ -80,15 +79,7 @@ __device__ __forceinline__ void fuse_walk(const ProjArgs& A, const orbfe_frustum
         const float ox = X - F.twc[0], oy = Y - F.twc[1], oz = Z - F.twc[2];
         const float dist3D = sqrtf((ox * ox + oy * oy) + oz * oz);
         if (dist3D < minD || dist3D > maxD) break;  // :748
-        const float ratio = p.max_distance / dist3D;  // PredictScale
-        const float q = spec_logf(ratio) / F.log_scale_factor;
-        int lvl;
-        if (!(q > 0.0f)) lvl = 0;
-        else if (q >= (float)F.n_levels) lvl = F.n_levels - 1;
-        else {
-            lvl = (int)ceilf(q);
-            if (lvl >= F.n_levels) lvl = F.n_levels - 1;
-        }
+        const int lvl = predict_scale(p.max_distance, dist3D, F.log_scale_factor, F.n_levels);
         MpWindow w;
         w.valid = true;
         w.x = u;
@@ -98,44 +89,33 @@ __device__ __forceinline__ void fuse_walk(const ProjArgs& A, const orbfe_frustum
         if (!w.valid) break;
         const unsigned long long* dp = reinterpret_cast<const unsigned long long*>(mpDesc + (size_t)src * 32);
         const unsigned long long d0 = dp[0], d1 = dp[1], d2 = dp[2], d3 = dp[3];
-        const int tabStride = A.g.cols + 1;
+        // 1 / sigma^2 of the two levels the walk visits (:787), read once
+        const float invS2Lo = chi2Gate ? invLevelSigma2[max(lvl - 1, 0)] : 0.0f, invS2Hi = chi2Gate ? invLevelSigma2[lvl] : 0.0f;
         uint32_t best = kKey32None;
-        for (int l = max(lvl - 1, 0); l <= min(lvl, A.tabLevels - 1); l++) {  // :787
-            const int* csl = A.colStart + (size_t)l * tabStride;
-            const float invS2 = chi2Gate ? invLevelSigma2[l] : 0.0f;
-            {
-                const int s = csl[w.minCX], e = csl[w.maxCX + 1];  // all rows of the window's columns
-                for (int sl = s; sl < e; sl++) {
-                    const int4 rq = A.rec[sl];
-                    const int cy = rq.y >> 8;
-                    if (cy < w.minCY || cy > w.maxCY) continue;
-                    const float kx = __int_as_float(rq.z), ky = __int_as_float(rq.w);
-                    if (!(fabsf(kx - u) < w.r && fabsf(ky - v) < w.r)) continue;  // src/KeyFrame.cc:826
-                    const float ex = u - kx, ey = v - ky;
-                    float kur = -1.0f;
-                    if (uRight) kur = uRight[A.order[rq.x]];
-                    if (!chi2Gate) {
-                        // the Sim3 overload (:864-975) has no reprojection gate
-                    } else if (kur >= 0) {  // :792-805
-                        const float er = ur - kur;
-                        const float e2 = (ex * ex + ey * ey) + er * er;
-                        if ((double)(e2 * invS2) > 7.8) continue;
-                    } else {
-                        const float e2 = ex * ex + ey * ey;
-                        if ((double)(e2 * invS2) > 5.99) continue;
-                    }
-                    if (CANDS) sink.push((uint32_t)rq.x);  // passed every gate of :787-820
-                    const unsigned long long* kd = A.descS + (size_t)sl * 4;
-                    if (rightDesc) {  // bRight (:820): the left feature passed the gates, its right twin's row is compared
-                        const int idx = A.order[rq.x];
-                        if (idx >= nRight) continue;
-                        kd = rightDesc + (size_t)idx * 4;
-                    }
-                    const int dist = __popcll(kd[0] ^ d0) + __popcll(kd[1] ^ d1) + __popcll(kd[2] ^ d2) + __popcll(kd[3] ^ d3);
-                    best = min(best, make_key32(dist, rq.x));
-                }
+        window_walk(A, w, lvl, [&](int l, int sl, const int4& rq) {
+            const float invS2 = l == lvl ? invS2Hi : invS2Lo;
+            const float ex = u - __int_as_float(rq.z), ey = v - __int_as_float(rq.w);
+            float kur = -1.0f;
+            if (uRight) kur = uRight[A.order[rq.x]];
+            if (!chi2Gate) {
+                // the Sim3 overload (:864-975) has no reprojection gate
+            } else if (kur >= 0) {  // :792-805
+                const float er = ur - kur;
+                const float e2 = (ex * ex + ey * ey) + er * er;
+                if ((double)(e2 * invS2) > 7.8) return;
+            } else {
+                const float e2 = ex * ex + ey * ey;
+                if ((double)(e2 * invS2) > 5.99) return;
             }
-        }
+            if (CANDS) sink.push((uint32_t)rq.x);  // passed every gate of :787-820
+            const unsigned long long* kd = A.descS + (size_t)sl * 4;
+            if (rightDesc) {  // bRight (:820): the left feature passed the gates, its right twin's row is compared
+                const int idx = A.order[rq.x];
+                if (idx >= nRight) return;
+                kd = rightDesc + (size_t)idx * 4;
+            }
+            best = min(best, make_key32(hamming256(kd, d0, d1, d2, d3), rq.x));
+        });
         if (best != kKey32None) {
             bestIdx = A.order[best & kRankMask] + (rightDesc ? A.kpStride : 0);
             bestDist = (int)(best >> kRankBits);
@@ -223,21 +203,6 @@ __global__ __launch_bounds__(64) void fuse_neighbors_kernel(const FuseTarget* __
     }
 }
 
-// PredictScale (src/MapPoint.cc:580-612) on the pinned logarithm, SPEC DECISION S8
-__device__ __forceinline__ int predict_scale(float maxDistance, float dist, float logScaleFactor, int nLevels)
-{
-    const float ratio = maxDistance / dist;
-    const float q = spec_logf(ratio) / logScaleFactor;
-    int lvl;
-    if (!(q > 0.0f)) lvl = 0;
-    else if (q >= (float)nLevels) lvl = nLevels - 1;
-    else {
-        lvl = (int)ceilf(q);
-        if (lvl >= nLevels) lvl = nLevels - 1;
-    }
-    return lvl;
-}
-
 // ---------------------------------------------------------------------------------------------
 // One direction of ORBmatcher::SearchBySim3 (src/ORBmatcher.cc:1017-1092, :1094-1170): thread per map point of
 // the source key frame -- source pose, similarity, the pinhole expression the function writes out itself
@@ -254,13 +219,9 @@ __global__ __launch_bounds__(256) void sim3_search_kernel(ProjArgs A, orbfe_sim3
     int bestIdx = -1;
     do {
         if (p.skip || p.bad) break;  // :1021-1025
-        const float X = p.x, Y = p.y, Z = p.z;
-        const float ax = ((D.rcw[0] * X + D.rcw[1] * Y) + D.rcw[2] * Z) + D.tcw[0];
-        const float ay = ((D.rcw[3] * X + D.rcw[4] * Y) + D.rcw[5] * Z) + D.tcw[1];
-        const float az = ((D.rcw[6] * X + D.rcw[7] * Y) + D.rcw[8] * Z) + D.tcw[2];
-        const float bx = ((D.sr[0] * ax + D.sr[1] * ay) + D.sr[2] * az) + D.t[0];
-        const float by = ((D.sr[3] * ax + D.sr[4] * ay) + D.sr[5] * az) + D.t[1];
-        const float bz = ((D.sr[6] * ax + D.sr[7] * ay) + D.sr[8] * az) + D.t[2];
+        float ax, ay, az, bx, by, bz;
+        rigid_transform(D.rcw, D.tcw, p.x, p.y, p.z, ax, ay, az);  // source pose, then the similarity
+        rigid_transform(D.sr, D.t, ax, ay, az, bx, by, bz);
         if (bz < 0.0f) break;  // :1032
         const float invz = 1.0f / bz;
         const float x = bx * invz, y = by * invz;
@@ -279,22 +240,10 @@ __global__ __launch_bounds__(256) void sim3_search_kernel(ProjArgs A, orbfe_sim3
         if (!w.valid) break;
         const unsigned long long* dp = reinterpret_cast<const unsigned long long*>(mpDesc + (size_t)i * 32);
         const unsigned long long d0 = dp[0], d1 = dp[1], d2 = dp[2], d3 = dp[3];
-        const int tabStride = A.g.cols + 1;
         uint32_t best = kKey32None;
-        for (int l = max(lvl - 1, 0); l <= min(lvl, A.tabLevels - 1); l++) {  // :1078
-            const int* csl = A.colStart + (size_t)l * tabStride;
-            const int s = csl[w.minCX], e = csl[w.maxCX + 1];
-            for (int sl = s; sl < e; sl++) {
-                const int4 rq = A.rec[sl];
-                const int cy = rq.y >> 8;
-                if (cy < w.minCY || cy > w.maxCY) continue;
-                const float kx = __int_as_float(rq.z), ky = __int_as_float(rq.w);
-                if (!(fabsf(kx - u) < w.r && fabsf(ky - v) < w.r)) continue;  // src/KeyFrame.cc:826
-                const unsigned long long* kd = A.descS + (size_t)sl * 4;
-                const int dist = __popcll(kd[0] ^ d0) + __popcll(kd[1] ^ d1) + __popcll(kd[2] ^ d2) + __popcll(kd[3] ^ d3);
-                best = min(best, make_key32(dist, rq.x));
-            }
-        }
+        window_walk(A, w, lvl, [&](int, int sl, const int4& rq) {
+            best = min(best, make_key32(hamming256(A.descS + (size_t)sl * 4, d0, d1, d2, d3), rq.x));
+        });
         if (best != kKey32None && (int)(best >> kRankBits) <= ORBFE_TH_HIGH) bestIdx = A.order[best & kRankMask];  // :1088
     } while (false);
     vnMatch[i] = bestIdx;
@@ -343,9 +292,8 @@ __global__ __launch_bounds__(256) void reloc_project_kernel(orbfe_frustum F, int
     do {
         if (p.skip || p.bad) break;  // :1221-1225
         const float X = p.x, Y = p.y, Z = p.z;
-        const float pcx = ((F.rcw[0] * X + F.rcw[1] * Y) + F.rcw[2] * Z) + F.tcw[0];
-        const float pcy = ((F.rcw[3] * X + F.rcw[4] * Y) + F.rcw[5] * Z) + F.tcw[1];
-        const float pcz = ((F.rcw[6] * X + F.rcw[7] * Y) + F.rcw[8] * Z) + F.tcw[2];
+        float pcx, pcy, pcz;
+        rigid_transform(F.rcw, F.tcw, X, Y, Z, pcx, pcy, pcz);
         float u, v;
         camera_project(F, pcx, pcy, pcz, u, v);  // no depth test in this overload
         if (u < F.min_x || u > F.max_x) break;   // :1232-1235
@@ -363,66 +311,14 @@ __global__ __launch_bounds__(256) void reloc_project_kernel(orbfe_frustum F, int
     out[i] = o;
 }
 
-// rotation histogram + three maxima (:1287-1323) over the claimed keypoints; single block
+// rotation filter over the claimed keypoints (match_common.h); single block
 __global__ __launch_bounds__(256) void reloc_finalize_kernel(int n, const orbfe_keypoint* __restrict__ kp,
                                                              const float* __restrict__ kfAngle, int checkOrientation,
                                                              int* __restrict__ matchOut, int* __restrict__ nMatches)
 {
-    __shared__ int hist[ORBFE_HISTO_LENGTH];
-    __shared__ int sInd[3];
-    __shared__ int sCount;
-    const int tid = threadIdx.x;
-    if (tid < ORBFE_HISTO_LENGTH) hist[tid] = 0;
-    if (tid == 0) sCount = 0;
-    __syncthreads();
-    const float factor = 1.0f / ORBFE_HISTO_LENGTH;
-    int local = 0;
-    for (int j = tid; j < n; j += blockDim.x) {
-        const int i = matchOut[j];
-        if (i < 0) continue;
-        local++;
-        if (checkOrientation) {
-            float rot = kfAngle[i] - kp[j].angle;
-            if (rot < 0.0f) rot = rot + 360.0f;
-            int bin = (int)roundf(rot * factor);
-            if (bin == ORBFE_HISTO_LENGTH) bin = 0;
-            atomicAdd(&hist[bin], 1);
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        if (checkOrientation) {  // ComputeThreeMaxima :1328-1370
-            int max1 = 0, max2 = 0, max3 = 0;
-            for (int i = 0; i < ORBFE_HISTO_LENGTH; i++) {
-                const int s = hist[i];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-                else if (s > max3) { max3 = s; ind3 = i; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) { ind3 = -1; }
-        }
-        sInd[0] = ind1; sInd[1] = ind2; sInd[2] = ind3;
-    }
-    __syncthreads();
-    if (checkOrientation) {
-        for (int j = tid; j < n; j += blockDim.x) {
-            const int i = matchOut[j];
-            if (i < 0) continue;
-            float rot = kfAngle[i] - kp[j].angle;
-            if (rot < 0.0f) rot = rot + 360.0f;
-            int bin = (int)roundf(rot * factor);
-            if (bin == ORBFE_HISTO_LENGTH) bin = 0;
-            if (bin != sInd[0] && bin != sInd[1] && bin != sInd[2]) {
-                matchOut[j] = -1;
-                local--;
-            }
-        }
-    }
-    if (local) atomicAdd(&sCount, local);
-    __syncthreads();
-    if (tid == 0) *nMatches = sCount;
+    rotation_filter_block(
+        n, checkOrientation, [&](int j) { return matchOut[j] >= 0; },
+        [&](int j) { return rotation_bin(kfAngle[matchOut[j]], kp[j].angle); }, [&](int j) { matchOut[j] = -1; }, nMatches);
 }
 
 }  // namespace

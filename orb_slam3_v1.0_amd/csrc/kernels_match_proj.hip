@@ -335,10 +335,10 @@ __device__ __forceinline__ int topk_scan(const ProjArgs& A, const MpWindow& w, c
             int dist;
             if constexpr (LDS) {
                 const unsigned long long* kd = S->desc[p - segBase];
-                dist = __popcll(kd[0] ^ d0) + __popcll(kd[1] ^ d1) + __popcll(kd[2] ^ d2) + __popcll(kd[3] ^ d3);
+                dist = hamming256(kd, d0, d1, d2, d3);
             } else {
                 const unsigned long long* kd = descS + (size_t)p * 4;
-                dist = __popcll(kd[0] ^ d0) + __popcll(kd[1] ^ d1) + __popcll(kd[2] ^ d2) + __popcll(kd[3] ^ d3);
+                dist = hamming256(kd, d0, d1, d2, d3);
             }
             if (dist >= A.dCut) continue;  // cannot change the verdict (proj_dcut)
             total++;
@@ -558,10 +558,10 @@ __device__ __forceinline__ void topk_wave_body(const ProjArgs& A, const TopkLds&
                         int dist;
                         if constexpr (LDS) {
                             const unsigned long long* kd = S.desc[p - segBase];
-                            dist = __popcll(kd[0] ^ d[0]) + __popcll(kd[1] ^ d[1]) + __popcll(kd[2] ^ d[2]) + __popcll(kd[3] ^ d[3]);
+                            dist = hamming256(kd, d[0], d[1], d[2], d[3]);
                         } else {
                             const unsigned long long* kd = descS + (size_t)p * 4;
-                            dist = __popcll(kd[0] ^ d[0]) + __popcll(kd[1] ^ d[1]) + __popcll(kd[2] ^ d[2]) + __popcll(kd[3] ^ d[3]);
+                            dist = hamming256(kd, d[0], d[1], d[2], d[3]);
                         }
                         if (dist < A.dCut) {  // proj_dcut
                             q = true;
@@ -690,17 +690,6 @@ struct ResolveLdsT {
     // compete for look-alike keypoints) then never wait on global memory
     unsigned long long desc[DESC ? N * 4 : 4];
 };
-
-__device__ __forceinline__ void wave_top2_u32(uint32_t& k1, uint32_t& k2)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t o1 = __shfl_xor(k1, d), o2 = __shfl_xor(k2, d);
-        const uint32_t lo = min(k1, o1), hi = max(k1, o1);
-        k2 = min(hi, min(k2, o2));
-        k1 = lo;
-    }
-}
 
 // exact rescan for a map point whose stored top-K ran dry: one WAVE scans the contiguous rank range of the
 // window's grid columns (lane-strided) and reduces the two smallest free keys; all lanes get the result.

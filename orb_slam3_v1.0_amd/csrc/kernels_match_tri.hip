@@ -203,64 +203,17 @@ __global__ __launch_bounds__(256) void tri_match_kernel(TriArgs A)
     }
     if (bestIdx2 >= 0) {
         A.match12[idx1] = bestIdx2;
-        if (A.checkOrientation) {
-            float rot = k1.angle - A.kp2[bestIdx2].angle;
-            if (rot < 0.0) rot += 360.0f;
-            int bin = (int)roundf(rot * (1.0f / ORBFE_HISTO_LENGTH));
-            if (bin == ORBFE_HISTO_LENGTH) bin = 0;
-            A.binOf[idx1] = bin;
-        }
+        if (A.checkOrientation) A.binOf[idx1] = rotation_bin(k1.angle, A.kp2[bestIdx2].angle);
     }
 }
 
-// rotation-histogram filter (:633-661) + count; single block
+// rotation filter (match_common.h) over the features of key frame 1; single block
 __global__ __launch_bounds__(256) void tri_finalize_kernel(TriArgs A)
 {
-    __shared__ int hist[ORBFE_HISTO_LENGTH];
-    __shared__ int sInd[3];
-    __shared__ int sCount;
-    const int tid = threadIdx.x;
-    if (tid < ORBFE_HISTO_LENGTH) hist[tid] = 0;
-    if (tid == 0) sCount = 0;
-    __syncthreads();
-    int local = 0;
-    for (int j = tid; j < A.n1; j += blockDim.x)
-        if (A.match12[j] >= 0) {
-            local++;
-            if (A.checkOrientation) atomicAdd(&hist[A.binOf[j]], 1);
-        }
-    __syncthreads();
-    if (tid == 0) {
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        if (A.checkOrientation) {  // ComputeThreeMaxima :1328-1370
-            int max1 = 0, max2 = 0, max3 = 0;
-            for (int i = 0; i < ORBFE_HISTO_LENGTH; i++) {
-                const int s = hist[i];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-                else if (s > max3) { max3 = s; ind3 = i; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) { ind3 = -1; }
-        }
-        sInd[0] = ind1; sInd[1] = ind2; sInd[2] = ind3;
-    }
-    __syncthreads();
-    if (A.checkOrientation) {
-        for (int j = tid; j < A.n1; j += blockDim.x)
-            if (A.match12[j] >= 0) {
-                const int bb = A.binOf[j];
-                if (bb != sInd[0] && bb != sInd[1] && bb != sInd[2]) {
-                    A.match12[j] = -1;
-                    local--;
-                }
-            }
-    }
-    if (local) atomicAdd(&sCount, local);
-    __syncthreads();
-    if (tid == 0) *A.nMatches = sCount;
+    rotation_filter_block(
+        A.n1, A.checkOrientation, [&](int j) { return A.match12[j] >= 0; }, [&](int j) { return A.binOf[j]; },
+        [&](int j) { A.match12[j] = -1; }, A.nMatches);
 }
-
 
 // ---------------------------------------------------------------------------------------------
 // One key frame against K neighbours in ONE launch (LocalMapping::CreateNewMapPoints, src/LocalMapping.cc:455-488: up to
@@ -365,12 +318,8 @@ __global__ __launch_bounds__(256) void tri_batch_kernel(const TriNeighbour* __re
                     bestDist = dist;
                 }
             }
-            if (bestIdx2 >= 0) {  // :619-627 (the bin is computed always; select uses it only with checkOrientation)
-                float rot = k1.angle - A.kp2[bestIdx2].angle;
-                if (rot < 0.0) rot += 360.0f;
-                bin = (int)roundf(rot * (1.0f / ORBFE_HISTO_LENGTH));
-                if (bin == ORBFE_HISTO_LENGTH) bin = 0;
-            }
+            // :619-627 (the bin is computed always; select uses it only with checkOrientation)
+            if (bestIdx2 >= 0) bin = rotation_bin(k1.angle, A.kp2[bestIdx2].angle);
         }
     }
     rawMatch[(size_t)k * n1 + idx1] = bestIdx2;

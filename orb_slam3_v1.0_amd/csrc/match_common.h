@@ -1,4 +1,5 @@
-// match_common.h -- pieces shared by the two matcher translation units.
+// match_common.h -- pieces shared by the matcher translation units: descriptor distance, the rotation-consistency filter,
+// wave64 reductions, scratch arenas.
 #pragma once
 #include <string>
 
@@ -15,11 +16,97 @@ __device__ __forceinline__ int hamming256(const uint2* a, const unsigned long lo
     return __popcll(a4[0] ^ b4[0]) + __popcll(a4[1] ^ b4[1]) + __popcll(a4[2] ^ b4[2]) + __popcll(a4[3] ^ b4[3]);
 }
 
+// the same with the query's four words in registers
+__device__ __forceinline__ int hamming256(const unsigned long long* a4, unsigned long long b0, unsigned long long b1,
+                                          unsigned long long b2, unsigned long long b3)
+{
+    return __popcll(a4[0] ^ b0) + __popcll(a4[1] ^ b1) + __popcll(a4[2] ^ b2) + __popcll(a4[3] ^ b3);
+}
+
+// ---- rotation consistency (checkOrientation) of every ORBmatcher search ----
+// the histogram bin of a match (src/ORBmatcher.cc:248-253 and its copies in every search): with HISTO_LENGTH bins and the
+// factor 1 / HISTO_LENGTH the angles reach bins 0 .. 12 only; that is the reference's behaviour
+__host__ __device__ __forceinline__ int rotation_bin(float angle1, float angle2)
+{
+    float rot = angle1 - angle2;
+    if (rot < 0.0f) rot = rot + 360.0f;
+    int bin = (int)roundf(rot * (1.0f / ORBFE_HISTO_LENGTH));
+    if (bin == ORBFE_HISTO_LENGTH) bin = 0;
+    return bin;
+}
+
+// ORBmatcher::ComputeThreeMaxima (src/ORBmatcher.cc:1328-1370) over hist[ORBFE_HISTO_LENGTH]: strict ">" keeps the lowest
+// bins among equal counts; the 10 % tests compare in binary32
+__host__ __device__ __forceinline__ void three_maxima(const int* hist, int& ind1, int& ind2, int& ind3)
+{
+    int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
+    for (int i = 0; i < ORBFE_HISTO_LENGTH; i++) {
+        const int s = hist[i];
+        if (s > max1) { max3 = max2; max2 = max1; max1 = s; i3 = i2; i2 = i1; i1 = i; }
+        else if (s > max2) { max3 = max2; max2 = s; i3 = i2; i2 = i; }
+        else if (s > max3) { max3 = s; i3 = i; }
+    }
+    if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
+    else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
+    ind1 = i1; ind2 = i2; ind3 = i3;
+}
+
+// The filter a search ends with (SearchByBoW :304-322, SearchForTriangulation :633-661, the relocalisation
+// SearchByProjection :1287-1323), run by ONE block over entries 0 .. n-1: histogram of the matches' bins, three maxima,
+// every match of another bin dropped, the number of survivors published.  alive(j): entry j is a match; binOf(j): its
+// bin; drop(j): remove it.  Without checkOrientation only the count is taken.
+template <class Alive, class BinOf, class Drop>
+__device__ __forceinline__ void rotation_filter_block(int n, int checkOrientation, Alive alive, BinOf binOf, Drop drop,
+                                                      int* nMatchesOut)
+{
+    __shared__ int hist[ORBFE_HISTO_LENGTH];
+    __shared__ int sInd[3];
+    __shared__ int sCount;
+    const int tid = threadIdx.x;
+    if (tid < ORBFE_HISTO_LENGTH) hist[tid] = 0;
+    if (tid == 0) sCount = 0;
+    __syncthreads();
+    int local = 0;
+    for (int j = tid; j < n; j += blockDim.x)
+        if (alive(j)) {
+            local++;
+            if (checkOrientation) atomicAdd(&hist[binOf(j)], 1);
+        }
+    __syncthreads();
+    if (tid == 0) {
+        int ind1 = -1, ind2 = -1, ind3 = -1;
+        if (checkOrientation) three_maxima(hist, ind1, ind2, ind3);
+        sInd[0] = ind1; sInd[1] = ind2; sInd[2] = ind3;
+    }
+    __syncthreads();
+    if (checkOrientation) {
+        for (int j = tid; j < n; j += blockDim.x)
+            if (alive(j)) {
+                const int b = binOf(j);
+                if (b != sInd[0] && b != sInd[1] && b != sInd[2]) {
+                    drop(j);
+                    local--;
+                }
+            }
+    }
+    if (local) atomicAdd(&sCount, local);
+    __syncthreads();
+    if (tid == 0) *nMatchesOut = sCount;
+}
+
+// ---- wave64 helpers ----
 __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int m)
 {
     unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
     lo = __shfl_xor(lo, m);
     hi = __shfl_xor(hi, m);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v, int l)
+{
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
     return ((unsigned long long)hi << 32) | lo;
 }
 
@@ -42,6 +129,31 @@ __device__ __forceinline__ void wave_top2(unsigned long long& k1, unsigned long 
         const unsigned long long o1 = shfl_xor_u64(k1, d), o2 = shfl_xor_u64(k2, d);
         top2_merge(k1, k2, o1, o2);
     }
+}
+
+// wave64 minimum with DPP row operations (one VALU instruction per step instead of an LDS permute): quad swaps, row
+// half-mirror and mirror leave every lane of a 16-lane row with the row minimum; row_bcast 15 / 31 fold the rows into lane
+// 63, which is read back as a scalar.  Lanes a row mask leaves out receive the identity.  All 64 lanes must be active.
+__device__ __forceinline__ unsigned wave_min_u32(unsigned v)
+{
+    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
+    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
+    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x141, 0xF, 0xF, false));  // row_half_mirror
+    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x140, 0xF, 0xF, false));  // row_mirror
+    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x142, 0xA, 0xF, false));  // row_bcast:15 into rows 1 and 3
+    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x143, 0xC, 0xF, false));  // row_bcast:31 into rows 2 and 3
+    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
+}
+
+// wave-wide top-2 of 32-bit keys (all 64 lanes receive the result): the minimum, then the minimum with its owner's smallest
+// key replaced by that lane's second.  Precondition: every lane holds its own (smallest, second smallest) pair, and keys are
+// distinct across lanes except for the "none" value 0xffffffff.
+__device__ __forceinline__ void wave_top2_u32(unsigned& k1, unsigned& k2)
+{
+    const unsigned m1 = wave_min_u32(k1);
+    const unsigned m2 = wave_min_u32(k1 == m1 ? k2 : k1);
+    k1 = m1;
+    k2 = m2;
 }
 
 [[maybe_unused]] static __global__ void fill_kernel(int* p, int v, size_t n)

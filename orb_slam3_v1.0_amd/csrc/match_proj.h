@@ -105,6 +105,27 @@ __device__ __forceinline__ void window_cells(const GridDesc& g, MpWindow& w)
     if (w.minCX >= g.cols || w.maxCX < 0 || w.minCY >= g.rows || w.maxCY < 0) w.valid = false;
 }
 
+// The candidate walk of KeyFrame::GetFeaturesInArea (src/KeyFrame.cc:798-832) on a key frame's per-level cell tables, as the
+// thread-per-map-point searches use it: levels [lvl - 1, lvl] (src/ORBmatcher.cc:787, :1078), all rows of the window's columns,
+// then the cell-row and the distance test (:826).  visit(level, slot, rec) sees every surviving record in visit order.
+template <class Visit>
+__device__ __forceinline__ void window_walk(const ProjArgs& A, const MpWindow& w, int lvl, Visit visit)
+{
+    const int tabStride = A.g.cols + 1;
+    for (int l = max(lvl - 1, 0); l <= min(lvl, A.tabLevels - 1); l++) {
+        const int* csl = A.colStart + (size_t)l * tabStride;
+        const int s = csl[w.minCX], e = csl[w.maxCX + 1];
+        for (int sl = s; sl < e; sl++) {
+            const int4 rq = A.rec[sl];
+            const int cy = rq.y >> 8;
+            if (cy < w.minCY || cy > w.maxCY) continue;
+            const float kx = __int_as_float(rq.z), ky = __int_as_float(rq.w);
+            if (!(fabsf(kx - w.x) < w.r && fabsf(ky - w.y) < w.r)) continue;
+            visit(l, sl, rq);
+        }
+    }
+}
+
 // median of three (v_med3_u32)
 __device__ __forceinline__ uint32_t umed3(uint32_t a, uint32_t b, uint32_t c) { return max(min(a, b), min(max(a, b), c)); }
 

@@ -2517,16 +2517,9 @@ int orbfe_triangulation_select(int n1, const int* raw_match12, const uint8_t* ra
         }
         matches12_out[i] = m;
     }
-    if (check_orientation) {  // :633-661 with ComputeThreeMaxima :1328-1370
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-        for (int i = 0; i < ORBFE_HISTO_LENGTH; i++) {
-            const int s = hist[i];
-            if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-            else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-            else if (s > max3) { max3 = s; ind3 = i; }
-        }
-        if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < 0.1f * (float)max1) { ind3 = -1; }
+    if (check_orientation) {  // :633-661
+        int ind1, ind2, ind3;
+        three_maxima(hist, ind1, ind2, ind3);
         for (int i = 0; i < n1; i++)
             if (matches12_out[i] >= 0) {
                 const int b = raw_bin[i];
