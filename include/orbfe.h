@@ -867,6 +867,80 @@ int orbfe_two_view_reconstruct(orbfe_handle *h, const orbfe_two_view_params *p, 
                                float *R21, float *t21, float *p3d, uint8_t *triangulated, orbfe_two_view_info *info);
 
 /* -------------------------------------------------------------------------------------------
+ * MLPnP RANSAC pose: the line behind orbfe_track_reference_keyframe in Tracking::TrackReferenceKeyFrame
+ * ---------------------------------------------------------------------------------------- */
+/* the frame's camera (F->mpCamera) and the arguments of MLPnPsolver::SetRansacParameters (src/MLPnPsolver.cpp:224-259; the call
+ * site passes 0.95, 50, 300, 12, 0.5, 5.991: src/Tracking.cc:840) plus iterate's nIterations (20, :845); versioned by struct_size */
+typedef struct orbfe_mlpnp_params {
+    int struct_size;          /* sizeof(orbfe_mlpnp_params) at the caller's compile time */
+    int camera_model;         /* ORBFE_CAMERA_PINHOLE or ORBFE_CAMERA_KANNALA_BRANDT8 */
+    float cam[8];             /* fx fy cx cy k1 k2 k3 k4 (mvParameters; k1 .. k4 are not read for a pinhole) */
+    float kb_precision;       /* KannalaBrandt8::precision (1e-6), the Newton exit of unproject */
+    double probability;       /* (0, 1) */
+    int min_inliers;          /* >= 0 */
+    int max_iterations;       /* [1, 4096] */
+    int min_set;              /* [6, 64] */
+    float epsilon;            /* (0, 1] */
+    float th2;
+    int n_iterations;         /* nIterations of iterate(): [0, 4096] */
+} orbfe_mlpnp_params;
+#define ORBFE_MLPNP_PARAMS_INIT {(int)sizeof(orbfe_mlpnp_params), 0, {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, 1e-6f, 0.95, 50, 300, 12, 0.5f, 5.991f, 20}
+
+#define ORBFE_MLPNP_EXIT_ABORT          0  /* N < mRansacMinInliers (:106-111): no GPU work */
+#define ORBFE_MLPNP_EXIT_REFINED        1  /* a Refine ended with more than mRansacMinInliers inliers (:189-200); the refined pose is returned */
+#define ORBFE_MLPNP_EXIT_BEST_UNREFINED 2  /* no Refine succeeded, the last best hypothesis is returned as it is (:204-219) */
+#define ORBFE_MLPNP_EXIT_FAILED         3  /* no hypothesis reached mRansacMinInliers */
+
+/* every intermediate of one call (optional: info may be NULL).  struct_size as above; the pointer members are caller-owned
+ * buffers, each may be NULL.  N = the number of i with mp_index[i] >= 0; correspondence c is the c-th such i.  T =
+ * total_iterations.  A pose is R (9, row-major) then t (3) in binary64, as computePose leaves it in mRi / mti. */
+typedef struct orbfe_mlpnp_info {
+    int struct_size;          /* sizeof(orbfe_mlpnp_info) at the caller's compile time */
+    int N;
+    int min_inliers, max_its, total_iterations;   /* as orbfe_mlpnp_plan */
+    int exit_kind;            /* ORBFE_MLPNP_EXIT_* */
+    int returning_iteration;  /* the hypothesis whose (refined) pose is returned, -1 when none */
+    int n_candidates;         /* hypotheses that set a new strict best among those with >= min_inliers inliers, in iteration order */
+    double *hyp_Rt;           /* [T][12] */
+    int *hyp_inliers;         /* [T] mnInliersi */
+    uint8_t *hyp_planar;      /* [T] 1 = the planar branch of computePose (:388) */
+    int *hyp_gn_evals;        /* [T] passes of mlpnp_gn's loop (:723) */
+    int *hyp_gn_exit;         /* [T] 0 = it_cnt reached maxIt, 1 = the break of :743, 2 = the break of :747 */
+    int *candidates;          /* [T] capacity, n_candidates written: their iterations */
+    double *cand_Rt;          /* [T][12] capacity: the pose Refine's computePose leaves in `result` (:327) for each candidate */
+    int *cand_inliers;        /* [T] capacity: the inliers of cand_Rt (mnRefinedInliers, had :330 scored `result`) */
+    uint8_t *cand_planar;     /* [T] capacity */
+    uint8_t *cand_mask;       /* [T][N] capacity: the inlier flags of cand_Rt per candidate */
+} orbfe_mlpnp_info;
+
+/* host only, no handle: SetRansacParameters' adjusted values for N correspondences -- *min_inliers = mRansacMinInliers, *max_its =
+ * mRansacMaxIts -- and *total_iterations = the passes the loop of a fresh solver's first iterate(n_iterations) makes when no Refine
+ * succeeds: max(mRansacMaxIts, n_iterations), or 0 (and *max_its = 0) when N < mRansacMinInliers.  binary64 with the platform's
+ * log / pow / ceil.  The caller draws total_iterations min-sets. */
+int orbfe_mlpnp_plan(const orbfe_mlpnp_params *p, int N, int *min_inliers, int *max_its, int *total_iterations);
+
+/* replaces a fresh MLPnPsolver(F, vpMapPointMatches) + SetRansacParameters + one iterate(n_iterations, bNoMore, vbInliers, nInliers,
+ * Tcw) (src/MLPnPsolver.cpp:56-352; the call: src/Tracking.cc:838-845).  Numerics: SPEC DECISION S13.
+ * kp (n) = mvKeysUn of the frame (x, y and octave are read; the handle's mvLevelSigma2 gives sigma2); mp_index[i] = the row of
+ * `points` that holds the world position (x y z floats, n_points rows) of the non-bad map point matched to keypoint i, or -1.
+ * sets = n_sets x min_set indices into the CORRESPONDENCE list (:121-141): an input, because the reference draws them from a
+ * rand() stream that belongs to the process (include/orbfe_adaptor.hpp draws them as the reference does); n_sets must equal
+ * orbfe_mlpnp_plan's total_iterations for N.  *solved = the function's return value, Tcw (16, row-major; identity when not solved),
+ * inliers (n, by keypoint), *n_inliers, *no_more = bNoMore.  N < min_inliers: *solved = 0, *no_more = 1, ORBFE_OK, no GPU work,
+ * sets not read.  ORBFE_ERR_INVALID_ARG: a wrong struct_size (params or info), a parameter outside its range, n_sets != the plan's
+ * total, a set index outside [0, N) or repeated inside a set, an mp_index >= n_points, an octave outside the handle's levels,
+ * n > 65536.  HOST pointers.  One submission and one synchronisation per call.
+ * NOT the reference's function in one respect ("Refine returns what it computes"): the reference's Refine never
+ * copies its computePose result into mRi / mti (:323-335), so its CheckInliers re-scores the hypothesis and iterate returns the
+ * first hypothesis with more than mRansacMinInliers inliers, unrefined.  This call adopts the refinement: with
+ * ORBFE_MLPNP_EXIT_REFINED, Tcw / inliers / n_inliers are the refined pose's, and the returning iteration is the first strict-best
+ * hypothesis whose REFINED pose has more than mRansacMinInliers inliers.  They differ from the reference's even in exact arithmetic;
+ * the reference's own choice can be read from info (the first it with hyp_inliers[it] > min_inliers, pose hyp_Rt[it]). */
+int orbfe_mlpnp_ransac(orbfe_handle *h, const orbfe_mlpnp_params *p, int n, const orbfe_keypoint *kp, const int *mp_index,
+                       int n_points, const float *points, const int *sets, int n_sets, int *solved, float *Tcw,
+                       uint8_t *inliers, int *n_inliers, int *no_more, orbfe_mlpnp_info *info);
+
+/* -------------------------------------------------------------------------------------------
  * Multi-device pool: the batched many-frame mode with host frames, sharded over several GPUs
  * ---------------------------------------------------------------------------------------- */
 /* A pool owns N members.  Member k is a handle made from *params with device_id = devices[k] (params->device_id is ignored),

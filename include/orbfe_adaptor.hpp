@@ -1466,4 +1466,98 @@ private:
     orbfe_two_view_params p_;
 };
 
+// MLPnPsolver (include/MLPnPsolver.h, src/MLPnPsolver.cpp:56-352) as ONE call (orbfe_mlpnp_ransac): the line behind SearchByBoW in
+// Tracking::TrackReferenceKeyFrame (src/Tracking.cc:838-845).  The constructor takes what the reference's reads from the frame and
+// the matches: mvKeysUn, one world position per keypoint (nullptr = no map point, or a bad one) and the camera.  The min-sets are
+// drawn here exactly as :121-141 draws them (the RandomInt formula of Thirdparty/DBoW2/src/DUtils/Random.cpp:47-50 on the process's
+// rand() stream, swap with the back), so a process that replaces the reference's class by this one sees the same sets.  The call
+// is a fresh solver's first iterate(): a second iterate() on one object throws.  One stated departure: Refine's
+// pose is adopted before its CheckInliers, so a refined return carries the refined pose and its inliers; the reference scores and
+// returns the unrefined hypothesis there (:323-335 never write mRi / mti).
+class MLPnPsolver {
+public:
+    MLPnPsolver(ORBextractor& extractor, const std::vector<KeyPoint>& vKeysUn, const std::vector<const std::array<float, 3>*>& vpMapPointMatches,
+                int cameraModel, const std::array<float, 8>& cameraParameters, float kbPrecision = 1e-6f)
+        : ex_(extractor), keys_(vKeysUn)
+    {
+        if (vpMapPointMatches.size() != vKeysUn.size()) throw std::invalid_argument("MLPnPsolver: one map point slot per keypoint");
+        p_ = ORBFE_MLPNP_PARAMS_INIT;
+        p_.camera_model = cameraModel;
+        for (int i = 0; i < 8; i++) p_.cam[i] = cameraParameters[(size_t)i];
+        p_.kb_precision = kbPrecision;
+        mpIndex_.assign(vKeysUn.size(), -1);
+        for (size_t i = 0; i < vKeysUn.size(); i++)
+            if (vpMapPointMatches[i]) {
+                mpIndex_[i] = (int)(points_.size() / 3);
+                points_.insert(points_.end(), vpMapPointMatches[i]->begin(), vpMapPointMatches[i]->end());
+                N_++;
+            }
+        SetRansacParameters();  // (:96: the reference's defaults until the caller sets its own)
+    }
+    void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 6, float epsilon = 0.4f,
+                             float th2 = 5.991f)
+    {
+        p_.probability = probability; p_.min_inliers = minInliers; p_.max_iterations = maxIterations; p_.min_set = minSet;
+        p_.epsilon = epsilon; p_.th2 = th2;
+    }
+    // the min-sets of a first iterate(nIterations) (:121-141)
+    std::vector<int> DrawSets(int nIterations)
+    {
+        p_.n_iterations = nIterations;
+        int minInliers = 0, maxIts = 0, total = 0;
+        orbfe_detail::check(orbfe_mlpnp_plan(&p_, N_, &minInliers, &maxIts, &total), nullptr, "orbfe_mlpnp_plan");
+        std::vector<int> sets((size_t)total * p_.min_set, 0);
+        std::vector<int> all((size_t)N_), avail;
+        for (int i = 0; i < N_; i++) all[(size_t)i] = i;
+        for (int it = 0; it < total; it++) {
+            avail = all;
+            for (int j = 0; j < p_.min_set; j++) {
+                const int d = (int)avail.size();
+                const int randi = int(((double)rand() / ((double)RAND_MAX + 1.0)) * d);
+                sets[(size_t)it * p_.min_set + j] = avail[(size_t)randi];
+                avail[(size_t)randi] = avail.back();
+                avail.pop_back();
+            }
+        }
+        return sets;
+    }
+    // Tout row-major 4 x 4; vbInliers per keypoint.  info (optional) receives every intermediate; sets (optional) replaces the draw.
+    bool iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers, std::array<float, 16>& Tout,
+                 orbfe_mlpnp_info* info = nullptr, const std::vector<int>* sets = nullptr)
+    {
+        if (iterated_) throw std::logic_error("MLPnPsolver::iterate: the call is a fresh solver's first iterate(); make a new solver");
+        iterated_ = true;
+        std::vector<int> drawn;
+        if (!sets) drawn = DrawSets(nIterations);
+        p_.n_iterations = nIterations;
+        const std::vector<int>& use = sets ? *sets : drawn;
+        const int n = (int)keys_.size();
+        std::vector<uint8_t> inl((size_t)(n > 0 ? n : 1));
+        int solved = 0, noMore = 0;
+        nInliers = 0;
+        orbfe_handle* h = ex_.handle();
+        orbfe_detail::check(orbfe_mlpnp_ransac(h, &p_, n, reinterpret_cast<const orbfe_keypoint*>(keys_.data()), mpIndex_.data(), N_,
+                                               points_.data(), use.empty() ? nullptr : use.data(), (int)(use.size() / (size_t)p_.min_set),
+                                               &solved, Tout.data(), inl.data(), &nInliers, &noMore, info),
+                            h, "orbfe_mlpnp_ransac");
+        bNoMore = noMore != 0;
+        vbInliers.clear();  // (:103)
+        if (!solved) return false;
+        vbInliers.assign((size_t)n, false);
+        for (int i = 0; i < n; i++) vbInliers[(size_t)i] = inl[(size_t)i] != 0;
+        return true;
+    }
+    int correspondences() const { return N_; }
+    const orbfe_mlpnp_params& params() const { return p_; }
+
+private:
+    ORBextractor& ex_;
+    std::vector<KeyPoint> keys_;
+    std::vector<int> mpIndex_;
+    std::vector<float> points_;
+    orbfe_mlpnp_params p_;
+    int N_ = 0;
+    bool iterated_ = false;
+};
+
 }  // namespace ORB_SLAM3

@@ -1,5 +1,5 @@
-// jacobi.h -- the pinned Jacobi sequences of SPEC DECISIONS S10 / S12 and the 3 x 3 binary32 helpers of S12, shared by
-// kernels_match_tri.hip and kernels_twoview.hip (device) and the host step of orbfe_two_view_reconstruct.
+// jacobi.h -- the pinned Jacobi sequences of SPEC DECISIONS S10 / S12 / S13 and the 3 x 3 binary32 helpers of S12, shared by
+// kernels_match_tri.hip, kernels_twoview.hip and kernels_mlpnp.hip (device) and the host step of orbfe_two_view_reconstruct.
 // Every translation unit that includes this is built with -ffp-contract=off: c * a - s * b is two products and one add.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -174,6 +174,86 @@ __host__ __device__ inline void rank2_f(const float (&F)[9], float (&Fn)[9])
 #pragma unroll
         for (int j = 0; j < 3; j++) Fn[3 * i + j] = (float)((double)F[3 * i + j] - w * v[j]);
     }
+}
+
+// ---- SPEC DECISION S13: the 12 x 12 sequence, and S12's 9 x 9 sequence, run by a team of threads ----
+constexpr int kMlpnpSweeps = 12;  // S13: fixed, no data-dependent exit
+
+// the pairs of round r.  n = 12 (11 rounds of 6): {r, 11} and {(r + k) mod 11, (r - k) mod 11}, k = 1 .. 5 (the circle method);
+// n = 9 (9 rounds of 4, S12): the pairs {i, j}, i < j, i + j == r (mod 9), in ascending i
+__device__ inline void jacobi_round_pair(int n, int r, int slot, int& p, int& q)
+{
+    if (n == 12) {
+        if (slot == 0) { p = r; q = 11; return; }
+        const int a = (r + slot) % 11, b = (r - slot + 11) % 11;
+        p = a < b ? a : b;
+        q = a < b ? b : a;
+        return;
+    }
+    int cnt = 0;
+    p = 0; q = 0;
+    for (int i = 0; i < 9; i++) {
+        const int j = (r - i + 9) % 9;
+        if (i < j) {
+            if (cnt == slot) { p = i; q = j; }
+            cnt++;
+        }
+    }
+}
+
+// what a team shares while it diagonalises one matrix (LDS on the device)
+struct JacobiTeamWork {
+    double M[12][12], V[12][12];
+    double c[6], s[6];
+    int skip[6];
+    int P[11][6], Q[11][6];
+};
+
+// n = 12: kMlpnpSweeps sweeps of 11 rounds of 6 pairs; n = 9: kTwoViewSweeps sweeps of 9 rounds of 4 pairs.  Per round the angles
+// from M as it stands at the start of the round, then the column phase of all pairs, then the row phase of all pairs and V's
+// column phase.  M (symmetric, n x n in W.M) becomes (nearly) diagonal, W.V its eigenvectors.  Called by every thread of the block.
+__device__ inline void jacobi_rounds_block(JacobiTeamWork& W, int n)
+{
+    const int tid = threadIdx.x, nth = blockDim.x;
+    const int np = n == 12 ? 6 : 4, nr = n == 12 ? 11 : 9, sweeps = n == 12 ? kMlpnpSweeps : kTwoViewSweeps;
+    for (int e = tid; e < nr * np; e += nth) jacobi_round_pair(n, e / np, e % np, W.P[e / np][e % np], W.Q[e / np][e % np]);
+    for (int e = tid; e < n * n; e += nth) W.V[e / n][e % n] = e / n == e % n ? 1.0 : 0.0;
+    __syncthreads();
+    for (int sweep = 0; sweep < sweeps; sweep++)
+        for (int r = 0; r < nr; r++) {
+            for (int e = tid; e < np; e += nth) {
+                const int p = W.P[r][e], q = W.Q[r][e];
+                const double apq = W.M[p][q];
+                const int skip = apq == 0.0;
+                double c = 1.0, sn = 0.0;
+                if (!skip) jacobi_angle(W.M[p][p], W.M[q][q], apq, c, sn);
+                W.c[e] = c; W.s[e] = sn; W.skip[e] = skip;
+            }
+            __syncthreads();
+            for (int e = tid; e < np * n; e += nth) {  // columns p, q of M
+                const int pr = e / n, k = e % n;
+                if (W.skip[pr]) continue;
+                const int p = W.P[r][pr], q = W.Q[r][pr];
+                const double c = W.c[pr], sn = W.s[pr];
+                const double a = W.M[k][p], b = W.M[k][q];
+                W.M[k][p] = c * a - sn * b;
+                W.M[k][q] = sn * a + c * b;
+            }
+            __syncthreads();
+            for (int e = tid; e < np * n; e += nth) {  // rows p, q of M; columns p, q of V
+                const int pr = e / n, k = e % n;
+                if (W.skip[pr]) continue;
+                const int p = W.P[r][pr], q = W.Q[r][pr];
+                const double c = W.c[pr], sn = W.s[pr];
+                const double a = W.M[p][k], b = W.M[q][k];
+                W.M[p][k] = c * a - sn * b;
+                W.M[q][k] = sn * a + c * b;
+                const double va = W.V[k][p], vb = W.V[k][q];
+                W.V[k][p] = c * va - sn * vb;
+                W.V[k][q] = sn * va + c * vb;
+            }
+            __syncthreads();
+        }
 }
 
 }  // namespace orbfe

@@ -70,6 +70,11 @@ int match_triangulation_run(MatchScratch& m, hipStream_t s, int G, const int* of
 int two_view_run(MatchScratch& m, hipStream_t s, const orbfe_two_view_params* P, int n1, const orbfe_keypoint* kp1, int n2,
                  const orbfe_keypoint* kp2, const int* matches12, const int* sets, int* reconstructed, float* R21, float* t21,
                  float* p3d, uint8_t* triangulated, orbfe_two_view_info* info, std::string& err);
+// kernels_mlpnp.hip (MLPnPsolver: SetRansacParameters + one iterate, SPEC DECISION S13)
+int mlpnp_plan(const orbfe_mlpnp_params* P, int N, int* minInliers, int* maxIts, int* total);
+int mlpnp_run(MatchScratch& m, hipStream_t s, const orbfe_mlpnp_params* P, const float* levelSigma2, int nLevels, int n,
+              const orbfe_keypoint* kp, const int* mpIndex, int nPoints, const float* points, const int* sets, int nSets, int* solved,
+              float* Tcw, uint8_t* inliers, int* nInliers, int* noMore, orbfe_mlpnp_info* info, std::string& err);
 // kernels_distinct.hip (MapPoint::ComputeDistinctiveDescriptors for a batch)
 int distinctive_run(MatchScratch& m, hipStream_t s, int nSets, const int* setOff, const uint8_t* desc, int* bestIdx,
                     int* bestMedian, std::string& err);

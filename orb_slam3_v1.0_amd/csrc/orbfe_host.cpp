@@ -2502,6 +2502,30 @@ int orbfe_two_view_reconstruct(orbfe_handle* h, const orbfe_two_view_params* p, 
     return rc;
 }
 
+int orbfe_mlpnp_plan(const orbfe_mlpnp_params* p, int N, int* min_inliers, int* max_its, int* total_iterations)
+{
+    if (!p || !min_inliers || !max_its || !total_iterations) return ORBFE_ERR_INVALID_ARG;
+    return mlpnp_plan(p, N, min_inliers, max_its, total_iterations);
+}
+
+int orbfe_mlpnp_ransac(orbfe_handle* h, const orbfe_mlpnp_params* p, int n, const orbfe_keypoint* kp, const int* mp_index, int n_points,
+                       const float* points, const int* sets, int n_sets, int* solved, float* Tcw, uint8_t* inliers, int* n_inliers,
+                       int* no_more, orbfe_mlpnp_info* info)
+{
+    if (!h || !p || n < 0 || n_points < 0 || n_sets < 0 || !solved || !Tcw || !n_inliers || !no_more ||
+        (n > 0 && (!kp || !mp_index || !inliers)) || (n_points > 0 && !points))
+        return ORBFE_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIPCHK(h, hipSetDevice(h->device));
+    std::string err;
+    MatchScope scope_(h, h->stream);
+    if (scope_.rc != ORBFE_OK) return scope_.rc;
+    const int rc = mlpnp_run(h->match, h->stream, p, h->sig2, h->nLevels, n, kp, mp_index, n_points, points, sets, n_sets, solved, Tcw,
+                             inliers, n_inliers, no_more, info, err);
+    if (rc != ORBFE_OK) h->err = err;
+    return rc;
+}
+
 int orbfe_triangulation_select(int n1, const int* raw_match12, const uint8_t* raw_bin, const uint8_t* has_mp1_now,
                                int check_orientation, int* matches12_out, int* n_matches)
 {

@@ -152,6 +152,34 @@ class TwoViewInfo(C.Structure):
 TWO_VIEW_MODEL_NONE, TWO_VIEW_MODEL_HOMOGRAPHY, TWO_VIEW_MODEL_FUNDAMENTAL = 0, 1, 2
 
 
+class MlpnpParams(C.Structure):
+    """orbfe_mlpnp_params: the frame's camera, the arguments of MLPnPsolver::SetRansacParameters and iterate's nIterations."""
+    _fields_ = [("struct_size", C.c_int), ("camera_model", C.c_int), ("cam", C.c_float * 8), ("kb_precision", C.c_float),
+                ("probability", C.c_double), ("min_inliers", C.c_int), ("max_iterations", C.c_int), ("min_set", C.c_int),
+                ("epsilon", C.c_float), ("th2", C.c_float), ("n_iterations", C.c_int)]
+
+    def __init__(self, cam=(0.0,) * 8, camera_model=0, kb_precision=1e-6, probability=0.95, min_inliers=50, max_iterations=300,
+                 min_set=12, epsilon=0.5, th2=5.991, n_iterations=20):
+        super().__init__(C.sizeof(MlpnpParams), int(camera_model), (C.c_float * 8)(*[float(x) for x in cam]), kb_precision, probability,
+                         min_inliers, max_iterations, min_set, epsilon, th2, n_iterations)
+
+
+class MlpnpInfo(C.Structure):
+    """orbfe_mlpnp_info: every intermediate of one orbfe_mlpnp_ransac call."""
+    _fields_ = [("struct_size", C.c_int), ("N", C.c_int), ("min_inliers", C.c_int), ("max_its", C.c_int), ("total_iterations", C.c_int),
+                ("exit_kind", C.c_int), ("returning_iteration", C.c_int), ("n_candidates", C.c_int), ("hyp_Rt", C.c_void_p),
+                ("hyp_inliers", C.c_void_p), ("hyp_planar", C.c_void_p), ("hyp_gn_evals", C.c_void_p), ("hyp_gn_exit", C.c_void_p),
+                ("candidates", C.c_void_p), ("cand_Rt", C.c_void_p), ("cand_inliers", C.c_void_p), ("cand_planar", C.c_void_p),
+                ("cand_mask", C.c_void_p)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(MlpnpInfo)
+
+
+MLPNP_EXIT_ABORT, MLPNP_EXIT_REFINED, MLPNP_EXIT_BEST_UNREFINED, MLPNP_EXIT_FAILED = 0, 1, 2, 3
+
+
 class TrackParams(C.Structure):
     """orbfe_track_params: frame grid statics (src/Frame.cc:101-105) + the call parameters of SearchByProjection."""
     _fields_ = [("struct_size", C.c_int), ("grid_cols", C.c_int), ("grid_rows", C.c_int), ("min_x", C.c_float),
@@ -186,7 +214,7 @@ SYMBOLS = [
     "orbfe_stream_submit_track", "orbfe_stream_collect_track", "orbfe_track_frame_map", "orbfe_track_reference_keyframe", "orbfe_debug_graph_stats", "orbfe_set_graph_capture",
     "orbfe_debug_clock_probe", "orbfe_keyframe_set_grid", "orbfe_fuse_search_keyframe", "orbfe_fuse_search_keyframes", "orbfe_fuse_select",
     "orbfe_init_frame_create", "orbfe_init_frame_destroy", "orbfe_init_frame_size", "orbfe_track_initialization",
-    "orbfe_set_stream_priority", "orbfe_two_view_reconstruct",
+    "orbfe_set_stream_priority", "orbfe_two_view_reconstruct", "orbfe_mlpnp_plan", "orbfe_mlpnp_ransac",
     "orbfe_shard_range", "orbfe_pool_create", "orbfe_pool_destroy", "orbfe_pool_size", "orbfe_pool_member",
     "orbfe_pool_member_frames", "orbfe_pool_last_error", "orbfe_pool_extract", "orbfe_pool_enable_track",
     "orbfe_pool_map_update", "orbfe_pool_track",
@@ -308,6 +336,10 @@ def lib():
     if hasattr(L, "orbfe_two_view_reconstruct"):  # (as above: absent from an earlier build loaded for an A/B)
         L.orbfe_two_view_reconstruct.argtypes = [vp, C.POINTER(TwoViewParams), ci, vp, ci, vp, vp, vp, C.POINTER(ci), vp, vp, vp, vp,
                                                  C.POINTER(TwoViewInfo)]
+    if hasattr(L, "orbfe_mlpnp_ransac"):  # (as above)
+        L.orbfe_mlpnp_plan.argtypes = [C.POINTER(MlpnpParams), ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
+        L.orbfe_mlpnp_ransac.argtypes = [vp, C.POINTER(MlpnpParams), ci, vp, vp, ci, vp, vp, ci, C.POINTER(ci), vp, vp, C.POINTER(ci),
+                                         C.POINTER(ci), C.POINTER(MlpnpInfo)]
     L.orbfe_distinctive_descriptors.argtypes = [vp, ci, vp, vp, vp, vp]
     L.orbfe_vocab_create.argtypes = [vp, ci, vp, vp, vp, vp, vp, ci, C.POINTER(vp)]
     L.orbfe_vocab_destroy.argtypes = [vp]
@@ -1135,6 +1167,54 @@ def two_view_reconstruct(extractor, params, kp1, kp2, matches12, sets, want_info
                    hyp_t=np.array(info.hyp_t, np.float32).reshape(8, 3), scores=buf["scores"], inliers_H=buf["inliers_H"][:N],
                    inliers_F=buf["inliers_F"][:N], rt_flags=buf["rt_flags"].reshape(-1)[:8 * N].reshape(8, N),
                    rt_x3d=buf["rt_x3d"].reshape(-1)[:24 * N].reshape(8, N, 3), rt_cos=buf["rt_cos"].reshape(-1)[:8 * N].reshape(8, N))
+    return out
+
+
+def mlpnp_plan(params, N):
+    """orbfe_mlpnp_plan (host-only): (mRansacMinInliers, mRansacMaxIts, passes of a first iterate(n_iterations)) for N correspondences"""
+    a, b, c = C.c_int(), C.c_int(), C.c_int()
+    rc = lib().orbfe_mlpnp_plan(C.byref(params), int(N), C.byref(a), C.byref(b), C.byref(c))
+    if rc != 0:
+        raise OrbfeError(rc, "orbfe_mlpnp_plan")
+    return a.value, b.value, c.value
+
+
+def mlpnp_ransac(extractor, params, kp, mp_index, points, sets, want_info=True):
+    """orbfe_mlpnp_ransac: a fresh MLPnPsolver + SetRansacParameters + one iterate (src/MLPnPsolver.cpp).  kp: KP_DTYPE array
+    (mvKeysUn), mp_index [n] (row of points or -1), points [m, 3] float32 world positions, sets [total_iterations, min_set] indices
+    into the correspondence list (None when the plan says 0) -> dict(solved, Tcw [4, 4], inliers [n], n_inliers, no_more) plus, with
+    want_info, every field of orbfe_mlpnp_info under its own name (the optional buffers included, cut to their used size)."""
+    kp = np.ascontiguousarray(kp, KP_DTYPE)
+    mi = np.ascontiguousarray(mp_index, np.int32)
+    assert len(mi) == len(kp)
+    pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    st = None if sets is None else np.ascontiguousarray(sets, np.int32)
+    n_sets = 0 if st is None else (len(st) if st.ndim == 2 else st.size // max(int(params.min_set), 1))
+    n = len(kp)
+    N = int((mi >= 0).sum())
+    Tcw, inl = np.zeros((4, 4), np.float32), np.zeros(max(n, 1), np.uint8)
+    solved, n_inl, no_more = C.c_int(0), C.c_int(0), C.c_int(0)
+    info = None
+    if want_info:
+        info = MlpnpInfo()
+        T = max(n_sets, 1)
+        buf = dict(hyp_Rt=np.zeros((T, 12), np.float64), hyp_inliers=np.zeros(T, np.int32), hyp_planar=np.zeros(T, np.uint8),
+                   hyp_gn_evals=np.zeros(T, np.int32), hyp_gn_exit=np.zeros(T, np.int32), candidates=np.zeros(T, np.int32),
+                   cand_Rt=np.zeros((T, 12), np.float64), cand_inliers=np.zeros(T, np.int32), cand_planar=np.zeros(T, np.uint8),
+                   cand_mask=np.zeros(T * max(N, 1), np.uint8))
+        for k, v in buf.items():
+            setattr(info, k, v.ctypes.data)
+    extractor._chk(extractor.L.orbfe_mlpnp_ransac(extractor.h, C.byref(params), n, _p(kp), _p(mi), len(pts), _p(pts), _p(st), n_sets,
+                                                  C.byref(solved), _p(Tcw), _p(inl), C.byref(n_inl), C.byref(no_more),
+                                                  C.byref(info) if want_info else None), "orbfe_mlpnp_ransac")
+    out = dict(solved=bool(solved.value), Tcw=Tcw, inliers=inl[:n], n_inliers=n_inl.value, no_more=bool(no_more.value))
+    if want_info:
+        T, nc = info.total_iterations, info.n_candidates
+        out.update(N=info.N, min_inliers=info.min_inliers, max_its=info.max_its, total_iterations=T, exit_kind=info.exit_kind,
+                   returning_iteration=info.returning_iteration, n_candidates=nc, hyp_Rt=buf["hyp_Rt"][:T], hyp_inliers=buf["hyp_inliers"][:T],
+                   hyp_planar=buf["hyp_planar"][:T], hyp_gn_evals=buf["hyp_gn_evals"][:T], hyp_gn_exit=buf["hyp_gn_exit"][:T],
+                   candidates=buf["candidates"][:nc], cand_Rt=buf["cand_Rt"][:nc], cand_inliers=buf["cand_inliers"][:nc],
+                   cand_planar=buf["cand_planar"][:nc], cand_mask=buf["cand_mask"][:nc * info.N].reshape(nc, info.N))
     return out
 
 
