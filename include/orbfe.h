@@ -941,6 +941,83 @@ int orbfe_mlpnp_ransac(orbfe_handle *h, const orbfe_mlpnp_params *p, int n, cons
                        uint8_t *inliers, int *n_inliers, int *no_more, orbfe_mlpnp_info *info);
 
 /* -------------------------------------------------------------------------------------------
+ * Motion-only pose optimisation: the line behind orbfe_mlpnp_ransac (src/Tracking.cc:869) and behind orbfe_track_frame
+ * (src/Tracking.cc:935)
+ * ---------------------------------------------------------------------------------------- */
+/* the frame's camera and the constants of Optimizer::PoseOptimization (src/Optimizer.cc:765-1067); versioned by struct_size */
+typedef struct orbfe_pose_opt_params {
+    int struct_size;          /* sizeof(orbfe_pose_opt_params) at the caller's compile time */
+    int camera_model;         /* ORBFE_CAMERA_PINHOLE; ORBFE_CAMERA_KANNALA_BRANDT8 -> ORBFE_ERR_UNSUPPORTED */
+    float cam[8];             /* fx fy cx cy k1 k2 k3 k4 (mvParameters; only the first four are read) */
+    float chi2_threshold;     /* chi2Mono[it] (:953), 5.991 in every round */
+    double huber_delta2;      /* deltaMono = (float) sqrt(7.815) (:805): > 0 */
+    int iterations;           /* its[it] (:956), 25 in every round: [1, 64] */
+    int rounds;               /* 4 (:959): [1, 4]; the Huber kernel is dropped after round index 2 as written (:993) */
+    int stereo;               /* 0; anything else (mvuRight >= 0, a second camera, the ToBody edges) -> ORBFE_ERR_UNSUPPORTED */
+} orbfe_pose_opt_params;
+#define ORBFE_POSE_OPT_PARAMS_INIT {(int)sizeof(orbfe_pose_opt_params), 0, {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, 5.991f, 7.815, 25, 4, 0}
+
+#define ORBFE_POSE_OPT_EXIT_RAN_ALL  0  /* the round ran all its iterations */
+#define ORBFE_POSE_OPT_EXIT_TRIALS   1  /* Terminate: 10 trials in one iteration */
+#define ORBFE_POSE_OPT_EXIT_RHO_ZERO 2  /* Terminate: rho == 0 */
+
+/* every intermediate of one orbfe_pose_optimization call (optional: info may be NULL).  Edge c is the c-th keypoint i with
+ * mp_index[i] >= 0; a pose is R (9, row-major) then t (3) in binary64.  Entries of rounds that did not run are zero. */
+typedef struct orbfe_pose_opt_info {
+    int struct_size;          /* sizeof(orbfe_pose_opt_info) at the caller's compile time */
+    int N_e;
+    int rounds_run;
+    int iterations[4];        /* Levenberg iterations started in the round */
+    int trials[4];            /* damped solves tried in the round */
+    int n_bad[4];             /* nBad after the round */
+    int exit_kind[4];         /* ORBFE_POSE_OPT_EXIT_* */
+    double pose[4][12];       /* the round's final pose */
+    double lambda[4];         /* the damping the round ended with */
+    double chi2[4];           /* the round's last accepted sum of rho0 (activeRobustChi2) */
+    uint8_t *outlier;         /* [4][N_e], caller-owned, may be NULL: the flags after each round, by edge */
+} orbfe_pose_opt_info;
+
+/* replaces Optimizer::PoseOptimization(pFrame) (src/Optimizer.cc:765-1067; the calls: src/Tracking.cc:869 and :935) for the branch
+ * this fork takes: one camera, mvuRight < 0, EdgeSE3ProjectXYZOnlyPose, pinhole.  Numerics: SPEC DECISION S14;
+ * tests/poseopt_ref.py is the normative restatement and the call equals it byte for byte.
+ * kp (n) = mvKeysUn (x, y, octave are read; the handle's mvInvLevelSigma2 is the information); mp_index[i] = the row of `points`
+ * (x y z floats, n_points rows) of the map point matched to keypoint i, or -1.  Rcw (9, row-major) / tcw (3) = pFrame->GetPose().
+ * Tcw_out (16, row-major) = the pose the reference hands to SetPose; outlier_out (n) = mvbOutlier; *n_inliers = the return value
+ * (nInitialCorrespondences - nBad).  Fewer than 3 matched keypoints: *n_inliers = 0, Tcw_out = the input pose, no flags, ORBFE_OK
+ * (:949); that return and every refusal below are decided from the arguments and the handle's level count before the device is touched.  Fewer than 10: one round (:1055).
+ * The whole call -- four rounds, every iteration and every trial -- is ONE kernel launch of one block; one submission, one
+ * synchronisation.  HOST pointers.
+ * ORBFE_ERR_INVALID_ARG: a wrong struct_size (params or info), a parameter outside its range, an mp_index >= n_points, an octave
+ * of a matched keypoint outside the handle's levels, n > 65536.  ORBFE_ERR_UNSUPPORTED: KannalaBrandt8 (its project() mixes
+ * atan2f / sqrtf with binary64 while projectJac uses atan2: a binary64 atan2 sequence has to be pinned first), stereo != 0,
+ * and the inertial variants are not offered at all (their edges belong to G2oTypes.cc).
+ * NOT the reference's function in three stated respects:
+ *   - g2o is an empty submodule in the reference tree: the Levenberg loop (OptimizationAlgorithmLevenberg + LinearSolverDense)
+ *     and SE3Quat::exp are restated from the published algorithm and adopted as this project's definition; parity with a g2o
+ *     build is unpinned, as S10-S13 are against Eigen;
+ *   - the pose is kept as a rotation matrix where g2o keeps a quaternion, and the initial pose takes no quaternion round trip
+ *     (:784); the matrix drifts from orthonormal by rounding only (measured: tests/test_poseopt.py);
+ *   - the inlier flags are scored on fresh errors at the round's final pose; g2o leaves the errors of a rejected last trial in
+ *     the active edges when a round ends on Terminate, and the reference reads those. */
+int orbfe_pose_optimization(orbfe_handle *h, const orbfe_pose_opt_params *p, int n, const orbfe_keypoint *kp, const int *mp_index,
+                            int n_points, const float *points, const float *Rcw, const float *tcw, float *Tcw_out,
+                            uint8_t *outlier_out, int *n_inliers, orbfe_pose_opt_info *info);
+
+/* Batched, HBM-resident form (no reference analogue: the batched mode's pose step): grid = batch, one block per frame.  Frame b's
+ * keypoints d_kp[b * kp_stride ..] and count d_n[b] are orbfe_extract_batch_device's outputs (kp_stride <= 65536), d_match[b *
+ * kp_stride ..] is orbfe_match_projection_batch_device's d_match_out (an index into frame b's points, or -1), frame b's points
+ * are d_points[b * point_stride_frames ..] (n_map_points records; point_stride_frames == 0: one set shared by all frames; only
+ * x y z are read).  d_pose_in / d_pose_out: 12 floats per frame, Rcw then tcw.  d_outlier: kp_stride bytes per frame, d_n[b] are
+ * written.  d_n_inliers: one int per frame.  A match outside [0, n_map_points) or on a keypoint whose octave is outside the handle's
+ * levels is no edge (the host call refuses such input; a device call cannot).  DEVICE pointers; asynchronous on `stream` (NULL ==
+ * the handle's stream): one launch, no host synchronisation.  Frame b's results are byte-equal to orbfe_pose_optimization on the
+ * same data. */
+int orbfe_pose_optimization_batch_device(orbfe_handle *h, const orbfe_pose_opt_params *p, int batch, const orbfe_keypoint *d_kp,
+                                         const int *d_n, int kp_stride, const int *d_match, int n_map_points,
+                                         const orbfe_world_point *d_points, int point_stride_frames, const float *d_pose_in,
+                                         float *d_pose_out, uint8_t *d_outlier, int *d_n_inliers, void *stream);
+
+/* -------------------------------------------------------------------------------------------
  * Multi-device pool: the batched many-frame mode with host frames, sharded over several GPUs
  * ---------------------------------------------------------------------------------------- */
 /* A pool owns N members.  Member k is a handle made from *params with device_id = devices[k] (params->device_id is ignored),

@@ -1560,4 +1560,57 @@ private:
     bool iterated_ = false;
 };
 
+// Optimizer::PoseOptimization(pFrame) (src/Optimizer.cc:765-1067) as ONE call (orbfe_pose_optimization): the line behind the MLPnP
+// solve in Tracking::TrackReferenceKeyFrame (src/Tracking.cc:869) and behind SearchLocalPoints in TrackLocalMap (:935).  It is NOT
+// named Optimizer: unlike the classes above it replaces one function, not a class -- Tracking.cc keeps including Optimizer.h for
+// GlobalBundleAdjustemnt (:698) and the PoseInertialOptimization* calls (:946, :952), so ORB_SLAM3::Optimizer stays the reference's.
+// `F` needs mNumKeypoints, mvKeysUn (shared_ptr<vector<KeyPoint>>), mvpMapPoints (entries with GetWorldPos()[0..2]), mvbOutlier,
+// mvuRight and mpCamera2; getPose(F, Rcw[9], tcw[3]) reads pFrame->GetPose() row-major, setPose(F, Tcw[16]) is pFrame->SetPose
+// (:1062-1065).  It fills mp_index / points from mvpMapPoints, writes mvbOutlier, sets the pose and returns
+// nInitialCorrespondences - nBad.
+// A frame with a second camera or a matched keypoint with mvuRight >= 0 throws (ORBFE_ERR_UNSUPPORTED: this fork is mono).
+// Three stated departures (include/orbfe.h): the Levenberg loop and SE3Quat::exp are restated from g2o's published
+// algorithm (g2o is not in the reference tree; parity with a g2o build is unpinned); the pose is kept as a rotation matrix, not a
+// quaternion; the flags of a round are scored on fresh errors at its final pose, where g2o leaves the errors of a rejected last
+// trial in the active edges.
+struct PoseOptimizer {
+    template <class FramePtr, class GetPose, class SetPose>
+    static int PoseOptimization(ORBextractor& extractor, FramePtr pFrame, int cameraModel, const std::array<float, 8>& cameraParameters,
+                                GetPose getPose, SetPose setPose, orbfe_pose_opt_info* info = nullptr)
+    {
+        orbfe_pose_opt_params p = ORBFE_POSE_OPT_PARAMS_INIT;
+        p.camera_model = cameraModel;
+        for (int i = 0; i < 8; i++) p.cam[i] = cameraParameters[(size_t)i];
+        if (pFrame->mpCamera2) p.stereo = 1;
+        const int n = pFrame->mNumKeypoints;
+        std::vector<int> mpIndex((size_t)(n > 0 ? n : 1), -1);
+        std::vector<float> points;
+        for (int i = 0; i < n; i++) {
+            auto pMP = pFrame->mvpMapPoints[(size_t)i];
+            if (!pMP) continue;
+            if (pFrame->mvuRight[(size_t)i] >= 0) p.stereo = 1;
+            const auto P = pMP->GetWorldPos();
+            mpIndex[(size_t)i] = (int)(points.size() / 3);
+            points.push_back(P[0]);
+            points.push_back(P[1]);
+            points.push_back(P[2]);
+        }
+        float Rcw[9], tcw[3];
+        getPose(pFrame, Rcw, tcw);
+        std::array<float, 16> Tcw;
+        std::vector<uint8_t> outlier((size_t)(n > 0 ? n : 1));
+        int nInliers = 0;
+        orbfe_handle* h = extractor.handle();
+        orbfe_detail::check(orbfe_pose_optimization(h, &p, n, reinterpret_cast<const orbfe_keypoint*>(pFrame->mvKeysUn->data()), mpIndex.data(),
+                                                    (int)(points.size() / 3), points.empty() ? nullptr : points.data(), Rcw, tcw, Tcw.data(),
+                                                    outlier.data(), &nInliers, info),
+                            h, "orbfe_pose_optimization");
+        for (int i = 0; i < n; i++)
+            if (mpIndex[(size_t)i] >= 0) pFrame->mvbOutlier[(size_t)i] = outlier[(size_t)i] != 0;  // (:822: false when nothing ran)
+        if ((int)(points.size() / 3) < 3) return 0;  // (:949-950: the pose is not touched)
+        setPose(pFrame, Tcw.data());
+        return nInliers;
+    }
+};
+
 }  // namespace ORB_SLAM3

@@ -20,6 +20,7 @@
 #include "match_common.h"
 #include "camera.h"
 #include "jacobi.h"
+#include "ldlt.h"
 
 #pragma clang fp contract(off)
 
@@ -230,52 +231,6 @@ __device__ inline void point_rows(const double* R, const double (*D)[9], const d
         for (int i = 0; i < 3; i++) J[3 + i] = g[i];
         (h ? r1 : r0) = d;
     }
-}
-
-// A x = b for symmetric 6 x 6 A (destroyed) by L D L^T with diagonal pivoting (S13)
-__device__ inline void ldlt_solve6(double (&A)[6][6], const double (&b)[6], double (&x)[6])
-{
-    double L[6][6], d[6];
-    int perm[6];
-    for (int i = 0; i < 6; i++) {
-        perm[i] = i;
-        for (int j = 0; j < 6; j++) L[i][j] = 0.0;
-    }
-    for (int k = 0; k < 6; k++) {
-        int best = k;
-        for (int i = k + 1; i < 6; i++)
-            if (fabs(A[i][i]) > fabs(A[best][best])) best = i;
-        for (int j = 0; j < 6; j++) { const double t = A[k][j]; A[k][j] = A[best][j]; A[best][j] = t; }
-        for (int i = 0; i < 6; i++) { const double t = A[i][k]; A[i][k] = A[i][best]; A[i][best] = t; }
-        for (int j = 0; j < 6; j++) { const double t = L[k][j]; L[k][j] = L[best][j]; L[best][j] = t; }
-        { const int t = perm[k]; perm[k] = perm[best]; perm[best] = t; }
-        const double dk = A[k][k];
-        d[k] = dk;
-        double col[6];
-        for (int i = 0; i < 6; i++) col[i] = A[i][k];
-        for (int i = k + 1; i < 6; i++) {
-            const double li = dk == 0.0 ? 0.0 : col[i] / dk;
-            L[i][k] = li;
-            for (int j = k + 1; j <= i; j++) {
-                const double val = A[i][j] - li * col[j];
-                A[i][j] = val;
-                A[j][i] = val;
-            }
-        }
-    }
-    double z[6], w[6], xs[6];
-    for (int i = 0; i < 6; i++) {
-        double acc = b[perm[i]];
-        for (int j = 0; j < i; j++) acc = acc - L[i][j] * z[j];
-        z[i] = acc;
-    }
-    for (int i = 0; i < 6; i++) w[i] = d[i] == 0.0 ? 0.0 : z[i] / d[i];
-    for (int i = 5; i >= 0; i--) {
-        double acc = w[i];
-        for (int j = i + 1; j < 6; j++) acc = acc - L[j][i] * xs[j];
-        xs[i] = acc;
-    }
-    for (int i = 0; i < 6; i++) x[perm[i]] = xs[i];
 }
 
 // bit image of a non-negative, non-NaN double: ordered like the value

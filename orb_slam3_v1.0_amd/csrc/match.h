@@ -1,6 +1,7 @@
 // match.h -- host entry points of the Hamming matchers (kernels_match.hip).
 #pragma once
 #include <string>
+#include <vector>
 
 #include "orbfe_internal.h"
 
@@ -75,6 +76,18 @@ int mlpnp_plan(const orbfe_mlpnp_params* P, int N, int* minInliers, int* maxIts,
 int mlpnp_run(MatchScratch& m, hipStream_t s, const orbfe_mlpnp_params* P, const float* levelSigma2, int nLevels, int n,
               const orbfe_keypoint* kp, const int* mpIndex, int nPoints, const float* points, const int* sets, int nSets, int* solved,
               float* Tcw, uint8_t* inliers, int* nInliers, int* noMore, orbfe_mlpnp_info* info, std::string& err);
+// kernels_poseopt.hip (Optimizer::PoseOptimization, SPEC DECISION S14)
+int pose_opt_check(const orbfe_pose_opt_params* P, const orbfe_pose_opt_info* info, std::string& err);
+int pose_opt_begin(const orbfe_pose_opt_params* P, int nLevels, int n, const orbfe_keypoint* kp, const int* mpIndex, int nPoints,
+                   const float* Rcw, const float* tcw, float* TcwOut, uint8_t* outlier, int* nInliers, orbfe_pose_opt_info* info,
+                   std::vector<int>& first, std::string& err);
+int pose_opt_run(MatchScratch& m, hipStream_t s, const orbfe_pose_opt_params* P, const float* invLevelSigma2, int nLevels, int n,
+                 const orbfe_keypoint* kp, const int* mpIndex, const float* points, const float* Rcw, const float* tcw,
+                 const std::vector<int>& first, float* TcwOut, uint8_t* outlier, int* nInliers, orbfe_pose_opt_info* info, std::string& err);
+int pose_opt_batch_device(MatchScratch& m, hipStream_t s, const orbfe_pose_opt_params* P, const float* invLevelSigma2, int nLevels,
+                          int batch, const orbfe_keypoint* dKp, const int* dN, int kpStride, const int* dMatch, int nMapPoints,
+                          const orbfe_world_point* dPoints, int pointStrideFrames, const float* dPoseIn, float* dPoseOut,
+                          uint8_t* dOutlier, int* dNInliers, std::string& err);
 // kernels_distinct.hip (MapPoint::ComputeDistinctiveDescriptors for a batch)
 int distinctive_run(MatchScratch& m, hipStream_t s, int nSets, const int* setOff, const uint8_t* desc, int* bestIdx,
                     int* bestMedian, std::string& err);

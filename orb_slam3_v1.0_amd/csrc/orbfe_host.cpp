@@ -2526,6 +2526,64 @@ int orbfe_mlpnp_ransac(orbfe_handle* h, const orbfe_mlpnp_params* p, int n, cons
     return rc;
 }
 
+int orbfe_pose_optimization(orbfe_handle* h, const orbfe_pose_opt_params* p, int n, const orbfe_keypoint* kp, const int* mp_index,
+                            int n_points, const float* points, const float* Rcw, const float* tcw, float* Tcw_out, uint8_t* outlier_out,
+                            int* n_inliers, orbfe_pose_opt_info* info)
+{
+    if (!p) return ORBFE_ERR_INVALID_ARG;
+    std::string err;
+    int rc = pose_opt_check(p, info, err);  // struct sizes, unsupported branches and ranges need no handle
+    if (rc == ORBFE_OK && (!h || n < 0 || n_points < 0 || !Rcw || !tcw || !Tcw_out || !n_inliers ||
+                           (n > 0 && (!kp || !mp_index || !outlier_out)) || (n_points > 0 && !points)))
+        return ORBFE_ERR_INVALID_ARG;
+    if (!h) return rc;
+    std::lock_guard<std::mutex> lk(h->mu);
+    std::vector<int> first;
+    // the other refusals and the return for fewer than 3 matches (:949) read the handle's level count only: the device is not touched
+    if (rc == ORBFE_OK) rc = pose_opt_begin(p, h->nLevels, n, kp, mp_index, n_points, Rcw, tcw, Tcw_out, outlier_out, n_inliers, info, first, err);
+    if (rc != ORBFE_OK) {
+        h->err = err;
+        return rc;
+    }
+    if (first.size() < 3) return ORBFE_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    MatchScope scope_(h, h->stream);
+    if (scope_.rc != ORBFE_OK) return scope_.rc;
+    rc = pose_opt_run(h->match, h->stream, p, h->invSig2, h->nLevels, n, kp, mp_index, points, Rcw, tcw, first, Tcw_out, outlier_out, n_inliers,
+                      info, err);
+    if (rc != ORBFE_OK) h->err = err;
+    return rc;
+}
+
+int orbfe_pose_optimization_batch_device(orbfe_handle* h, const orbfe_pose_opt_params* p, int batch, const orbfe_keypoint* d_kp,
+                                         const int* d_n, int kp_stride, const int* d_match, int n_map_points,
+                                         const orbfe_world_point* d_points, int point_stride_frames, const float* d_pose_in,
+                                         float* d_pose_out, uint8_t* d_outlier, int* d_n_inliers, void* stream_)
+{
+    if (!p) return ORBFE_ERR_INVALID_ARG;
+    std::string err;
+    const int crc = pose_opt_check(p, nullptr, err);
+    if (crc != ORBFE_OK) {
+        if (h) {
+            std::lock_guard<std::mutex> lk(h->mu);
+            h->err = err;
+        }
+        return crc;
+    }
+    if (!h || batch < 1 || !d_kp || !d_n || kp_stride < 1 || !d_match || n_map_points < 0 || (n_map_points > 0 && !d_points) ||
+        point_stride_frames < 0 || !d_pose_in || !d_pose_out || !d_outlier || !d_n_inliers)
+        return ORBFE_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = stream_ ? (hipStream_t)stream_ : h->stream;
+    MatchScope scope_(h, s);
+    if (scope_.rc != ORBFE_OK) return scope_.rc;
+    const int rc = pose_opt_batch_device(h->match, s, p, h->invSig2, h->nLevels, batch, d_kp, d_n, kp_stride, d_match, n_map_points,
+                                         d_points, point_stride_frames, d_pose_in, d_pose_out, d_outlier, d_n_inliers, err);
+    if (rc != ORBFE_OK) h->err = err;
+    return rc;
+}
+
 int orbfe_triangulation_select(int n1, const int* raw_match12, const uint8_t* raw_bin, const uint8_t* has_mp1_now,
                                int check_orientation, int* matches12_out, int* n_matches)
 {

@@ -180,6 +180,30 @@ class MlpnpInfo(C.Structure):
 MLPNP_EXIT_ABORT, MLPNP_EXIT_REFINED, MLPNP_EXIT_BEST_UNREFINED, MLPNP_EXIT_FAILED = 0, 1, 2, 3
 
 
+class PoseOptParams(C.Structure):
+    """orbfe_pose_opt_params: the frame's camera and the constants of Optimizer::PoseOptimization (src/Optimizer.cc:765-1067)."""
+    _fields_ = [("struct_size", C.c_int), ("camera_model", C.c_int), ("cam", C.c_float * 8), ("chi2_threshold", C.c_float),
+                ("huber_delta2", C.c_double), ("iterations", C.c_int), ("rounds", C.c_int), ("stereo", C.c_int)]
+
+    def __init__(self, cam=(0.0,) * 8, camera_model=0, chi2_threshold=5.991, huber_delta2=7.815, iterations=25, rounds=4, stereo=0):
+        super().__init__(C.sizeof(PoseOptParams), int(camera_model), (C.c_float * 8)(*[float(x) for x in cam]), chi2_threshold,
+                         huber_delta2, iterations, rounds, stereo)
+
+
+class PoseOptInfo(C.Structure):
+    """orbfe_pose_opt_info: every intermediate of one orbfe_pose_optimization call."""
+    _fields_ = [("struct_size", C.c_int), ("N_e", C.c_int), ("rounds_run", C.c_int), ("iterations", C.c_int * 4), ("trials", C.c_int * 4),
+                ("n_bad", C.c_int * 4), ("exit_kind", C.c_int * 4), ("pose", (C.c_double * 12) * 4), ("lambda_", C.c_double * 4),
+                ("chi2", C.c_double * 4), ("outlier", C.c_void_p)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(PoseOptInfo)
+
+
+POSE_OPT_EXIT_RAN_ALL, POSE_OPT_EXIT_TRIALS, POSE_OPT_EXIT_RHO_ZERO = 0, 1, 2
+
+
 class TrackParams(C.Structure):
     """orbfe_track_params: frame grid statics (src/Frame.cc:101-105) + the call parameters of SearchByProjection."""
     _fields_ = [("struct_size", C.c_int), ("grid_cols", C.c_int), ("grid_rows", C.c_int), ("min_x", C.c_float),
@@ -215,6 +239,7 @@ SYMBOLS = [
     "orbfe_debug_clock_probe", "orbfe_keyframe_set_grid", "orbfe_fuse_search_keyframe", "orbfe_fuse_search_keyframes", "orbfe_fuse_select",
     "orbfe_init_frame_create", "orbfe_init_frame_destroy", "orbfe_init_frame_size", "orbfe_track_initialization",
     "orbfe_set_stream_priority", "orbfe_two_view_reconstruct", "orbfe_mlpnp_plan", "orbfe_mlpnp_ransac",
+    "orbfe_pose_optimization", "orbfe_pose_optimization_batch_device",
     "orbfe_shard_range", "orbfe_pool_create", "orbfe_pool_destroy", "orbfe_pool_size", "orbfe_pool_member",
     "orbfe_pool_member_frames", "orbfe_pool_last_error", "orbfe_pool_extract", "orbfe_pool_enable_track",
     "orbfe_pool_map_update", "orbfe_pool_track",
@@ -340,6 +365,10 @@ def lib():
         L.orbfe_mlpnp_plan.argtypes = [C.POINTER(MlpnpParams), ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
         L.orbfe_mlpnp_ransac.argtypes = [vp, C.POINTER(MlpnpParams), ci, vp, vp, ci, vp, vp, ci, C.POINTER(ci), vp, vp, C.POINTER(ci),
                                          C.POINTER(ci), C.POINTER(MlpnpInfo)]
+    if hasattr(L, "orbfe_pose_optimization"):  # (as above)
+        L.orbfe_pose_optimization.argtypes = [vp, C.POINTER(PoseOptParams), ci, vp, vp, ci, vp, vp, vp, vp, vp, C.POINTER(ci),
+                                              C.POINTER(PoseOptInfo)]
+        L.orbfe_pose_optimization_batch_device.argtypes = [vp, C.POINTER(PoseOptParams), ci, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp]
     L.orbfe_distinctive_descriptors.argtypes = [vp, ci, vp, vp, vp, vp]
     L.orbfe_vocab_create.argtypes = [vp, ci, vp, vp, vp, vp, vp, ci, C.POINTER(vp)]
     L.orbfe_vocab_destroy.argtypes = [vp]
@@ -1216,6 +1245,54 @@ def mlpnp_ransac(extractor, params, kp, mp_index, points, sets, want_info=True):
                    candidates=buf["candidates"][:nc], cand_Rt=buf["cand_Rt"][:nc], cand_inliers=buf["cand_inliers"][:nc],
                    cand_planar=buf["cand_planar"][:nc], cand_mask=buf["cand_mask"][:nc * info.N].reshape(nc, info.N))
     return out
+
+
+def pose_optimization(extractor, params, kp, mp_index, points, Rcw, tcw, want_info=True):
+    """orbfe_pose_optimization: Optimizer::PoseOptimization (src/Optimizer.cc:765-1067), mono pinhole, SPEC DECISION S14.  kp: KP_DTYPE
+    array (mvKeysUn), mp_index [n] (row of points or -1), points [m, 3] float32 world positions, Rcw [9] / tcw [3] float32 = the frame's
+    pose -> dict(Tcw [4, 4], outlier [n], n_inliers) plus, with want_info, the fields of orbfe_pose_opt_info as N_e, rounds_run and
+    round_pose / round_iterations / round_trials / round_lambda / round_chi2 / round_nbad / round_exit / round_outlier, cut to the
+    rounds that ran."""
+    kp = np.ascontiguousarray(kp, KP_DTYPE)
+    mi = np.ascontiguousarray(mp_index, np.int32)
+    assert len(mi) == len(kp)
+    pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    R = np.ascontiguousarray(Rcw, np.float32).reshape(9)
+    t = np.ascontiguousarray(tcw, np.float32).reshape(3)
+    n = len(kp)
+    Ne = int((mi >= 0).sum())
+    Tcw, outl = np.zeros((4, 4), np.float32), np.zeros(max(n, 1), np.uint8)
+    n_inl = C.c_int(0)
+    info = None
+    if want_info:
+        info = PoseOptInfo()
+        rbuf = np.zeros(4 * max(Ne, 1), np.uint8)
+        info.outlier = rbuf.ctypes.data
+    h = extractor.h if extractor is not None else None
+    rc = lib().orbfe_pose_optimization(h, C.byref(params), n, _p(kp), _p(mi), len(pts), _p(pts), _p(R), _p(t), _p(Tcw), _p(outl),
+                                       C.byref(n_inl), C.byref(info) if want_info else None)
+    if rc != 0:
+        raise OrbfeError(rc, "orbfe_pose_optimization", lib().orbfe_last_error(h).decode() if h else "")
+    out = dict(Tcw=Tcw, outlier=outl[:n], n_inliers=n_inl.value)
+    if want_info:
+        nr, Ne = info.rounds_run, info.N_e
+        out.update(N_e=Ne, rounds_run=nr, round_pose=np.array(info.pose, np.float64).reshape(4, 12)[:nr],
+                   round_iterations=np.array(info.iterations, np.int32)[:nr], round_trials=np.array(info.trials, np.int32)[:nr],
+                   round_lambda=np.array(info.lambda_, np.float64)[:nr], round_chi2=np.array(info.chi2, np.float64)[:nr],
+                   round_nbad=np.array(info.n_bad, np.int32)[:nr], round_exit=np.array(info.exit_kind, np.int32)[:nr],
+                   round_outlier=rbuf[:nr * Ne].reshape(nr, Ne))
+    return out
+
+
+def pose_optimization_batch_device(extractor, params, batch, d_kp_ptr, d_n_ptr, kp_stride, d_match_ptr, n_map_points, d_points_ptr,
+                                   point_stride_frames, d_pose_in_ptr, d_pose_out_ptr, d_outlier_ptr, d_n_inliers_ptr, stream=None):
+    """orbfe_pose_optimization_batch_device: one block per frame, everything resident in HBM (raw device pointers as ints: the
+    keypoints / counts of extract_batch_device, the matches of match_projection_batch_device, orbfe_world_point records, 12-float
+    poses); asynchronous on `stream`."""
+    extractor._chk(extractor.L.orbfe_pose_optimization_batch_device(extractor.h, C.byref(params), int(batch), d_kp_ptr, d_n_ptr,
+                                                                     int(kp_stride), d_match_ptr, int(n_map_points), d_points_ptr,
+                                                                     int(point_stride_frames), d_pose_in_ptr, d_pose_out_ptr, d_outlier_ptr,
+                                                                     d_n_inliers_ptr, stream), "orbfe_pose_optimization_batch_device")
 
 
 def triangulation_select(raw_match12, raw_bin, hasMP1_now, checkOrientation=True):
