@@ -1,9 +1,12 @@
 // camera.h -- GeometricCamera::unproject of the two camera models (SPEC DECISION S10), shared by kernels_match_tri.hip and
 // kernels_mlpnp.hip.  Same sequence as oracle/match_oracle.c kb8_unproject; contraction is off in every including unit.
+// No HIP here: tests/cpp/mlpnp.cpp includes this text as host C++.
 #pragma once
-#include "device_math.h"
+#include "spec_math.h"
 
+#if defined(__clang__)
 #pragma clang fp contract(off)
+#endif
 
 namespace orbfe {
 
@@ -12,12 +15,12 @@ struct CamP {
     int camera_model;
 };
 
-__device__ __forceinline__ CamP cam_of(const float (&c)[8], int model)
+ORBFE_HD inline CamP cam_of(const float (&c)[8], int model)
 {
     return CamP{c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], model};
 }
 
-__device__ inline void cam_unproject(const CamP& C, float precision, float u, float v, float& rx, float& ry)
+ORBFE_HD inline void cam_unproject(const CamP& C, float precision, float u, float v, float& rx, float& ry)
 {
     const float pwx = (u - C.cx) / C.fx;
     const float pwy = (v - C.cy) / C.fy;

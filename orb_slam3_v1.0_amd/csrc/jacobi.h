@@ -1,14 +1,16 @@
 // jacobi.h -- the pinned Jacobi sequences of SPEC DECISIONS S10 / S12 / S13 and the 3 x 3 binary32 helpers of S12, shared by
-// kernels_match_tri.hip, kernels_twoview.hip and kernels_mlpnp.hip (device) and the host step of orbfe_two_view_reconstruct.
+// kernels_match_tri.hip, kernels_twoview.hip and kernels_mlpnp.hip (device), the host step of orbfe_two_view_reconstruct and, as
+// plain host C++, tests/cpp/mlpnp.cpp and tests/cpp/two_view.cpp.  No HIP outside the __HIPCC__ block at the end.
 // Every translation unit that includes this is built with -ffp-contract=off: c * a - s * b is two products and one add.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <math.h>
+#include <cmath>
+
+#include "host_device.h"
 
 namespace orbfe {
 
 // smallest-eigenvalue eigenvector of the symmetric 4x4 matrix M (destroyed)
-__device__ inline void sym4_min_eigenvector(double (&M)[4][4], double (&vOut)[4])
+ORBFE_HD inline void sym4_min_eigenvector(double (&M)[4][4], double (&vOut)[4])
 {
     double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
     for (int sweep = 0; sweep < 8; sweep++) {
@@ -51,7 +53,7 @@ __device__ inline void sym4_min_eigenvector(double (&M)[4][4], double (&vOut)[4]
 constexpr int kTwoViewSweeps = 10;  // S12: fixed, no data-dependent exit
 
 // the rotation angle of every Jacobi sequence here (S10): c, s from M[p][p], M[q][q], M[p][q] != 0
-__host__ __device__ inline void jacobi_angle(double app, double aqq, double apq, double& c, double& sn)
+ORBFE_HD inline void jacobi_angle(double app, double aqq, double apq, double& c, double& sn)
 {
     const double theta = (aqq - app) / (2.0 * apq);
     const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
@@ -61,25 +63,25 @@ __host__ __device__ inline void jacobi_angle(double app, double aqq, double apq,
 
 // S12, n = 3: kTwoViewSweeps cyclic sweeps in the pair order (0,1) (0,2) (1,2); M becomes (nearly) diagonal, V its eigenvectors
 template <int P, int Q>
-__host__ __device__ inline void jacobi3_rotate(double (&M)[3][3], double (&V)[3][3])
+ORBFE_HD inline void jacobi3_rotate(double (&M)[3][3], double (&V)[3][3])
 {
     const double apq = M[P][Q];
     if (apq == 0.0) return;
     double c, sn;
     jacobi_angle(M[P][P], M[Q][Q], apq, c, sn);
-#pragma unroll
+    ORBFE_UNROLL
     for (int k = 0; k < 3; k++) {
         const double mkp = M[k][P], mkq = M[k][Q];
         M[k][P] = c * mkp - sn * mkq;
         M[k][Q] = sn * mkp + c * mkq;
     }
-#pragma unroll
+    ORBFE_UNROLL
     for (int k = 0; k < 3; k++) {
         const double mpk = M[P][k], mqk = M[Q][k];
         M[P][k] = c * mpk - sn * mqk;
         M[Q][k] = sn * mpk + c * mqk;
     }
-#pragma unroll
+    ORBFE_UNROLL
     for (int k = 0; k < 3; k++) {
         const double vkp = V[k][P], vkq = V[k][Q];
         V[k][P] = c * vkp - sn * vkq;
@@ -87,11 +89,11 @@ __host__ __device__ inline void jacobi3_rotate(double (&M)[3][3], double (&V)[3]
     }
 }
 
-__host__ __device__ inline void jacobi3(double (&M)[3][3], double (&V)[3][3])
+ORBFE_HD inline void jacobi3(double (&M)[3][3], double (&V)[3][3])
 {
-#pragma unroll
+    ORBFE_UNROLL
     for (int i = 0; i < 3; i++)
-#pragma unroll
+        ORBFE_UNROLL
         for (int j = 0; j < 3; j++) V[i][j] = i == j ? 1.0 : 0.0;
     for (int sweep = 0; sweep < kTwoViewSweeps; sweep++) {
         jacobi3_rotate<0, 1>(M, V);
@@ -101,24 +103,24 @@ __host__ __device__ inline void jacobi3(double (&M)[3][3], double (&V)[3][3])
 }
 
 // C = A B, row-major 3 x 3 binary32, k ascending
-__host__ __device__ inline void mul3(const float (&A)[9], const float (&B)[9], float (&C)[9])
+ORBFE_HD inline void mul3(const float (&A)[9], const float (&B)[9], float (&C)[9])
 {
-#pragma unroll
+    ORBFE_UNROLL
     for (int i = 0; i < 3; i++)
-#pragma unroll
+        ORBFE_UNROLL
         for (int j = 0; j < 3; j++) C[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
 }
 
-__host__ __device__ inline void transpose3(const float (&A)[9], float (&T)[9])
+ORBFE_HD inline void transpose3(const float (&A)[9], float (&T)[9])
 {
-#pragma unroll
+    ORBFE_UNROLL
     for (int i = 0; i < 3; i++)
-#pragma unroll
+        ORBFE_UNROLL
         for (int j = 0; j < 3; j++) T[3 * i + j] = A[3 * j + i];
 }
 
 // adjugate / determinant (S12: Matrix3f::inverse())
-__host__ __device__ inline void inv3(const float (&a)[9], float (&o)[9])
+ORBFE_HD inline void inv3(const float (&a)[9], float (&o)[9])
 {
     const float c00 = a[4] * a[8] - a[5] * a[7];
     const float c01 = a[2] * a[7] - a[1] * a[8];
@@ -136,7 +138,7 @@ __host__ __device__ inline void inv3(const float (&a)[9], float (&o)[9])
     o[6] = c20 * inv; o[7] = c21 * inv; o[8] = c22 * inv;
 }
 
-__host__ __device__ inline float det3(const float (&a)[9])
+ORBFE_HD inline float det3(const float (&a)[9])
 {
     const float c00 = a[4] * a[8] - a[5] * a[7];
     const float c10 = a[5] * a[6] - a[3] * a[8];
@@ -146,32 +148,32 @@ __host__ __device__ inline float det3(const float (&a)[9])
 
 // rank-2 step of ComputeF21 (src/TwoViewReconstruction.cc:300-305): Fpre - (Fpre v) v^T with v the eigenvector of the
 // smallest eigenvalue of Fpre^T Fpre (lowest index on ties), binary64, rounded to float per entry
-__host__ __device__ inline void rank2_f(const float (&F)[9], float (&Fn)[9])
+ORBFE_HD inline void rank2_f(const float (&F)[9], float (&Fn)[9])
 {
     double G[3][3], V[3][3];
-#pragma unroll
+    ORBFE_UNROLL
     for (int i = 0; i < 3; i++)
-#pragma unroll
+        ORBFE_UNROLL
         for (int j = 0; j < 3; j++) {
             double acc = 0.0;
-#pragma unroll
+            ORBFE_UNROLL
             for (int k = 0; k < 3; k++) acc = acc + (double)F[3 * k + i] * (double)F[3 * k + j];
             G[i][j] = acc;
         }
     jacobi3(G, V);
     double best = G[0][0];
     double v[3] = {V[0][0], V[1][0], V[2][0]};
-#pragma unroll
+    ORBFE_UNROLL
     for (int i = 1; i < 3; i++) {
         const bool less = G[i][i] < best;
         best = less ? G[i][i] : best;
-#pragma unroll
+        ORBFE_UNROLL
         for (int k = 0; k < 3; k++) v[k] = less ? V[k][i] : v[k];
     }
-#pragma unroll
+    ORBFE_UNROLL
     for (int i = 0; i < 3; i++) {
         const double w = ((double)F[3 * i] * v[0] + (double)F[3 * i + 1] * v[1]) + (double)F[3 * i + 2] * v[2];
-#pragma unroll
+        ORBFE_UNROLL
         for (int j = 0; j < 3; j++) Fn[3 * i + j] = (float)((double)F[3 * i + j] - w * v[j]);
     }
 }
@@ -181,7 +183,7 @@ constexpr int kMlpnpSweeps = 12;  // S13: fixed, no data-dependent exit
 
 // the pairs of round r.  n = 12 (11 rounds of 6): {r, 11} and {(r + k) mod 11, (r - k) mod 11}, k = 1 .. 5 (the circle method);
 // n = 9 (9 rounds of 4, S12): the pairs {i, j}, i < j, i + j == r (mod 9), in ascending i
-__device__ inline void jacobi_round_pair(int n, int r, int slot, int& p, int& q)
+ORBFE_HD inline void jacobi_round_pair(int n, int r, int slot, int& p, int& q)
 {
     if (n == 12) {
         if (slot == 0) { p = r; q = 11; return; }
@@ -209,6 +211,7 @@ struct JacobiTeamWork {
     int P[11][6], Q[11][6];
 };
 
+#if defined(__HIPCC__)
 // n = 12: kMlpnpSweeps sweeps of 11 rounds of 6 pairs; n = 9: kTwoViewSweeps sweeps of 9 rounds of 4 pairs.  Per round the angles
 // from M as it stands at the start of the round, then the column phase of all pairs, then the row phase of all pairs and V's
 // column phase.  M (symmetric, n x n in W.M) becomes (nearly) diagonal, W.V its eigenvectors.  Called by every thread of the block.
@@ -255,5 +258,6 @@ __device__ inline void jacobi_rounds_block(JacobiTeamWork& W, int n)
             __syncthreads();
         }
 }
+#endif  // __HIPCC__
 
 }  // namespace orbfe

@@ -4,9 +4,10 @@
 // SPEC DECISION S13: binary64 where the C++ is double, binary32 where it is float, one operation per
 // operator, no contraction, every sum sequential from 0.0 in ascending order; the null vector of A^T A by a fixed Jacobi sequence
 // (12 sweeps of 11 rounds of 6 disjoint pairs; the planar branch's 9 x 9 by S12's sequence), the 3 x 3 decompositions by the n = 3
-// sequence of jacobi.h, sin / cos / acos / cbrt by the sequences of device_math.h, the Jacobian by the chain rule, the 6 x 6 solve
-// by L D L^T with diagonal pivoting.  tests/mlpnp_ref.py is the normative restatement; every byte this file produces is
-// compared with it.
+// sequence of jacobi.h, sin / cos / acos / cbrt by the sequences of spec_math.h, the Jacobian by the chain rule, the 6 x 6 solve
+// by L D L^T with diagonal pivoting (ldlt.h).  tests/mlpnp_ref.py is the normative restatement; every byte this file produces is
+// compared with it.  What one thread computes on its own (mat3d.h and the headers above) is host-safe text that tests/cpp/mlpnp.cpp
+// includes; this file holds what a team of threads does together.
 //
 //   mlpnp_prep_kernel        one thread per correspondence: bearing (S10 unproject), its null-space basis, the world point in binary64
 //   mlpnp_hypothesis_kernel  one wave per RANSAC hypothesis: computePose (:355-657) on its min-set, CheckInliers (:261-292) over all
@@ -21,6 +22,7 @@
 #include "camera.h"
 #include "jacobi.h"
 #include "ldlt.h"
+#include "mat3d.h"
 
 #pragma clang fp contract(off)
 
@@ -31,8 +33,6 @@ namespace {
 constexpr int kMlpnpChunk = 64;            // points staged per pass of a sequential sum
 constexpr int kMlpnpRefineThreads = 256;
 constexpr int kMlpnpMaxWords = 1024;       // inlier mask words a refine block indexes from LDS: N <= 65536
-constexpr double kEps = 0x1p-52;
-constexpr double kRankTol = 0x1.8p-51;     // 3 eps: Eigen's FullPivHouseholderQR threshold for a 3 x 3
 
 struct MlpnpCorr {   // per correspondence, [N]
     const double* X;     // [N][3] world point
@@ -70,176 +70,6 @@ struct PoseWork {
     unsigned long long maxBits;
     int firstNan;
 };
-
-// ---- 3 x 3 binary64 helpers, row-major ----
-__device__ inline double dot3(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-__device__ inline double norm3(const double* a) { return sqrt(dot3(a, a)); }
-__device__ inline void matvec3(const double* R, const double* x, double* o)
-{
-    for (int i = 0; i < 3; i++) o[i] = (R[3 * i] * x[0] + R[3 * i + 1] * x[1]) + R[3 * i + 2] * x[2];
-}
-__device__ inline void mul3d(const double* A, const double* B, double* C)
-{
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) C[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
-}
-__device__ inline void transpose3d(const double* A, double* T)
-{
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) T[3 * i + j] = A[3 * j + i];
-}
-__device__ inline double det3d(const double* a)
-{
-    const double c00 = a[4] * a[8] - a[5] * a[7];
-    const double c10 = a[5] * a[6] - a[3] * a[8];
-    const double c20 = a[3] * a[7] - a[4] * a[6];
-    return (a[0] * c00 + a[1] * c10) + a[2] * c20;
-}
-__device__ inline void cross3(const double* a, const double* b, double* o)
-{
-    o[0] = a[1] * b[2] - a[2] * b[1];
-    o[1] = a[2] * b[0] - a[0] * b[2];
-    o[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-// eigen-decomposition of the symmetric G (row-major, destroyed) by the n = 3 sequence; order[] = the columns stably sorted by
-// ascending (descending) eigenvalue
-__device__ inline void eig3_sorted(const double* G, bool descending, double (&lam)[3], double (&E)[3][3], int (&order)[3])
-{
-    double M[3][3];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) M[i][j] = G[3 * i + j];
-    jacobi3(M, E);
-    for (int i = 0; i < 3; i++) { lam[i] = M[i][i]; order[i] = i; }
-    for (int a = 1; a < 3; a++)  // stable insertion sort
-        for (int b = a; b > 0; b--) {
-            const double x = lam[order[b]], y = lam[order[b - 1]];
-            const bool before = descending ? x > y : x < y;
-            if (!before) break;
-            const int t = order[b]; order[b] = order[b - 1]; order[b - 1] = t;
-        }
-}
-
-// U V^T of A's singular value decomposition, negated when its determinant is negative (:545-549, :604-608)
-__device__ inline void polar3(const double* A, double* R)
-{
-    double G[9];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) {
-            double acc = 0.0;
-            for (int k = 0; k < 3; k++) acc = acc + A[3 * k + i] * A[3 * k + j];
-            G[3 * i + j] = acc;
-        }
-    double lam[3], E[3][3];
-    int order[3];
-    eig3_sorted(G, true, lam, E, order);
-    double v[3][3], av[3][3], u[3][3];
-    for (int i = 0; i < 3; i++) {
-        for (int k = 0; k < 3; k++) v[i][k] = E[k][order[i]];
-        matvec3(A, v[i], av[i]);
-    }
-    for (int i = 0; i < 2; i++) {
-        const double nrm = norm3(av[i]);
-        for (int k = 0; k < 3; k++) u[i][k] = av[i][k] / nrm;
-    }
-    cross3(u[0], u[1], u[2]);
-    if (dot3(av[2], u[2]) < 0.0)
-        for (int k = 0; k < 3; k++) u[2][k] = -u[2][k];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) R[3 * i + j] = (u[0][i] * v[0][j] + u[1][i] * v[1][j]) + u[2][i] * v[2][j];
-    if (det3d(R) < 0.0)
-        for (int k = 0; k < 9; k++) R[k] = -R[k];
-}
-
-__device__ inline void skew3(const double* w, double* K)
-{
-    K[0] = 0.0; K[1] = -w[2]; K[2] = w[1];
-    K[3] = w[2]; K[4] = 0.0; K[5] = -w[0];
-    K[6] = -w[1]; K[7] = w[0]; K[8] = 0.0;
-}
-
-// rodrigues2rot (:659-674) and, when D is given, dR / dw_k from the closed form (the limit [e_k]x for |w| <= eps)
-__device__ inline void rodrigues2rot(const double* w, double* R, double (*D)[9])
-{
-    double K[9], K2[9];
-    skew3(w, K);
-    mul3d(K, K, K2);
-    const double n = norm3(w);
-    const bool big = n > kEps;
-    double sn, cs;
-    spec_sincos64(n, sn, cs);
-    const double a = sn / n;
-    const double nn = n * n;
-    const double b = (1.0 - cs) / nn;
-    for (int k = 0; k < 9; k++) {
-        const double I = (k == 0 || k == 4 || k == 8) ? 1.0 : 0.0;
-        R[k] = big ? (I + a * K[k]) + b * K2[k] : I;
-    }
-    if (!D) return;
-    const double da = (n * cs - sn) / nn;
-    const double db = (n * sn - 2.0 * (1.0 - cs)) / (nn * n);
-    for (int k = 0; k < 3; k++) {
-        const double ek[3] = {k == 0 ? 1.0 : 0.0, k == 1 ? 1.0 : 0.0, k == 2 ? 1.0 : 0.0};
-        double G[9], GK[9], KG[9];
-        skew3(ek, G);
-        for (int e = 0; e < 9; e++) G[e] = G[e] == 0.0 ? 0.0 : G[e];  // (-0.0 of skew3 -> +0.0: the restatement's table holds +0.0)
-        mul3d(G, K, GK);
-        mul3d(K, G, KG);
-        const double wk = w[k] / n;
-        const double ca = da * wk, cb = db * wk;
-        for (int e = 0; e < 9; e++) {
-            const double S = GK[e] + KG[e];
-            const double Dk = ((ca * K[e] + a * G[e]) + cb * K2[e]) + b * S;
-            D[k][e] = big ? Dk : G[e];
-        }
-    }
-}
-
-// rot2rodrigues (:676-691)
-__device__ inline void rot2rodrigues(const double* R, double* om)
-{
-    const double trace = ((R[0] + R[4]) + R[8]) - 1.0;
-    const double wn = spec_acos64(trace / 2.0);
-    om[0] = 0.0; om[1] = 0.0; om[2] = 0.0;
-    if (wn > kEps) {
-        double sn, cs;
-        spec_sincos64(wn, sn, cs);
-        const double sc = wn / (2.0 * sn);
-        om[0] = (R[7] - R[5]) * sc;
-        om[1] = (R[2] - R[6]) * sc;
-        om[2] = (R[3] - R[1]) * sc;
-    }
-}
-
-// the two rows of mlpnp_residuals_and_jacs (:759-805) of one point: J0 / J1 (6 each) and the residuals
-__device__ inline void point_rows(const double* R, const double (*D)[9], const double* T, const double* X, const double* nr,
-                                           const double* ns, double* J0, double& r0, double* J1, double& r1)
-{
-    double q[3], v[3], DX[3][3];
-    matvec3(R, X, q);
-    for (int i = 0; i < 3; i++) q[i] = q[i] + T[i];
-    const double nq = norm3(q);
-    for (int i = 0; i < 3; i++) v[i] = q[i] / nq;
-    for (int k = 0; k < 3; k++) matvec3(D[k], X, DX[k]);
-    for (int h = 0; h < 2; h++) {
-        const double* nv = h ? ns : nr;
-        double* J = h ? J1 : J0;
-        const double d = dot3(nv, v);
-        double g[3];
-        for (int i = 0; i < 3; i++) g[i] = (nv[i] - d * v[i]) / nq;
-        for (int k = 0; k < 3; k++) J[k] = dot3(g, DX[k]);
-        for (int i = 0; i < 3; i++) J[3 + i] = g[i];
-        (h ? r1 : r0) = d;
-    }
-}
-
-// bit image of a non-negative, non-NaN double: ordered like the value
-__device__ inline unsigned long long nonneg_bits(double v)
-{
-    unsigned long long u;
-    memcpy(&u, &v, sizeof u);
-    return u;
-}
 
 // computePose (:355-657) on the n points indexOf(0 .. n-1) of C, by the whole block sharing W.  Every thread returns the same R (row-major),
 // t, planar flag, Gauss-Newton evaluations and exit kind (0: it_cnt == maxIt, 1: :743, 2: :747).
@@ -667,11 +497,7 @@ int mlpnp_run(MatchScratch& m, hipStream_t s, const orbfe_mlpnp_params* P, const
     }
     if (!mlpnp_params_ok(P) || n > 64 * kMlpnpMaxWords) return ORBFE_ERR_INVALID_ARG;
     std::vector<int> first;  // mvKeyPointIndices (:67-94)
-    for (int i = 0; i < n; i++)
-        if (mpIndex[i] >= 0) {
-            if (mpIndex[i] >= nPoints || kp[i].octave < 0 || kp[i].octave >= nLevels) return ORBFE_ERR_INVALID_ARG;
-            first.push_back(i);
-        }
+    if (!matched_keypoints(n, kp, mpIndex, nPoints, nLevels, first)) return ORBFE_ERR_INVALID_ARG;
     const int N = (int)first.size();
     int minInliers, maxIts, total;
     const int prc = mlpnp_plan(P, N, &minInliers, &maxIts, &total);
@@ -827,10 +653,7 @@ int mlpnp_run(MatchScratch& m, hipStream_t s, const orbfe_mlpnp_params* P, const
         return ORBFE_OK;
     }
     *solved = 1;
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++) Tcw[4 * i + j] = (float)Rt[3 * i + j];
-        Tcw[4 * i + 3] = (float)Rt[9 + i];
-    }
+    fill_tcw(Rt, Rt + 9, Tcw);
     for (int cI = 0; cI < N; cI++)
         if ((mask[cI / 64] >> (cI % 64)) & 1ull) inliers[first[(size_t)cI]] = 1;
     return ORBFE_OK;

@@ -5,7 +5,9 @@
 // SPEC DECISION S14: binary64 where the C++ is double, one operation per operator, no contraction; every sum
 // over edges is a fixed pairwise tree over P = the smallest power of two >= N_e (+0.0 for the padding and for inactive edges); the
 // Levenberg loop and SE3Quat::exp are restated from g2o's published algorithm; the 6 x 6 solve is S13's ldlt_solve6, sin / cos are
-// device_math.h's sequences.  tests/poseopt_ref.py is the normative restatement; every byte this file produces is compared with it.
+// spec_math.h's sequences.  tests/poseopt_ref.py is the normative restatement; every byte this file produces is compared with it.
+// What one thread computes for one edge (poseopt_math.h) is host-safe text that tests/cpp/poseopt.cpp includes; this file holds the
+// tree, the loop around it and the host calls.
 //
 // pose_opt_kernel: ONE block per frame runs the whole call -- the compaction of the matched keypoints into edges, four rounds, every
 // iteration and every trial -- with no host step and no second launch.
@@ -24,8 +26,8 @@
 #include <vector>
 
 #include "match_common.h"
-#include "device_math.h"
 #include "ldlt.h"
+#include "poseopt_math.h"
 
 #pragma clang fp contract(off)
 
@@ -38,7 +40,6 @@ constexpr int kPoseOptMaxKp = 65536;
 constexpr int kPoseOptMaxWaves = kPoseOptThreads / 64;
 constexpr int kPoseOptStack = 8;           // log2(kPoseOptMaxKp / kPoseOptThreads): the deepest run of one thread
 constexpr int kPoseOptTrials = 10;
-constexpr int kNV = 28;                    // 21 of H (upper triangle, row by row), 6 of b, sum rho0
 
 struct PoseOptRounds {   // what the kernel reports per call (host call only)
     int Ne, roundsRun;
@@ -63,14 +64,10 @@ struct PoseOptArgs {
     int* edgeIdx;                // [batch][kpStride] scratch: edge -> keypoint
     PoseOptRounds* rounds;       // nullable
     uint8_t* roundOutlier;       // nullable, [4][N_e]
-    double fx, fy, cx, cy, delta;
+    PoseCam cam;
     float chi2Thr;
     int iterations, nRounds, nLevels;
     float invSigma2[kMaxLevels];
-};
-
-struct EdgeD {
-    double X, Y, Z, ox, oy, w;
 };
 
 template <int CTRL>
@@ -142,108 +139,6 @@ __device__ __forceinline__ void block_tree(PoseOptShared& S, const TreeShape& T,
         else v[k] = (a + S.part[flip][1][k]) + (S.part[flip][2][k] + S.part[flip][3][k]);
     }
     flip ^= 1;
-}
-
-// Xc, the residual and chi2 of one edge at (R, t) (Pinhole.cpp:33-39)
-__device__ __forceinline__ void edge_residual(const PoseOptArgs& G, const EdgeD& E, const double (&R)[9], const double (&t)[3], double& x,
-                                              double& y, double& z, double& e0, double& e1, double& chi2)
-{
-    x = ((R[0] * E.X + R[1] * E.Y) + R[2] * E.Z) + t[0];
-    y = ((R[3] * E.X + R[4] * E.Y) + R[5] * E.Z) + t[1];
-    z = ((R[6] * E.X + R[7] * E.Y) + R[8] * E.Z) + t[2];
-    const double u = G.fx * x / z + G.cx;
-    const double v = G.fy * y / z + G.cy;
-    e0 = E.ox - u;
-    e1 = E.oy - v;
-    chi2 = e0 * (E.w * e0) + e1 * (E.w * e1);
-}
-
-__device__ __forceinline__ void robust(double chi2, double delta, bool huber, double& rho0, double& rho1)
-{
-    if (!huber || chi2 <= delta * delta) {
-        rho0 = chi2;
-        rho1 = 1.0;
-    } else {
-        const double s = sqrt(chi2);
-        rho0 = 2.0 * s * delta - delta * delta;
-        rho1 = delta / s;
-    }
-}
-
-// the 28 terms of one active edge
-__device__ __forceinline__ void edge_terms(const PoseOptArgs& G, const EdgeD& E, const double (&R)[9], const double (&t)[3], bool huber,
-                                           double (&v)[kNV])
-{
-    double x, y, z, e0, e1, chi2, rho0, rho1;
-    edge_residual(G, E, R, t, x, y, z, e0, e1, chi2);
-    robust(chi2, G.delta, huber, rho0, rho1);
-    // J = -projectJac(Xc) SE3deriv (OptimizableTypes.cpp:57-62, Pinhole.cpp:69-79); the structural zeros are not multiplied
-    const double zz = z * z;
-    const double a = G.fx / z;
-    const double b = -G.fx * x / zz;
-    const double c = G.fy / z;
-    const double d = -G.fy * y / zz;
-    const double J0[6] = {-(b * y), -(a * z - b * x), a * y, -a, 0.0, -b};
-    const double J1[6] = {-(d * y - c * z), d * x, -(c * x), 0.0, -c, -d};
-    const double ww = rho1 * E.w;
-    const double we0 = ww * e0, we1 = ww * e1;
-    int at = 0;
-#pragma unroll
-    for (int j = 0; j < 6; j++)
-#pragma unroll
-        for (int k = j; k < 6; k++) v[at++] = (J0[j] * ww) * J0[k] + (J1[j] * ww) * J1[k];
-#pragma unroll
-    for (int j = 0; j < 6; j++) v[21 + j] = -(J0[j] * we0 + J1[j] * we1);
-    v[27] = rho0;
-}
-
-__device__ __forceinline__ void mul3(const double (&A)[9], const double (&B)[9], double (&C)[9])
-{
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) C[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
-}
-
-__device__ __forceinline__ void matvec3(const double (&A)[9], const double (&x)[3], double (&y)[3])
-{
-#pragma unroll
-    for (int i = 0; i < 3; i++) y[i] = (A[3 * i] * x[0] + A[3 * i + 1] * x[1]) + A[3 * i + 2] * x[2];
-}
-
-// exp(dx) . (R, t) -> (Rn, tn): SE3Quat::exp as published, kept as matrices (S14)
-__device__ inline void apply_update(const double (&dx)[6], const double (&R)[9], const double (&t)[3], double (&Rn)[9], double (&tn)[3])
-{
-    const double om[3] = {dx[0], dx[1], dx[2]}, up[3] = {dx[3], dx[4], dx[5]};
-    const double theta = sqrt((om[0] * om[0] + om[1] * om[1]) + om[2] * om[2]);
-    const double Om[9] = {0.0, -om[2], om[1], om[2], 0.0, -om[0], -om[1], om[0], 0.0};
-    const double I[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
-    double Om2[9], Re[9], V[9];
-    mul3(Om, Om, Om2);
-    if (theta < 1e-5) {
-#pragma unroll
-        for (int i = 0; i < 9; i++) {
-            Re[i] = (I[i] + Om[i]) + 0.5 * Om2[i];
-            V[i] = (I[i] + 0.5 * Om[i]) + Om2[i] / 6.0;
-        }
-    } else {
-        double s, c;
-        spec_sincos64(theta, s, c);
-        const double A = s / theta;
-        const double B = (1.0 - c) / (theta * theta);
-        const double C = (theta - s) / (theta * theta * theta);
-#pragma unroll
-        for (int i = 0; i < 9; i++) {
-            Re[i] = (I[i] + A * Om[i]) + B * Om2[i];
-            V[i] = (I[i] + B * Om[i]) + C * Om2[i];
-        }
-    }
-    double Rt[3], Vu[3];
-    mul3(Re, R, Rn);
-    matvec3(Re, t, Rt);
-    matvec3(V, up, Vu);
-#pragma unroll
-    for (int i = 0; i < 3; i++) tn[i] = Rt[i] + Vu[i];
 }
 
 // the frame as one thread sees it: where its run of edges is and how to fetch one
@@ -354,7 +249,7 @@ __device__ void pose_opt_frame(const PoseOptArgs& G, PoseOptShared& S, const Tre
             run_tree<RUN, kNV>(T.run, acc, [&](int k, double (&v)[kNV]) {
                 EdgeD e;
                 int ki;
-                if (fetch(k, e, ki)) edge_terms(G, e, R, t, huber, v);
+                if (fetch(k, e, ki)) edge_terms(G.cam, e, R, t, huber, v);
                 else {
 #pragma unroll
                     for (int q = 0; q < kNV; q++) v[q] = 0.0;
@@ -408,8 +303,8 @@ __device__ void pose_opt_frame(const PoseOptArgs& G, PoseOptShared& S, const Tre
                     v[0] = 0.0;
                     if (fetch(k, e, ki)) {
                         double x, y, z, e0, e1, chi2, rho0, rho1;
-                        edge_residual(G, e, Rn, tn, x, y, z, e0, e1, chi2);
-                        robust(chi2, G.delta, huber, rho0, rho1);
+                        edge_residual(G.cam, e, Rn, tn, x, y, z, e0, e1, chi2);
+                        robust(chi2, G.cam.delta, huber, rho0, rho1);
                         v[0] = rho0;
                     }
                 });
@@ -459,7 +354,7 @@ __device__ void pose_opt_frame(const PoseOptArgs& G, PoseOptShared& S, const Tre
                 e = load_edge(G, F, c, ki);
             }
             double x, y, z, e0, e1, chi2;
-            edge_residual(G, e, R, t, x, y, z, e0, e1, chi2);
+            edge_residual(G.cam, e, R, t, x, y, z, e0, e1, chi2);
             const bool out = (float)chi2 > G.chi2Thr;
             if (RUN > 0) act[k] = !out;
             F.outlier[ki] = out ? 1 : 0;
@@ -578,11 +473,11 @@ constexpr char kPoseOptSizeErr[] =
 void fill_args(PoseOptArgs& G, const orbfe_pose_opt_params* P, const float* invLevelSigma2, int nLevels)
 {
     memset(&G, 0, sizeof G);
-    G.fx = (double)P->cam[0];
-    G.fy = (double)P->cam[1];
-    G.cx = (double)P->cam[2];
-    G.cy = (double)P->cam[3];
-    G.delta = (double)(float)sqrt(P->huber_delta2);   // deltaMono is a float (:805), setDelta takes a double (:837)
+    G.cam.fx = (double)P->cam[0];
+    G.cam.fy = (double)P->cam[1];
+    G.cam.cx = (double)P->cam[2];
+    G.cam.cy = (double)P->cam[3];
+    G.cam.delta = (double)(float)sqrt(P->huber_delta2);   // deltaMono is a float (:805), setDelta takes a double (:837)
     G.chi2Thr = P->chi2_threshold;
     G.iterations = P->iterations;
     G.nRounds = P->rounds;
@@ -618,19 +513,10 @@ int pose_opt_begin(const orbfe_pose_opt_params* P, int nLevels, int n, const orb
     const int crc = pose_opt_check(P, info, err);
     if (crc != ORBFE_OK) return crc;
     if (n > kPoseOptMaxKp) return ORBFE_ERR_INVALID_ARG;
-    first.clear();
-    for (int i = 0; i < n; i++)
-        if (mpIndex[i] >= 0) {
-            if (mpIndex[i] >= nPoints || kp[i].octave < 0 || kp[i].octave >= nLevels) return ORBFE_ERR_INVALID_ARG;
-            first.push_back(i);
-        }
+    if (!matched_keypoints(n, kp, mpIndex, nPoints, nLevels, first)) return ORBFE_ERR_INVALID_ARG;
     const int Ne = (int)first.size();
     *nInliers = 0;
-    for (int i = 0; i < 16; i++) TcwOut[i] = (i % 5 == 0) ? 1.0f : 0.0f;
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++) TcwOut[4 * i + j] = Rcw[3 * i + j];
-        TcwOut[4 * i + 3] = tcw[i];
-    }
+    fill_tcw(Rcw, tcw, TcwOut);
     if (n > 0) memset(outlier, 0, (size_t)n);
     uint8_t* infoOutlier = info ? info->outlier : nullptr;
     if (info) {
@@ -706,10 +592,7 @@ int pose_opt_run(MatchScratch& m, hipStream_t s, const orbfe_pose_opt_params* P,
     const uint8_t* r = hp + inBytes;
     const float* pose = reinterpret_cast<const float*>(r);
     const PoseOptRounds* I = reinterpret_cast<const PoseOptRounds*>(r + (oRounds - oPoseOut));
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++) TcwOut[4 * i + j] = pose[3 * i + j];
-        TcwOut[4 * i + 3] = pose[9 + i];
-    }
+    fill_tcw(pose, pose + 9, TcwOut);
     *nInliers = *reinterpret_cast<const int*>(r + (oNInl - oPoseOut));
     memcpy(outlier, r + (oOutlier - oPoseOut), (size_t)n);
     if (info) {

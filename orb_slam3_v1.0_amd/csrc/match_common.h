@@ -2,6 +2,7 @@
 // wave64 reductions, scratch arenas.
 #pragma once
 #include <string>
+#include <vector>
 
 #include "match.h"
 
@@ -190,6 +191,30 @@ struct Carver {
     size_t off = 0;
     size_t take(size_t bytes) { const size_t o = off; off = (off + bytes + 255) / 256 * 256; return o; }
 };
+
+// mvKeyPointIndices of MLPnPsolver (src/MLPnPsolver.cpp:67-94) and the edge list of PoseOptimization: the keypoints that have a map
+// point, in keypoint order.  false: a map point index or an octave is out of range.
+inline bool matched_keypoints(int n, const orbfe_keypoint* kp, const int* mpIndex, int nPoints, int nLevels, std::vector<int>& first)
+{
+    first.clear();
+    for (int i = 0; i < n; i++)
+        if (mpIndex[i] >= 0) {
+            if (mpIndex[i] >= nPoints || kp[i].octave < 0 || kp[i].octave >= nLevels) return false;
+            first.push_back(i);
+        }
+    return true;
+}
+
+// row-major 4 x 4 Tcw = [R t; 0 0 0 1] from a row-major 3 x 3 R and t, rounded to float
+template <class T>
+inline void fill_tcw(const T* R, const T* t, float* Tcw)
+{
+    for (int i = 0; i < 16; i++) Tcw[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) Tcw[4 * i + j] = (float)R[3 * i + j];
+        Tcw[4 * i + 3] = (float)t[i];
+    }
+}
 
 #define MCHK(call)                                                                          \
     do {                                                                                    \

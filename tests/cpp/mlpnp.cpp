@@ -2,10 +2,11 @@
 //   (a) the library through include/orbfe_adaptor.hpp's MLPnPsolver class (orbfe_mlpnp_ransac),
 //   (b) SPEC DECISION S13 as a single-thread host loop (this file, -O2 -ffp-contract=off, one pinned core): every hypothesis in turn,
 //       Refine for every candidate, the first success returns.
-// (b) is the kernels' arithmetic written out for one CPU thread (the helpers below follow csrc/kernels_mlpnp.hip, device_math.h and
-// jacobi.h line by line, so it is the latency yardstick, not an independent oracle -- that is tests/mlpnp_ref.py): its results
-// must equal the library's bit for bit (host_same=1), and tests/test_mlpnp_cpp.py compares them with the numpy restatement
-// without a GPU.
+// (b) is the kernels' arithmetic for one CPU thread, so it is the latency yardstick, not an independent oracle -- that is
+// tests/mlpnp_ref.py.  Shared with the kernels, as the same text compiled for the host (-I csrc): everything one thread computes on
+// its own -- spec_math.h, camera.h, jacobi.h, mat3d.h, ldlt.h.  Restated here: only the one-thread ordering of what a team of threads
+// does in csrc/kernels_mlpnp.hip (jacobi_rounds, compute_pose, check_inliers, ransac).  Its results must equal the library's bit for
+// bit (host_same=1), and tests/test_mlpnp_cpp.py compares them with the numpy restatement without a GPU.
 //   usage: mlpnp                                   -> library version (link test)
 //          mlpnp <scene.bin> <out.bin> host        -> (b) only, its results to out.bin: no GPU needed
 //          mlpnp <scene.bin> <out.bin> [reps]      -> (a) and (b); results of (a) to out.bin; medians of `reps` calls
@@ -27,495 +28,16 @@
 #include <sched.h>
 
 #include "orbfe_adaptor.hpp"
+#include "camera.h"
+#include "jacobi.h"
+#include "ldlt.h"
+#include "mat3d.h"
 
 using namespace ORB_SLAM3;
 
 namespace s13 {
 
-constexpr int kSweeps3 = 10, kSweeps9 = 10, kSweeps12 = 12;
-constexpr double kEps = 0x1p-52;
-constexpr double kRankTol = 0x1.8p-51;
-
-static float spec_atan2f(float y, float x)
-{
-    const float kPi = 0x1.921fb6p+1f, kPi2 = 0x1.921fb6p+0f, kPi4 = 0x1.921fb6p-1f;
-    const float ax = fabsf(x), ay = fabsf(y);
-    const float mx = ax > ay ? ax : ay;
-    const float mn = ax > ay ? ay : ax;
-    if (mx == 0.0f) return 0.0f;
-    float t = mn / mx;  // correctly rounded (hipcc default: -fhip-fp32-correctly-rounded-divide-sqrt)
-    float base = 0.0f;
-    if (t > 0x1.a8279ap-2f) {
-        t = (t - 1.0f) / (t + 1.0f);
-        base = kPi4;
-    }
-    const float z = t * t;
-    float p = 0x1.61e174p-4f * z;
-    p = p + -0x1.1fe904p-3f;
-    p = p * z;
-    p = p + 0x1.99799ep-3f;
-    p = p * z;
-    p = p + -0x1.555556p-2f;
-    float r = p * z;
-    r = r * t;
-    r = r + t;
-    r = base + r;
-    if (ay > ax) r = kPi2 - r;
-    if (x < 0.0f) r = kPi - r;
-    if (y < 0.0f) r = -r;
-    return r;
-}
-
-
-// cos/sin of an angle given in degrees (src/cuda/Orb_gpu.cu:327-329)
-static void cos_sin_deg(float deg, float& c, float& s)
-{
-    float kf = deg * 0x1.6c16c2p-7f;
-    kf = kf + 0.5f;
-    const int k = (int)kf;
-    const float r = deg - 90.0f * (float)k;
-    const float x = r * 0x1.1df46ap-6f;
-    const float z = x * x;
-    float p = -0x1.9b7856p-13f * z;
-    p = p + 0x1.110e32p-7f;
-    p = p * z;
-    p = p + -0x1.555558p-3f;
-    float sn = p * z;
-    sn = sn * x;
-    sn = sn + x;
-    float q = 0x1.9bfe2ep-16f * z;
-    q = q + -0x1.6c134p-10f;
-    q = q * z;
-    q = q + 0x1.555554p-5f;
-    float cs = q * z;
-    cs = cs * z;
-    float h = 0.5f * z;
-    h = 1.0f - h;
-    cs = cs + h;
-    switch (k & 3) {
-    case 0: c = cs; s = sn; break;
-    case 1: c = -sn; s = cs; break;
-    case 2: c = -cs; s = -sn; break;
-    default: c = sn; s = -cs; break;
-    }
-}
-
-
-template <class Frustum>
-static void camera_project(const Frustum& F, float x, float y, float z, float& u, float& v)
-{
-    if (F.camera_model == 0) {
-        u = F.fx * x / z + F.cx;
-        v = F.fy * y / z + F.cy;
-        return;
-    }
-    const float x2_plus_y2 = x * x + y * y;
-    const float theta = spec_atan2f(sqrtf(x2_plus_y2), z);
-    const float psi = spec_atan2f(y, x);
-    const float theta2 = theta * theta;
-    const float theta3 = theta * theta2;
-    const float theta5 = theta3 * theta2;
-    const float theta7 = theta5 * theta2;
-    const float theta9 = theta7 * theta2;
-    const float r = (((theta + F.k1 * theta3) + F.k2 * theta5) + F.k3 * theta7) + F.k4 * theta9;
-    float deg = psi * 0x1.ca5dc2p+5f;  // 180 / pi
-    if (deg < 0.0f) deg = deg + 360.0f;
-    float c, s;
-    cos_sin_deg(deg, c, s);
-    u = F.fx * r * c + F.cx;
-    v = F.fy * r * s + F.cy;
-}
-
-
-struct CamP {
-    float fx, fy, cx, cy, k1, k2, k3, k4;
-    int camera_model;
-};
-
-static CamP cam_of(const float (&c)[8], int model)
-{
-    return CamP{c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], model};
-}
-
-static void cam_unproject(const CamP& C, float precision, float u, float v, float& rx, float& ry)
-{
-    const float pwx = (u - C.cx) / C.fx;
-    const float pwy = (v - C.cy) / C.fy;
-    rx = pwx;
-    ry = pwy;
-    if (C.camera_model == 0) return;  // Pinhole::unproject (src/CameraModels/Pinhole.cpp:57-60)
-    // KannalaBrandt8::unproject (:115-142): Newton on theta (1 + k1 theta^2 + ...) = theta_d
-    float scale = 1.0f;
-    float theta_d = sqrtf(pwx * pwx + pwy * pwy);
-    const float kHalfPi = 0x1.921fb6p+0f;
-    theta_d = fminf(fmaxf(-kHalfPi, theta_d), kHalfPi);
-    if (theta_d > 1e-8f) {
-        float theta = theta_d;
-        for (int j = 0; j < 10; j++) {
-            const float theta2 = theta * theta, theta4 = theta2 * theta2, theta6 = theta4 * theta2, theta8 = theta4 * theta4;
-            const float k0t2 = C.k1 * theta2, k1t4 = C.k2 * theta4, k2t6 = C.k3 * theta6, k3t8 = C.k4 * theta8;
-            const float num = theta * ((((1.0f + k0t2) + k1t4) + k2t6) + k3t8) - theta_d;
-            const float den = (((1.0f + 3.0f * k0t2) + 5.0f * k1t4) + 7.0f * k2t6) + 9.0f * k3t8;
-            const float fix = num / den;
-            theta = theta - fix;
-            if (fabsf(fix) < precision) break;
-        }
-        float c, sn;
-        cos_sin_deg(theta * 0x1.ca5dc2p+5f, c, sn);  // theta in [0, pi/2] as degrees
-        scale = (sn / c) / theta_d;
-    }
-    rx = pwx * scale;
-    ry = pwy * scale;
-}
-
-
-// ---- SPEC DECISION S13: binary64 sin / cos / acos / cbrt as sequences of + - x / sqrt and the exact floor / frexp / ldexp ----
-// (ocml and glibc differ in the last place).  The same constants and operation order as tests/mlpnp_ref.py sincos64 / acos64 /
-// cbrt64 (tests/test_mlpnp_cpp.py compares every result of this file with the restatement's).
-constexpr double kTwoOverPi = 0x1.45f306dc9c883p-1;
-constexpr double kPio2_1 = 0x1.921fb54400000p+0, kPio2_2 = 0x1.0b4611a600000p-34, kPio2_3 = 0x1.3198a2e037073p-69;  // pi / 2 in three parts (33 + 33 + 53 bits)
-constexpr double kPio2Hi = 0x1.921fb54442d18p+0, kPio2Lo = 0x1.1a62633145c07p-54, kPiHi = 0x1.921fb54442d18p+1, kPiLo = 0x1.1a62633145c07p-53;
-constexpr double kSinC[9] = {-0x1.5555555555555p-3, 0x1.1111111111111p-7, -0x1.a01a01a01a01ap-13, 0x1.71de3a556c734p-19, -0x1.ae64567f544e4p-26, 0x1.6124613a86d09p-33, -0x1.ae7f3e733b81fp-41, 0x1.952c77030ad4ap-49, -0x1.2f49b46814157p-57};  // (-1)^k / (2k + 1)!, k = 1 .. 9
-constexpr double kCosC[10] = {-0x1.0000000000000p-1, 0x1.5555555555555p-5, -0x1.6c16c16c16c17p-10, 0x1.a01a01a01a01ap-16, -0x1.27e4fb7789f5cp-22, 0x1.1eed8eff8d898p-29, -0x1.93974a8c07c9dp-37, 0x1.ae7f3e733b81fp-45, -0x1.6827863b97d97p-53, 0x1.e542ba4020225p-62};  // (-1)^k / (2k)!, k = 1 .. 10
-constexpr double kAsinC[28] = {0x1.5555555555555p-3, 0x1.3333333333333p-4, 0x1.6db6db6db6db7p-5, 0x1.f1c71c71c71c7p-6, 0x1.6e8ba2e8ba2e9p-6, 0x1.1c4ec4ec4ec4fp-6, 0x1.c99999999999ap-7, 0x1.7a87878787878p-7, 0x1.3fde50d79435ep-7, 0x1.12ef3cf3cf3cfp-7, 0x1.df3bd37a6f4dfp-8, 0x1.a6863d70a3d71p-8, 0x1.782dda12f684cp-8, 0x1.51ba308d3dcb1p-8, 0x1.31683bdef7bdfp-8, 0x1.15ee9d45d1746p-8, 0x1.fcaf8fb6db6dbp-9, 0x1.d3d2a8e0dd67dp-9, 0x1.b026f57b13b14p-9, 0x1.90cb77f60c7cep-9, 0x1.750de64d7d05fp-9, 0x1.5c5f56efaaaabp-9, 0x1.464c0950f7d47p-9, 0x1.3275586c5f2f0p-9, 0x1.208d3570ae5a6p-9, 0x1.1052bc5fa960ap-9, 0x1.018f963c229bfp-9, 0x1.e82be60d9127ep-10};  // (2k)! / (4^k k!^2 (2k + 1)), k = 1 .. 28
-constexpr double kCbrtA = 0.75, kCbrtB = 0.22;
-constexpr int kCbrtNewton = 6;
-
-template <int N>
-static double horner64(double z, const double (&c)[N])
-{
-    double p = c[N - 1];
-    for (int k = N - 2; k >= 0; k--) p = p * z + c[k];
-    return p;
-}
-
-// sin x and cos x for 0 <= x < 2^20 (NaN elsewhere): k = floor(x * 2/pi + 0.5), r = ((x - k P1) - k P2) - k P3, Taylor polynomials
-// of r by Horner in z = r * r, picked and signed by the quadrant k mod 4
-static void spec_sincos64(double x, double& s, double& c)
-{
-    if (!(x >= 0.0 && x < 1048576.0)) { s = NAN; c = NAN; return; }
-    const double k = floor(x * kTwoOverPi + 0.5);
-    const double r = ((x - k * kPio2_1) - k * kPio2_2) - k * kPio2_3;
-    const double z = r * r;
-    const double sn = r + (r * z) * horner64(z, kSinC);
-    const double cs = 1.0 + z * horner64(z, kCosC);
-    const double q = k - 4.0 * floor(k * 0.25);
-    if (q == 0.0) { s = sn; c = cs; }
-    else if (q == 1.0) { s = cs; c = -sn; }
-    else if (q == 2.0) { s = -sn; c = -cs; }
-    else { s = -cs; c = sn; }
-}
-
-// acos on [-1, 1] (NaN outside): |x| <= 0.5: pi/2 - asin x; else 2 asin(sqrt((1 - |x|) / 2)), reflected about pi for x < 0;
-// asin t = t + (t z) P(z), z = t * t
-static double spec_acos64(double x)
-{
-    const double ax = fabs(x);
-    if (ax <= 0.5) {
-        const double z = x * x;
-        const double a = x + (x * z) * horner64(z, kAsinC);
-        return (kPio2Hi - a) + kPio2Lo;
-    }
-    const double z = (1.0 - ax) * 0.5;
-    const double sq = sqrt(z);
-    const double a = sq + (sq * z) * horner64(z, kAsinC);
-    const double r = 2.0 * a;
-    return x < 0.0 ? (kPiHi - r) + kPiLo : r;
-}
-
-// cube root of x > 0 (0, inf and NaN are returned as they are): x = m 2^e, e + 3000 = 3 q + r, a = m 2^r in [0.5, 4),
-// y = 0.75 + 0.22 a, six Newton steps, result y 2^(q - 1000)
-static double spec_cbrt64(double x)
-{
-    if (!(x > 0.0 && x < INFINITY)) return x;
-    int e;
-    const double m = frexp(x, &e);
-    const int e3 = e + 3000;
-    const int q = e3 / 3;
-    const int r = e3 - 3 * q;
-    const double a = ldexp(m, r);
-    double y = kCbrtA + kCbrtB * a;
-    for (int i = 0; i < kCbrtNewton; i++) y = y - ((y * y) * y - a) / (3.0 * (y * y));
-    return ldexp(y, q - 1000);
-}
-
-// the rotation angle of every Jacobi sequence here (S10): c, s from M[p][p], M[q][q], M[p][q] != 0
-static void jacobi_angle(double app, double aqq, double apq, double& c, double& sn)
-{
-    const double theta = (aqq - app) / (2.0 * apq);
-    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    c = 1.0 / sqrt(t * t + 1.0);
-    sn = t * c;
-}
-
-// S12, n = 3: kSweeps3 cyclic sweeps in the pair order (0,1) (0,2) (1,2); M becomes (nearly) diagonal, V its eigenvectors
-template <int P, int Q>
-static void jacobi3_rotate(double (&M)[3][3], double (&V)[3][3])
-{
-    const double apq = M[P][Q];
-    if (apq == 0.0) return;
-    double c, sn;
-    jacobi_angle(M[P][P], M[Q][Q], apq, c, sn);
-    for (int k = 0; k < 3; k++) {
-        const double mkp = M[k][P], mkq = M[k][Q];
-        M[k][P] = c * mkp - sn * mkq;
-        M[k][Q] = sn * mkp + c * mkq;
-    }
-    for (int k = 0; k < 3; k++) {
-        const double mpk = M[P][k], mqk = M[Q][k];
-        M[P][k] = c * mpk - sn * mqk;
-        M[Q][k] = sn * mpk + c * mqk;
-    }
-    for (int k = 0; k < 3; k++) {
-        const double vkp = V[k][P], vkq = V[k][Q];
-        V[k][P] = c * vkp - sn * vkq;
-        V[k][Q] = sn * vkp + c * vkq;
-    }
-}
-
-static void jacobi3(double (&M)[3][3], double (&V)[3][3])
-{
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) V[i][j] = i == j ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < kSweeps3; sweep++) {
-        jacobi3_rotate<0, 1>(M, V);
-        jacobi3_rotate<0, 2>(M, V);
-        jacobi3_rotate<1, 2>(M, V);
-    }
-}
-
-
-// the pairs of round r.  n = 12 (11 rounds of 6): {r, 11} and {(r + k) mod 11, (r - k) mod 11}, k = 1 .. 5 (the circle method);
-// n = 9 (9 rounds of 4, S12): the pairs {i, j}, i < j, i + j == r (mod 9), in ascending i
-static void jacobi_round_pair(int n, int r, int slot, int& p, int& q)
-{
-    if (n == 12) {
-        if (slot == 0) { p = r; q = 11; return; }
-        const int a = (r + slot) % 11, b = (r - slot + 11) % 11;
-        p = a < b ? a : b;
-        q = a < b ? b : a;
-        return;
-    }
-    int cnt = 0;
-    p = 0; q = 0;
-    for (int i = 0; i < 9; i++) {
-        const int j = (r - i + 9) % 9;
-        if (i < j) {
-            if (cnt == slot) { p = i; q = j; }
-            cnt++;
-        }
-    }
-}
-
-
-// ---- 3 x 3 binary64 helpers, row-major ----
-static double dot3(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-static double norm3(const double* a) { return sqrt(dot3(a, a)); }
-static void matvec3(const double* R, const double* x, double* o)
-{
-    for (int i = 0; i < 3; i++) o[i] = (R[3 * i] * x[0] + R[3 * i + 1] * x[1]) + R[3 * i + 2] * x[2];
-}
-static void mul3d(const double* A, const double* B, double* C)
-{
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) C[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
-}
-static void transpose3d(const double* A, double* T)
-{
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) T[3 * i + j] = A[3 * j + i];
-}
-static double det3d(const double* a)
-{
-    const double c00 = a[4] * a[8] - a[5] * a[7];
-    const double c10 = a[5] * a[6] - a[3] * a[8];
-    const double c20 = a[3] * a[7] - a[4] * a[6];
-    return (a[0] * c00 + a[1] * c10) + a[2] * c20;
-}
-static void cross3(const double* a, const double* b, double* o)
-{
-    o[0] = a[1] * b[2] - a[2] * b[1];
-    o[1] = a[2] * b[0] - a[0] * b[2];
-    o[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-// eigen-decomposition of the symmetric G (row-major, destroyed) by the n = 3 sequence; order[] = the columns stably sorted by
-// ascending (descending) eigenvalue
-static void eig3_sorted(const double* G, bool descending, double (&lam)[3], double (&E)[3][3], int (&order)[3])
-{
-    double M[3][3];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) M[i][j] = G[3 * i + j];
-    jacobi3(M, E);
-    for (int i = 0; i < 3; i++) { lam[i] = M[i][i]; order[i] = i; }
-    for (int a = 1; a < 3; a++)  // stable insertion sort
-        for (int b = a; b > 0; b--) {
-            const double x = lam[order[b]], y = lam[order[b - 1]];
-            const bool before = descending ? x > y : x < y;
-            if (!before) break;
-            const int t = order[b]; order[b] = order[b - 1]; order[b - 1] = t;
-        }
-}
-
-// U V^T of A's singular value decomposition, negated when its determinant is negative (:545-549, :604-608)
-static void polar3(const double* A, double* R)
-{
-    double G[9];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) {
-            double acc = 0.0;
-            for (int k = 0; k < 3; k++) acc = acc + A[3 * k + i] * A[3 * k + j];
-            G[3 * i + j] = acc;
-        }
-    double lam[3], E[3][3];
-    int order[3];
-    eig3_sorted(G, true, lam, E, order);
-    double v[3][3], av[3][3], u[3][3];
-    for (int i = 0; i < 3; i++) {
-        for (int k = 0; k < 3; k++) v[i][k] = E[k][order[i]];
-        matvec3(A, v[i], av[i]);
-    }
-    for (int i = 0; i < 2; i++) {
-        const double nrm = norm3(av[i]);
-        for (int k = 0; k < 3; k++) u[i][k] = av[i][k] / nrm;
-    }
-    cross3(u[0], u[1], u[2]);
-    if (dot3(av[2], u[2]) < 0.0)
-        for (int k = 0; k < 3; k++) u[2][k] = -u[2][k];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) R[3 * i + j] = (u[0][i] * v[0][j] + u[1][i] * v[1][j]) + u[2][i] * v[2][j];
-    if (det3d(R) < 0.0)
-        for (int k = 0; k < 9; k++) R[k] = -R[k];
-}
-
-static void skew3(const double* w, double* K)
-{
-    K[0] = 0.0; K[1] = -w[2]; K[2] = w[1];
-    K[3] = w[2]; K[4] = 0.0; K[5] = -w[0];
-    K[6] = -w[1]; K[7] = w[0]; K[8] = 0.0;
-}
-
-// rodrigues2rot (:659-674) and, when D is given, dR / dw_k from the closed form (the limit [e_k]x for |w| <= eps)
-static void rodrigues2rot(const double* w, double* R, double (*D)[9])
-{
-    double K[9], K2[9];
-    skew3(w, K);
-    mul3d(K, K, K2);
-    const double n = norm3(w);
-    const bool big = n > kEps;
-    double sn, cs;
-    spec_sincos64(n, sn, cs);
-    const double a = sn / n;
-    const double nn = n * n;
-    const double b = (1.0 - cs) / nn;
-    for (int k = 0; k < 9; k++) {
-        const double I = (k == 0 || k == 4 || k == 8) ? 1.0 : 0.0;
-        R[k] = big ? (I + a * K[k]) + b * K2[k] : I;
-    }
-    if (!D) return;
-    const double da = (n * cs - sn) / nn;
-    const double db = (n * sn - 2.0 * (1.0 - cs)) / (nn * n);
-    for (int k = 0; k < 3; k++) {
-        const double ek[3] = {k == 0 ? 1.0 : 0.0, k == 1 ? 1.0 : 0.0, k == 2 ? 1.0 : 0.0};
-        double G[9], GK[9], KG[9];
-        skew3(ek, G);
-        for (int e = 0; e < 9; e++) G[e] = G[e] == 0.0 ? 0.0 : G[e];  // (-0.0 of skew3 -> +0.0: the restatement's table holds +0.0)
-        mul3d(G, K, GK);
-        mul3d(K, G, KG);
-        const double wk = w[k] / n;
-        const double ca = da * wk, cb = db * wk;
-        for (int e = 0; e < 9; e++) {
-            const double S = GK[e] + KG[e];
-            const double Dk = ((ca * K[e] + a * G[e]) + cb * K2[e]) + b * S;
-            D[k][e] = big ? Dk : G[e];
-        }
-    }
-}
-
-// rot2rodrigues (:676-691)
-static void rot2rodrigues(const double* R, double* om)
-{
-    const double trace = ((R[0] + R[4]) + R[8]) - 1.0;
-    const double wn = spec_acos64(trace / 2.0);
-    om[0] = 0.0; om[1] = 0.0; om[2] = 0.0;
-    if (wn > kEps) {
-        double sn, cs;
-        spec_sincos64(wn, sn, cs);
-        const double sc = wn / (2.0 * sn);
-        om[0] = (R[7] - R[5]) * sc;
-        om[1] = (R[2] - R[6]) * sc;
-        om[2] = (R[3] - R[1]) * sc;
-    }
-}
-
-// the two rows of mlpnp_residuals_and_jacs (:759-805) of one point: J0 / J1 (6 each) and the residuals
-static void point_rows(const double* R, const double (*D)[9], const double* T, const double* X, const double* nr,
-                                           const double* ns, double* J0, double& r0, double* J1, double& r1)
-{
-    double q[3], v[3], DX[3][3];
-    matvec3(R, X, q);
-    for (int i = 0; i < 3; i++) q[i] = q[i] + T[i];
-    const double nq = norm3(q);
-    for (int i = 0; i < 3; i++) v[i] = q[i] / nq;
-    for (int k = 0; k < 3; k++) matvec3(D[k], X, DX[k]);
-    for (int h = 0; h < 2; h++) {
-        const double* nv = h ? ns : nr;
-        double* J = h ? J1 : J0;
-        const double d = dot3(nv, v);
-        double g[3];
-        for (int i = 0; i < 3; i++) g[i] = (nv[i] - d * v[i]) / nq;
-        for (int k = 0; k < 3; k++) J[k] = dot3(g, DX[k]);
-        for (int i = 0; i < 3; i++) J[3 + i] = g[i];
-        (h ? r1 : r0) = d;
-    }
-}
-
-// A x = b for symmetric 6 x 6 A (destroyed) by L D L^T with diagonal pivoting (S13)
-static void ldlt_solve6(double (&A)[6][6], const double (&b)[6], double (&x)[6])
-{
-    double L[6][6], d[6];
-    int perm[6];
-    for (int i = 0; i < 6; i++) {
-        perm[i] = i;
-        for (int j = 0; j < 6; j++) L[i][j] = 0.0;
-    }
-    for (int k = 0; k < 6; k++) {
-        int best = k;
-        for (int i = k + 1; i < 6; i++)
-            if (fabs(A[i][i]) > fabs(A[best][best])) best = i;
-        for (int j = 0; j < 6; j++) { const double t = A[k][j]; A[k][j] = A[best][j]; A[best][j] = t; }
-        for (int i = 0; i < 6; i++) { const double t = A[i][k]; A[i][k] = A[i][best]; A[i][best] = t; }
-        for (int j = 0; j < 6; j++) { const double t = L[k][j]; L[k][j] = L[best][j]; L[best][j] = t; }
-        { const int t = perm[k]; perm[k] = perm[best]; perm[best] = t; }
-        const double dk = A[k][k];
-        d[k] = dk;
-        double col[6];
-        for (int i = 0; i < 6; i++) col[i] = A[i][k];
-        for (int i = k + 1; i < 6; i++) {
-            const double li = dk == 0.0 ? 0.0 : col[i] / dk;
-            L[i][k] = li;
-            for (int j = k + 1; j <= i; j++) {
-                const double val = A[i][j] - li * col[j];
-                A[i][j] = val;
-                A[j][i] = val;
-            }
-        }
-    }
-    double z[6], w[6], xs[6];
-    for (int i = 0; i < 6; i++) {
-        double acc = b[perm[i]];
-        for (int j = 0; j < i; j++) acc = acc - L[i][j] * z[j];
-        z[i] = acc;
-    }
-    for (int i = 0; i < 6; i++) w[i] = d[i] == 0.0 ? 0.0 : z[i] / d[i];
-    for (int i = 5; i >= 0; i--) {
-        double acc = w[i];
-        for (int j = i + 1; j < 6; j++) acc = acc - L[j][i] * xs[j];
-        xs[i] = acc;
-    }
-    for (int i = 0; i < 6; i++) x[perm[i]] = xs[i];
-}
-
+using namespace orbfe;   // csrc/*.h: the kernels' own text of everything one thread computes alone, compiled for the host
 
 struct Pose {
     double R[9], t[3];
@@ -530,7 +52,7 @@ struct Corr {
 // the fixed Jacobi sequence on the symmetric n x n M (n = 12 or 9, stride 12): M becomes (nearly) diagonal, V its eigenvectors
 static void jacobi_rounds(double (*M)[12], double (*V)[12], int n)
 {
-    const int np = n == 12 ? 6 : 4, nr = n == 12 ? 11 : 9, sweeps = n == 12 ? kSweeps12 : kSweeps9;
+    const int np = n == 12 ? 6 : 4, nr = n == 12 ? 11 : 9, sweeps = n == 12 ? kMlpnpSweeps : kTwoViewSweeps;
     for (int i = 0; i < n; i++)
         for (int j = 0; j < n; j++) V[i][j] = i == j ? 1.0 : 0.0;
     for (int sweep = 0; sweep < sweeps; sweep++)

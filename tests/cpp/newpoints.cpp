@@ -4,7 +4,7 @@
 //   (a) orbfe_match_triangulation_batch, (b) orbfe_create_new_points_batch (three alternations, median of `reps` calls each),
 //   (c) the geometry of SPEC DECISION S11 as a single-thread host loop (Pinhole cameras; this file, -O2) over the matches the
 //       K orbfe_triangulation_select calls return -- what the mapping thread computes itself when it only has (a).
-// The host loop doubles as a third implementation: its verdicts and points must equal the library's bit for bit.
+// The host loop's verdicts and points must equal the library's bit for bit (its Jacobi sequence is csrc/jacobi.h's text; the rest is restated).
 //   usage: newpoints <scene.bin> <out.bin> [reps]      (scene.bin: see tests/test_newpoints_cpp.py)
 // -DNEWPOINTS_SEARCH_ONLY builds (a) alone, so that the program links against a library from before the new entry points
 // (tools/newpoints_ab.py: A/B against an earlier build under tools/ab/).
@@ -19,6 +19,7 @@
 #include <sched.h>
 
 #include "orbfe_adaptor.hpp"
+#include "jacobi.h"
 
 using namespace ORB_SLAM3;
 
@@ -73,39 +74,7 @@ static std::shared_ptr<KeyFrame> read_keyframe(Reader& r, int n, const std::vect
 }
 
 // ---- S11 on the host, Pinhole cameras: src/LocalMapping.cc:571-705 + src/GeometricTools.cc:47-66, the operation order of DESIGN.md ----
-static void sym4_min_eigenvector(double (&M)[4][4], double (&vOut)[4])
-{
-    double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-    for (int sweep = 0; sweep < 8; sweep++)
-        for (int p = 0; p < 3; p++)
-            for (int q = p + 1; q < 4; q++) {
-                const double apq = M[p][q];
-                if (apq == 0.0) continue;
-                const double theta = (M[q][q] - M[p][p]) / (2.0 * apq);
-                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-                const double c = 1.0 / std::sqrt(t * t + 1.0);
-                const double sn = t * c;
-                for (int k = 0; k < 4; k++) {
-                    const double a = M[k][p], b = M[k][q];
-                    M[k][p] = c * a - sn * b;
-                    M[k][q] = sn * a + c * b;
-                }
-                for (int k = 0; k < 4; k++) {
-                    const double a = M[p][k], b = M[q][k];
-                    M[p][k] = c * a - sn * b;
-                    M[q][k] = sn * a + c * b;
-                }
-                for (int k = 0; k < 4; k++) {
-                    const double a = V[k][p], b = V[k][q];
-                    V[k][p] = c * a - sn * b;
-                    V[k][q] = sn * a + c * b;
-                }
-            }
-    int m = 0;
-    for (int i = 1; i < 4; i++)
-        if (M[i][i] < M[m][m]) m = i;
-    for (int k = 0; k < 4; k++) vOut[k] = V[k][m];
-}
+using orbfe::sym4_min_eigenvector;   // csrc/jacobi.h: the S10 sequence is the kernels' own text, compiled for the host (-I csrc)
 
 static int host_newpoint(const orbfe_newpoint_params& G, const KeyPoint& k1, const KeyPoint& k2, const float* sf1, const float* sf2, float* x3D)
 {

@@ -1,10 +1,12 @@
 // Optimizer::PoseOptimization (src/Optimizer.cc:765-1067) from a plain C++ program, two ways on the same inputs:
 //   (a) the library through include/orbfe_adaptor.hpp's PoseOptimizer::PoseOptimization wrapper (orbfe_pose_optimization),
 //   (b) SPEC DECISION S14 as a single-thread host loop (this file, -O2 -ffp-contract=off, one pinned core).
-// (b) is the kernel's arithmetic written out for one CPU thread (the 6 x 6 solve is csrc/ldlt.h itself; the other helpers follow
-// csrc/kernels_poseopt.hip and device_math.h line by line, so it is the latency yardstick, not an independent oracle -- that is tests/poseopt_ref.py): its results
-// must equal the library's bit for bit (host_same=1), and tests/test_poseopt_cpp.py compares them with the numpy restatement without
-// a GPU.  The tree sums are walked with a binary-counter stack over all P slots: the same additions as the kernel's tree.
+// (b) is the kernel's arithmetic for one CPU thread, so it is the latency yardstick, not an independent oracle -- that is
+// tests/poseopt_ref.py.  Shared with the kernel, as the same text compiled for the host (-I csrc): the edge arithmetic and the pose
+// update (poseopt_math.h), the 3 x 3 products (mat3d.h), sin / cos (spec_math.h), the 6 x 6 solve (ldlt.h).  Restated here: only the
+// one-thread ordering of what the block does in csrc/kernels_poseopt.hip -- the tree sums, walked with a binary-counter stack over all
+// P slots (the same additions as the kernel's tree), and the Levenberg loop around them.  Its results must equal the library's bit for
+// bit (host_same=1), and tests/test_poseopt_cpp.py compares them with the numpy restatement without a GPU.
 //   usage: poseopt                                   -> library version (link test)
 //          poseopt <scene.bin> <out.bin> host [reps] -> (b) only, its results to out.bin: no GPU needed; with reps, the median
 //          poseopt <scene.bin> <out.bin> [reps]      -> (a) and (b); results of (a) to out.bin; medians of `reps` calls
@@ -26,6 +28,7 @@
 
 #include "orbfe_adaptor.hpp"
 #include "ldlt.h"
+#include "poseopt_math.h"
 
 // The translation unit that binds src/Tracking.cc:869,935 keeps including the reference's Optimizer.h for its other entry points
 // (:698, :946, :952): a class of that name must compile beside the adaptor.
@@ -40,47 +43,12 @@ using namespace ORB_SLAM3;
 
 namespace s14 {
 
-constexpr int kNV = 28, kTrials = 10, kStack = 17;
+using namespace orbfe;   // csrc/ldlt.h, mat3d.h, spec_math.h, poseopt_math.h: the kernel's own text of what one thread computes for one edge
 
-// device_math.h spec_sincos64
-constexpr double kTwoOverPi = 0x1.45f306dc9c883p-1;
-constexpr double kPio2_1 = 0x1.921fb54400000p+0, kPio2_2 = 0x1.0b4611a600000p-34, kPio2_3 = 0x1.3198a2e037073p-69;
-constexpr double kSinC[9] = {-0x1.5555555555555p-3, 0x1.1111111111111p-7, -0x1.a01a01a01a01ap-13, 0x1.71de3a556c734p-19, -0x1.ae64567f544e4p-26,
-                             0x1.6124613a86d09p-33, -0x1.ae7f3e733b81fp-41, 0x1.952c77030ad4ap-49, -0x1.2f49b46814157p-57};
-constexpr double kCosC[10] = {-0x1.0000000000000p-1, 0x1.5555555555555p-5, -0x1.6c16c16c16c17p-10, 0x1.a01a01a01a01ap-16, -0x1.27e4fb7789f5cp-22,
-                              0x1.1eed8eff8d898p-29, -0x1.93974a8c07c9dp-37, 0x1.ae7f3e733b81fp-45, -0x1.6827863b97d97p-53, 0x1.e542ba4020225p-62};
-
-template <int N>
-static double horner64(double z, const double (&c)[N])
-{
-    double p = c[N - 1];
-    for (int k = N - 2; k >= 0; k--) p = p * z + c[k];
-    return p;
-}
-
-static void spec_sincos64(double x, double& s, double& c)
-{
-    if (!(x >= 0.0 && x < 1048576.0)) { s = NAN; c = NAN; return; }
-    const double k = std::floor(x * kTwoOverPi + 0.5);
-    const double r = ((x - k * kPio2_1) - k * kPio2_2) - k * kPio2_3;
-    const double z = r * r;
-    const double sn = r + (r * z) * horner64(z, kSinC);
-    const double cs = 1.0 + z * horner64(z, kCosC);
-    const double q = k - 4.0 * std::floor(k * 0.25);
-    if (q == 0.0) { s = sn; c = cs; }
-    else if (q == 1.0) { s = cs; c = -sn; }
-    else if (q == 2.0) { s = -sn; c = -cs; }
-    else { s = -cs; c = sn; }
-}
-
-using orbfe::ldlt_solve6;   // csrc/ldlt.h: the kernels' own text, compiled for the host
-
-struct EdgeD {
-    double X, Y, Z, ox, oy, w;
-};
+constexpr int kTrials = 10, kStack = 17;
 
 struct Problem {
-    double fx, fy, cx, cy, delta;
+    PoseCam cam;
     float chi2Thr;
     int iterations, rounds;
     std::vector<EdgeD> E;
@@ -88,94 +56,6 @@ struct Problem {
     std::vector<uint8_t> active;
     int P;
 };
-
-static void edge_residual(const Problem& G, const EdgeD& E, const double (&R)[9], const double (&t)[3], double& x, double& y, double& z,
-                          double& e0, double& e1, double& chi2)
-{
-    x = ((R[0] * E.X + R[1] * E.Y) + R[2] * E.Z) + t[0];
-    y = ((R[3] * E.X + R[4] * E.Y) + R[5] * E.Z) + t[1];
-    z = ((R[6] * E.X + R[7] * E.Y) + R[8] * E.Z) + t[2];
-    const double u = G.fx * x / z + G.cx;
-    const double v = G.fy * y / z + G.cy;
-    e0 = E.ox - u;
-    e1 = E.oy - v;
-    chi2 = e0 * (E.w * e0) + e1 * (E.w * e1);
-}
-
-static void robust(double chi2, double delta, bool huber, double& rho0, double& rho1)
-{
-    if (!huber || chi2 <= delta * delta) {
-        rho0 = chi2;
-        rho1 = 1.0;
-    } else {
-        const double s = std::sqrt(chi2);
-        rho0 = 2.0 * s * delta - delta * delta;
-        rho1 = delta / s;
-    }
-}
-
-static void edge_terms(const Problem& G, const EdgeD& E, const double (&R)[9], const double (&t)[3], bool huber, double (&v)[kNV])
-{
-    double x, y, z, e0, e1, chi2, rho0, rho1;
-    edge_residual(G, E, R, t, x, y, z, e0, e1, chi2);
-    robust(chi2, G.delta, huber, rho0, rho1);
-    const double zz = z * z;
-    const double a = G.fx / z;
-    const double b = -G.fx * x / zz;
-    const double c = G.fy / z;
-    const double d = -G.fy * y / zz;
-    const double J0[6] = {-(b * y), -(a * z - b * x), a * y, -a, 0.0, -b};
-    const double J1[6] = {-(d * y - c * z), d * x, -(c * x), 0.0, -c, -d};
-    const double ww = rho1 * E.w;
-    const double we0 = ww * e0, we1 = ww * e1;
-    int at = 0;
-    for (int j = 0; j < 6; j++)
-        for (int k = j; k < 6; k++) v[at++] = (J0[j] * ww) * J0[k] + (J1[j] * ww) * J1[k];
-    for (int j = 0; j < 6; j++) v[21 + j] = -(J0[j] * we0 + J1[j] * we1);
-    v[27] = rho0;
-}
-
-static void mul3(const double (&A)[9], const double (&B)[9], double (&C)[9])
-{
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) C[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
-}
-
-static void matvec3(const double (&A)[9], const double (&x)[3], double (&y)[3])
-{
-    for (int i = 0; i < 3; i++) y[i] = (A[3 * i] * x[0] + A[3 * i + 1] * x[1]) + A[3 * i + 2] * x[2];
-}
-
-static void apply_update(const double (&dx)[6], const double (&R)[9], const double (&t)[3], double (&Rn)[9], double (&tn)[3])
-{
-    const double om[3] = {dx[0], dx[1], dx[2]}, up[3] = {dx[3], dx[4], dx[5]};
-    const double theta = std::sqrt((om[0] * om[0] + om[1] * om[1]) + om[2] * om[2]);
-    const double Om[9] = {0.0, -om[2], om[1], om[2], 0.0, -om[0], -om[1], om[0], 0.0};
-    const double I[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
-    double Om2[9], Re[9], V[9];
-    mul3(Om, Om, Om2);
-    if (theta < 1e-5) {
-        for (int i = 0; i < 9; i++) {
-            Re[i] = (I[i] + Om[i]) + 0.5 * Om2[i];
-            V[i] = (I[i] + 0.5 * Om[i]) + Om2[i] / 6.0;
-        }
-    } else {
-        double s, c;
-        spec_sincos64(theta, s, c);
-        const double A = s / theta;
-        const double B = (1.0 - c) / (theta * theta);
-        const double C = (theta - s) / (theta * theta * theta);
-        for (int i = 0; i < 9; i++) {
-            Re[i] = (I[i] + A * Om[i]) + B * Om2[i];
-            V[i] = (I[i] + B * Om[i]) + C * Om2[i];
-        }
-    }
-    double Rt[3], Vu[3];
-    mul3(Re, R, Rn);
-    matvec3(Re, t, Rt);
-    matvec3(V, up, Vu);
-    for (int i = 0; i < 3; i++) tn[i] = Rt[i] + Vu[i];
-}
 
 // T(v) over the P slots: v(2i) + v(2i + 1) first, then pairs of pairs (a binary counter over the slot index)
 template <int NV, class Term>
@@ -235,7 +115,7 @@ static void run(Problem& G, const float* Rcw, const float* tcw, int n, Result& o
             nIt++;
             double acc[kNV];
             tree<kNV>(P, acc, [&](int c, double (&v)[kNV]) {
-                if (c < Ne && G.active[(size_t)c]) edge_terms(G, G.E[(size_t)c], R, t, huber, v);
+                if (c < Ne && G.active[(size_t)c]) edge_terms(G.cam, G.E[(size_t)c], R, t, huber, v);
                 else
                     for (int q = 0; q < kNV; q++) v[q] = 0.0;
             });
@@ -279,8 +159,8 @@ static void run(Problem& G, const float* Rcw, const float* tcw, int n, Result& o
                     v[0] = 0.0;
                     if (c < Ne && G.active[(size_t)c]) {
                         double x, y, z, e0, e1, chi2, rho0, rho1;
-                        edge_residual(G, G.E[(size_t)c], Rn, tn, x, y, z, e0, e1, chi2);
-                        robust(chi2, G.delta, huber, rho0, rho1);
+                        edge_residual(G.cam, G.E[(size_t)c], Rn, tn, x, y, z, e0, e1, chi2);
+                        robust(chi2, G.cam.delta, huber, rho0, rho1);
                         v[0] = rho0;
                     }
                 });
@@ -314,7 +194,7 @@ static void run(Problem& G, const float* Rcw, const float* tcw, int n, Result& o
         int nBad = 0;
         for (int c = 0; c < Ne; c++) {
             double x, y, z, e0, e1, chi2;
-            edge_residual(G, G.E[(size_t)c], R, t, x, y, z, e0, e1, chi2);
+            edge_residual(G.cam, G.E[(size_t)c], R, t, x, y, z, e0, e1, chi2);
             const bool bad = (float)chi2 > G.chi2Thr;
             G.active[(size_t)c] = bad ? 0 : 1;
             out.outlier[(size_t)G.kpOf[(size_t)c]] = bad ? 1 : 0;
@@ -443,8 +323,7 @@ int main(int argc, char** argv)
     sched_setaffinity(0, sizeof set, &set);  // one pinned core
 
     s14::Problem G;
-    G.fx = (double)cam[0]; G.fy = (double)cam[1]; G.cx = (double)cam[2]; G.cy = (double)cam[3];
-    G.delta = (double)(float)std::sqrt(delta2);
+    G.cam = orbfe::PoseCam{(double)cam[0], (double)cam[1], (double)cam[2], (double)cam[3], (double)(float)std::sqrt(delta2)};
     G.chi2Thr = thr;
     G.iterations = head[3];
     G.rounds = head[4];
@@ -455,7 +334,7 @@ int main(int argc, char** argv)
         for (int i = 0; i < n; i++) {
             if (mpIndex[(size_t)i] < 0) continue;
             const float* p = &points[3 * (size_t)mpIndex[(size_t)i]];
-            G.E.push_back(s14::EdgeD{(double)p[0], (double)p[1], (double)p[2], (double)keys[(size_t)i].pt.x, (double)keys[(size_t)i].pt.y,
+            G.E.push_back(orbfe::EdgeD{(double)p[0], (double)p[1], (double)p[2], (double)keys[(size_t)i].pt.x, (double)keys[(size_t)i].pt.y,
                                      (double)invSigma2[(size_t)keys[(size_t)i].octave]});
             G.kpOf.push_back(i);
         }

@@ -3,8 +3,13 @@
 //   (a) the library through include/orbfe_adaptor.hpp's TwoViewReconstruction class (orbfe_two_view_reconstruct),
 //   (b) SPEC DECISION S12 as a single-thread host loop (this file, -O2 -ffp-contract=off, one pinned core),
 //   (c) the same loop with FindHomography and FindFundamental on two threads (two pinned cores), as :102-107 runs them.
-// (b) / (c) are a third implementation of S12 next to tests/twoview_ref.py and the kernels: their results must equal the
-// library's bit for bit (host_same=1), and tests/test_twoview_cpp.py compares them with the numpy restatement without a GPU.
+// (b) / (c) are the library's arithmetic for one or two CPU threads, so they are the latency yardstick, not an independent oracle --
+// that is tests/twoview_ref.py.  Shared with the library, as the same text compiled for the host (-I csrc): the 3 x 3 helpers, the
+// Jacobi angle, the n = 3 and n = 4 sequences and the rank-2 step (jacobi.h); the per-match terms, the ordered keys, Normalize, the
+// 3 x 3 SVD and the motion hypotheses (twoview_math.h).  Restated here: only the one-thread ordering of what the teams of threads do in
+// csrc/kernels_twoview.hip (null9, find_model and its score sums, check_rt) and the selection rules of the host call (reconstruct).
+// Their results must equal the library's bit for bit (host_same=1), and tests/test_twoview_cpp.py compares them with the numpy
+// restatement without a GPU.
 //   usage: two_view                                   -> library version (link test)
 //          two_view <scene.bin> <out.bin> host        -> (b) and (c) only, results of (b) to out.bin: no GPU needed
 //          two_view <scene.bin> <out.bin> [reps]      -> (a), (b), (c); results of (a) to out.bin; medians of `reps` calls
@@ -24,92 +29,18 @@
 #include <sched.h>
 
 #include "orbfe_adaptor.hpp"
+#include "jacobi.h"
+#include "twoview_math.h"
 
 using namespace ORB_SLAM3;
 
 namespace s12 {
 
-constexpr int kSweeps = 10;
-constexpr double kCosOneDegree = 0x1.ffec097f5af8ap-1;
+using namespace orbfe;   // csrc/jacobi.h, twoview_math.h: the library's own text of everything outside the teams of threads, compiled for the host
 
-static void mul3(const float* A, const float* B, float* C)
-{
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) C[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
-}
-static void transpose3(const float* A, float* T)
-{
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) T[3 * i + j] = A[3 * j + i];
-}
-static void cof3(const float* a, float* c)
-{
-    c[0] = a[4] * a[8] - a[5] * a[7]; c[1] = a[2] * a[7] - a[1] * a[8]; c[2] = a[1] * a[5] - a[2] * a[4];
-    c[3] = a[5] * a[6] - a[3] * a[8]; c[4] = a[0] * a[8] - a[2] * a[6]; c[5] = a[2] * a[3] - a[0] * a[5];
-    c[6] = a[3] * a[7] - a[4] * a[6]; c[7] = a[1] * a[6] - a[0] * a[7]; c[8] = a[0] * a[4] - a[1] * a[3];
-}
-static float det3(const float* a)
-{
-    float c[9];
-    cof3(a, c);
-    return (a[0] * c[0] + a[1] * c[3]) + a[2] * c[6];
-}
-static void inv3(const float* a, float* o)
-{
-    float c[9];
-    cof3(a, c);
-    const float det = (a[0] * c[0] + a[1] * c[3]) + a[2] * c[6];
-    const float inv = 1.0f / det;
-    for (int i = 0; i < 9; i++) o[i] = c[i] * inv;
-}
-static void angle(double app, double aqq, double apq, double& c, double& s)
-{
-    const double theta = (aqq - app) / (2.0 * apq);
-    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-    c = 1.0 / std::sqrt(t * t + 1.0);
-    s = t * c;
-}
-// cyclic sequence (S10): pairs in lexicographic order, every angle from M as it stands
-template <int n>
-static void jacobi_cyclic(double (&M)[n][n], double (&V)[n][n], int sweeps)
-{
-    for (int i = 0; i < n; i++)
-        for (int j = 0; j < n; j++) V[i][j] = i == j ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < sweeps; sweep++)
-        for (int p = 0; p < n - 1; p++)
-            for (int q = p + 1; q < n; q++) {
-                const double apq = M[p][q];
-                if (apq == 0.0) continue;
-                double c, s;
-                angle(M[p][p], M[q][q], apq, c, s);
-                for (int k = 0; k < n; k++) {
-                    const double a = M[k][p], b = M[k][q];
-                    M[k][p] = c * a - s * b;
-                    M[k][q] = s * a + c * b;
-                }
-                for (int k = 0; k < n; k++) {
-                    const double a = M[p][k], b = M[q][k];
-                    M[p][k] = c * a - s * b;
-                    M[q][k] = s * a + c * b;
-                }
-                for (int k = 0; k < n; k++) {
-                    const double a = V[k][p], b = V[k][q];
-                    V[k][p] = c * a - s * b;
-                    V[k][q] = s * a + c * b;
-                }
-            }
-}
-template <int n>
-static void min_column(const double (&M)[n][n], const double (&V)[n][n], double* out)
-{
-    int bi = 0;
-    for (int i = 1; i < n; i++)
-        if (M[i][i] < M[bi][bi]) bi = i;
-    for (int k = 0; k < n; k++) out[k] = V[k][bi];
-}
 // S12 at n = 9: round r = the pairs {i, j}, i < j, i + j == r (mod 9), ascending i; angles from M at the start of the round, then
 // the column phase of all four pairs, the row phase of all four, V's column phase
-static void null9(const float (*A)[9], int rows, float* out)
+static void null9(const float (*A)[9], int rows, float (&out)[9])
 {
     double M[9][9], V[9][9];
     for (int i = 0; i < 9; i++)
@@ -119,7 +50,7 @@ static void null9(const float (*A)[9], int rows, float* out)
             M[i][j] = acc;
             V[i][j] = i == j ? 1.0 : 0.0;
         }
-    for (int sweep = 0; sweep < kSweeps; sweep++)
+    for (int sweep = 0; sweep < kTwoViewSweeps; sweep++)
         for (int r = 0; r < 9; r++) {
             int P[4], Q[4], np = 0;
             double C[4], S[4];
@@ -132,7 +63,7 @@ static void null9(const float (*A)[9], int rows, float* out)
                 const double apq = M[P[e]][Q[e]];
                 skip[e] = apq == 0.0;
                 C[e] = 1.0; S[e] = 0.0;
-                if (!skip[e]) angle(M[P[e]][P[e]], M[Q[e]][Q[e]], apq, C[e], S[e]);
+                if (!skip[e]) jacobi_angle(M[P[e]][P[e]], M[Q[e]][Q[e]], apq, C[e], S[e]);
             }
             for (int e = 0; e < 4; e++) {
                 if (skip[e]) continue;
@@ -159,85 +90,39 @@ static void null9(const float (*A)[9], int rows, float* out)
                 }
             }
         }
-    double v[9];
-    min_column<9>(M, V, v);
-    for (int k = 0; k < 9; k++) out[k] = (float)v[k];
+    int bi = 0;  // the column of the smallest diagonal entry, lowest index on ties
+    for (int i = 1; i < 9; i++)
+        if (M[i][i] < M[bi][bi]) bi = i;
+    for (int k = 0; k < 9; k++) out[k] = (float)V[k][bi];
 }
-static void rank2(const float* F, float* Fn)
-{
-    double G[3][3], V[3][3], v[3];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) {
-            double acc = 0.0;
-            for (int k = 0; k < 3; k++) acc = acc + (double)F[3 * k + i] * (double)F[3 * k + j];
-            G[i][j] = acc;
-        }
-    jacobi_cyclic<3>(G, V, kSweeps);
-    min_column<3>(G, V, v);
-    for (int i = 0; i < 3; i++) {
-        const double w = ((double)F[3 * i] * v[0] + (double)F[3 * i + 1] * v[1]) + (double)F[3 * i + 2] * v[2];
-        for (int j = 0; j < 3; j++) Fn[3 * i + j] = (float)((double)F[3 * i + j] - w * v[j]);
-    }
-}
-static void normalize(const std::vector<KeyPoint>& kp, std::vector<float>& px, std::vector<float>& py, float* T)
-{
-    const int n = (int)kp.size();
-    float meanX = 0.0f, meanY = 0.0f;
-    for (int i = 0; i < n; i++) { meanX = meanX + kp[i].pt.x; meanY = meanY + kp[i].pt.y; }
-    meanX = meanX / (float)n;
-    meanY = meanY / (float)n;
-    float devX = 0.0f, devY = 0.0f;
-    px.resize(n); py.resize(n);
-    for (int i = 0; i < n; i++) {
-        px[i] = kp[i].pt.x - meanX;
-        py[i] = kp[i].pt.y - meanY;
-        devX = devX + std::fabs(px[i]);
-        devY = devY + std::fabs(py[i]);
-    }
-    devX = devX / (float)n;
-    devY = devY / (float)n;
-    const float sX = (float)(1.0 / (double)devX), sY = (float)(1.0 / (double)devY);
-    for (int i = 0; i < n; i++) { px[i] = px[i] * sX; py[i] = py[i] * sY; }
-    for (int i = 0; i < 9; i++) T[i] = 0.0f;
-    T[0] = sX; T[4] = sY; T[2] = -meanX * sX; T[5] = -meanY * sY; T[8] = 1.0f;
-}
-
 struct Pt { float u1, v1, u2, v2; };
 
-static float check_homography(const float* H21, const float* H12, const std::vector<Pt>& pts, float invSigmaSquare, std::vector<uint8_t>& in)
+// CheckHomography (:308-384) / CheckFundamental (:386-471): the two terms of every match in match order, first-image term first.  A
+// rejected term is +0.0f, and adding it leaves the score as it is: the score starts at +0.0f and no term is negative, so it is never -0.0f.
+static float check_homography(const float (&H21)[9], const float (&H12)[9], const std::vector<Pt>& pts, float invSigmaSquare, std::vector<uint8_t>& in)
 {
-    const float th = 5.991f;
     float score = 0.0f;
     for (size_t i = 0; i < pts.size(); i++) {
         const Pt& p = pts[i];
-        bool bIn = true;
-        const float w2 = (float)(1.0 / (double)((H12[6] * p.u2 + H12[7] * p.v2) + H12[8]));
-        const float a = ((H12[0] * p.u2 + H12[1] * p.v2) + H12[2]) * w2, b = ((H12[3] * p.u2 + H12[4] * p.v2) + H12[5]) * w2;
-        const float d1 = ((p.u1 - a) * (p.u1 - a) + (p.v1 - b) * (p.v1 - b)) * invSigmaSquare;
-        if (d1 > th) bIn = false; else score = score + (th - d1);
-        const float w1 = (float)(1.0 / (double)((H21[6] * p.u1 + H21[7] * p.v1) + H21[8]));
-        const float c = ((H21[0] * p.u1 + H21[1] * p.v1) + H21[2]) * w1, d = ((H21[3] * p.u1 + H21[4] * p.v1) + H21[5]) * w1;
-        const float d2 = ((p.u2 - c) * (p.u2 - c) + (p.v2 - d) * (p.v2 - d)) * invSigmaSquare;
-        if (d2 > th) bIn = false; else score = score + (th - d2);
+        float term1, term2;
+        bool bIn;
+        homography_terms(H21, H12, invSigmaSquare, p.u1, p.v1, p.u2, p.v2, term1, term2, bIn);
+        score = score + term1;
+        score = score + term2;
         in[i] = bIn;
     }
     return score;
 }
-static float check_fundamental(const float* F, const std::vector<Pt>& pts, float invSigmaSquare, std::vector<uint8_t>& in)
+static float check_fundamental(const float (&F)[9], const std::vector<Pt>& pts, float invSigmaSquare, std::vector<uint8_t>& in)
 {
-    const float th = 3.841f, thScore = 5.991f;
     float score = 0.0f;
     for (size_t i = 0; i < pts.size(); i++) {
         const Pt& p = pts[i];
-        bool bIn = true;
-        const float a2 = (F[0] * p.u1 + F[1] * p.v1) + F[2], b2 = (F[3] * p.u1 + F[4] * p.v1) + F[5], c2 = (F[6] * p.u1 + F[7] * p.v1) + F[8];
-        const float num2 = (a2 * p.u2 + b2 * p.v2) + c2;
-        const float chi1 = (num2 * num2 / (a2 * a2 + b2 * b2)) * invSigmaSquare;
-        if (chi1 > th) bIn = false; else score = score + (thScore - chi1);
-        const float a1 = (F[0] * p.u2 + F[3] * p.v2) + F[6], b1 = (F[1] * p.u2 + F[4] * p.v2) + F[7], c1 = (F[2] * p.u2 + F[5] * p.v2) + F[8];
-        const float num1 = (a1 * p.u1 + b1 * p.v1) + c1;
-        const float chi2 = (num1 * num1 / (a1 * a1 + b1 * b1)) * invSigmaSquare;
-        if (chi2 > th) bIn = false; else score = score + (thScore - chi2);
+        float term1, term2;
+        bool bIn;
+        fundamental_terms(F, invSigmaSquare, p.u1, p.v1, p.u2, p.v2, term1, term2, bIn);
+        score = score + term1;
+        score = score + term2;
         in[i] = bIn;
     }
     return score;
@@ -285,7 +170,7 @@ static void find_model(const Shared& S, bool isF, Model& best, float* scores)
             sc = check_homography(X21, X12, S.pts, S.invSigmaSquare, cur);
         } else {
             float Fn[9];
-            rank2(X, Fn);
+            rank2_f(X, Fn);
             mul3(S.T2t, Fn, tmp);
             mul3(tmp, S.T1, X21);
             sc = check_fundamental(X21, S.pts, S.invSigmaSquare, cur);
@@ -300,117 +185,8 @@ static void find_model(const Shared& S, bool isF, Model& best, float* scores)
     }
 }
 
-static void svd3(const float* A, float* U, float* w, float* V, bool fullRank)
-{
-    double M[3][3], E[3][3];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) {
-            double acc = 0.0;
-            for (int k = 0; k < 3; k++) acc = acc + (double)A[3 * k + i] * (double)A[3 * k + j];
-            M[i][j] = acc;
-        }
-    jacobi_cyclic<3>(M, E, kSweeps);
-    int order[3] = {0, 1, 2};
-    std::stable_sort(order, order + 3, [&](int a, int b) { return M[a][a] > M[b][b]; });
-    double v[3][3], u[3][3];
-    for (int i = 0; i < 3; i++) {
-        const double lam = M[order[i]][order[i]];
-        w[i] = (float)std::sqrt(lam > 0.0 ? lam : 0.0);
-        for (int k = 0; k < 3; k++) v[i][k] = E[k][order[i]];
-    }
-    auto times = [&](const double* x, double* av) {
-        for (int r = 0; r < 3; r++) av[r] = ((double)A[3 * r] * x[0] + (double)A[3 * r + 1] * x[1]) + (double)A[3 * r + 2] * x[2];
-    };
-    for (int i = 0; i < 2; i++) {
-        double av[3];
-        times(v[i], av);
-        const double nrm = std::sqrt((av[0] * av[0] + av[1] * av[1]) + av[2] * av[2]);
-        for (int r = 0; r < 3; r++) u[i][r] = av[r] / nrm;
-    }
-    u[2][0] = u[0][1] * u[1][2] - u[0][2] * u[1][1];
-    u[2][1] = u[0][2] * u[1][0] - u[0][0] * u[1][2];
-    u[2][2] = u[0][0] * u[1][1] - u[0][1] * u[1][0];
-    if (fullRank) {
-        double av[3];
-        times(v[2], av);
-        if ((av[0] * u[2][0] + av[1] * u[2][1]) + av[2] * u[2][2] < 0.0)
-            for (int r = 0; r < 3; r++) u[2][r] = -u[2][r];
-    }
-    for (int i = 0; i < 3; i++)
-        for (int r = 0; r < 3; r++) { U[3 * r + i] = (float)u[i][r]; V[3 * r + i] = (float)v[i][r]; }
-}
-static void unit3(float* t)
-{
-    const float nrm = std::sqrt((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]);
-    for (int i = 0; i < 3; i++) t[i] = t[i] / nrm;
-}
-static int hypotheses_f(const float* F21, const float* K, float (*R)[9], float (*t)[3])
-{
-    float Kt[9], tmp[9], E[9], U[9], w[3], V[9], Vt[9], Wt[9], R1[9], R2[9];
-    transpose3(K, Kt);
-    mul3(Kt, F21, tmp);
-    mul3(tmp, K, E);
-    svd3(E, U, w, V, false);
-    transpose3(V, Vt);
-    float tt[3] = {U[2], U[5], U[8]};
-    unit3(tt);
-    const float W[9] = {0.0f, -1.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f};
-    transpose3(W, Wt);
-    mul3(U, W, tmp);
-    mul3(tmp, Vt, R1);
-    if (det3(R1) < 0.0f) for (float& x : R1) x = -x;
-    mul3(U, Wt, tmp);
-    mul3(tmp, Vt, R2);
-    if (det3(R2) < 0.0f) for (float& x : R2) x = -x;
-    for (int h = 0; h < 4; h++) {
-        std::memcpy(R[h], (h & 1) ? R2 : R1, sizeof R1);
-        for (int i = 0; i < 3; i++) t[h][i] = h < 2 ? tt[i] : -tt[i];
-    }
-    return 4;
-}
-static int hypotheses_h(const float* H21, const float* K, float (*R)[9], float (*t)[3])
-{
-    float invK[9], tmp[9], A[9], U[9], w[3], V[9], Vt[9], sU[9];
-    inv3(K, invK);
-    mul3(invK, H21, tmp);
-    mul3(tmp, K, A);
-    svd3(A, U, w, V, true);
-    transpose3(V, Vt);
-    const float s = det3(U) * det3(Vt);
-    const float d1 = w[0], d2 = w[1], d3 = w[2];
-    if ((double)(d1 / d2) < 1.00001 || (double)(d2 / d3) < 1.00001) return 0;
-    const float aux1 = std::sqrt((d1 * d1 - d2 * d2) / (d1 * d1 - d3 * d3));
-    const float aux3 = std::sqrt((d2 * d2 - d3 * d3) / (d1 * d1 - d3 * d3));
-    const float x1[4] = {aux1, aux1, -aux1, -aux1}, x3[4] = {aux3, -aux3, aux3, -aux3};
-    const float aux_stheta = std::sqrt((d1 * d1 - d2 * d2) * (d2 * d2 - d3 * d3)) / ((d1 + d3) * d2);
-    const float ctheta = (d2 * d2 + d1 * d3) / ((d1 + d3) * d2);
-    const float stheta[4] = {aux_stheta, -aux_stheta, -aux_stheta, aux_stheta};
-    const float aux_sphi = std::sqrt((d1 * d1 - d2 * d2) * (d2 * d2 - d3 * d3)) / ((d1 - d3) * d2);
-    const float cphi = (d1 * d3 - d2 * d2) / ((d1 - d3) * d2);
-    const float sphi[4] = {aux_sphi, -aux_sphi, -aux_sphi, aux_sphi};
-    for (int i = 0; i < 9; i++) sU[i] = s * U[i];
-    for (int i = 0; i < 8; i++) {
-        const int j = i & 3;
-        const bool second = i >= 4;
-        const float Rp1[9] = {ctheta, 0.0f, -stheta[j], 0.0f, 1.0f, 0.0f, stheta[j], 0.0f, ctheta};
-        const float Rp2[9] = {cphi, 0.0f, sphi[j], 0.0f, -1.0f, 0.0f, sphi[j], 0.0f, -cphi};
-        mul3(sU, second ? Rp2 : Rp1, tmp);
-        mul3(tmp, Vt, R[i]);
-        const float k = second ? d1 + d3 : d1 - d3;
-        const float tp[3] = {x1[j] * k, 0.0f * k, (second ? x3[j] : -x3[j]) * k};
-        for (int r = 0; r < 3; r++) t[i][r] = (U[3 * r] * tp[0] + U[3 * r + 1] * tp[1]) + U[3 * r + 2] * tp[2];
-        unit3(t[i]);
-    }
-    return 8;
-}
-static unsigned ordered_key(float f)
-{
-    unsigned u;
-    std::memcpy(&u, &f, 4);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 // CheckRT (:799-914): flags (bit 0 counted, bit 1 vbGood), x3d, -> nGood, cosine at rank min(50, nGood - 1)
-static int check_rt(const float* R, const float* t, const float* K, const std::vector<Pt>& pts, const std::vector<uint8_t>& inl, float th2,
+static int check_rt(const float (&R)[9], const float (&t)[3], const float (&K)[9], const std::vector<Pt>& pts, const std::vector<uint8_t>& inl, float th2,
                     std::vector<uint8_t>& flags, std::vector<float>& x3d, float& cosSel)
 {
     const float fx = K[0], fy = K[4], cx = K[2], cy = K[5];
@@ -436,15 +212,14 @@ static int check_rt(const float* R, const float* t, const float* K, const std::v
             A[2][j] = p.u2 * P2[8 + j] - P2[j];
             A[3][j] = p.v2 * P2[8 + j] - P2[4 + j];
         }
-        double M[4][4], V[4][4], vv[4];
+        double M[4][4], vv[4];
         for (int i = 0; i < 4; i++)
             for (int j = 0; j < 4; j++) {
                 double acc = 0.0;
                 for (int k = 0; k < 4; k++) acc = acc + (double)A[k][i] * (double)A[k][j];
                 M[i][j] = acc;
             }
-        jacobi_cyclic<4>(M, V, 8);
-        min_column<4>(M, V, vv);
+        sym4_min_eigenvector(M, vv);
         const float X = (float)(vv[0] / vv[3]), Y = (float)(vv[1] / vv[3]), Z = (float)(vv[2] / vv[3]);
         if (!std::isfinite(X) || !std::isfinite(Y) || !std::isfinite(Z)) continue;
         const float dist1 = std::sqrt((X * X + Y * Y) + Z * Z);
@@ -471,9 +246,7 @@ static int check_rt(const float* R, const float* t, const float* K, const std::v
     if (nGood > 0) {
         const size_t idx = (size_t)std::min(50, nGood - 1);
         std::nth_element(keys.begin(), keys.begin() + idx, keys.end());
-        const unsigned k = keys[idx];
-        const unsigned u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-        std::memcpy(&cosSel, &u, 4);
+        cosSel = ordered_key_inverse(keys[idx]);
     }
     return nGood;
 }
@@ -504,8 +277,8 @@ static void reconstruct(const orbfe_two_view_params& P, const std::vector<KeyPoi
     S.sets = sets;
     std::vector<float> x1, y1, x2, y2;
     float T2[9];
-    normalize(k1, x1, y1, S.T1);
-    normalize(k2, x2, y2, T2);
+    normalize_points((int)k1.size(), reinterpret_cast<const orbfe_keypoint*>(k1.data()), x1, y1, S.T1);
+    normalize_points((int)k2.size(), reinterpret_cast<const orbfe_keypoint*>(k2.data()), x2, y2, T2);
     inv3(T2, S.T2inv);
     transpose3(T2, S.T2t);
     const float sigma2 = P.sigma * P.sigma;
@@ -554,7 +327,7 @@ static void reconstruct(const orbfe_two_view_params& P, const std::vector<KeyPoi
     for (uint8_t b : inl) nInl += b != 0;
     const float K[9] = {P.fx, 0.0f, P.cx, 0.0f, P.fy, P.cy, 0.0f, 0.0f, 1.0f};
     float R[8][9], t[8][3];
-    out.nHyp = useH ? hypotheses_h(out.H21, K, R, t) : hypotheses_f(out.F21, K, R, t);
+    out.nHyp = useH ? motion_hypotheses_h(out.H21, K, R, t) : motion_hypotheses_f(out.F21, K, R, t);
     if (out.nHyp == 0) { out.exit_line = 609; return; }
     const float th2 = (float)(4.0 * (double)sigma2);
     std::vector<uint8_t> flags[8];

@@ -31,7 +31,7 @@ ROUNDS12 = [[(r, 11)] + [tuple(sorted(((r + k) % 11, (r - k) % 11))) for k in ra
 assert len({p for r in ROUNDS12 for p in r}) == 66 and all(len({x for p in r for x in p}) == 12 for r in ROUNDS12)
 
 # ---------------------------------------------------------------------------------------------------------------------
-# binary64 sin / cos / acos / cbrt (the same constants as csrc/device_math.h: test_mlpnp.py compares the two tables)
+# binary64 sin / cos / acos / cbrt (the same constants as csrc/spec_math.h: test_mlpnp.py compares the two tables)
 # ---------------------------------------------------------------------------------------------------------------------
 _h = float.fromhex
 TWO_OVER_PI = _h("0x1.45f306dc9c883p-1")

@@ -164,8 +164,8 @@ def test_pinned_functions_against_numpy():
 
 
 def test_device_tables_are_the_restatements():
-    """device_math.h and mlpnp_ref.py share their constants"""
-    txt = open(os.path.join(ROOT, "orb_slam3_v1.0_amd", "csrc", "device_math.h")).read()
+    """spec_math.h and mlpnp_ref.py share their constants"""
+    txt = open(os.path.join(ROOT, "orb_slam3_v1.0_amd", "csrc", "spec_math.h")).read()
 
     def table(name):
         body = re.search(r"constexpr double %s\[\d+\] = \{([^}]*)\}" % name, txt).group(1)

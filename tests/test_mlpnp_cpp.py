@@ -1,7 +1,9 @@
 """tests/cpp/mlpnp.cpp: MLPnPsolver (constructor, SetRansacParameters, one iterate) from a plain C++ program through
 include/orbfe_adaptor.hpp's MLPnPsolver class.  The program carries its own single-thread host loop of SPEC DECISION S13 (the kernels'
-arithmetic written out for the CPU; mlpnp_ref.py is the independent oracle of both).  Without a GPU the loop is compared with the numpy restatement byte for byte;
-on the GPU the library's results through the adaptor must equal both, and a second iterate() on one solver must be refused."""
+arithmetic for the CPU: csrc's host-safe headers compiled as host C++, with only the ordering of the team-parallel parts restated;
+mlpnp_ref.py is the independent oracle of both).  The host loop is built stand-alone with -fsanitize=address,undefined (a program with
+its own main, never loaded into Python) and compared with the numpy restatement byte for byte without a GPU; on the GPU the library's
+results through the adaptor must equal both, and a second iterate() on one solver must be refused."""
 import os
 import re
 import subprocess
@@ -14,20 +16,24 @@ import mlpnp_scenarios as MS
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "orb_slam3_v1.0_amd", "csrc")
 BIN = os.path.join(ROOT, "tests", "cpp", "mlpnp.bin")
+BIN_SAN = os.path.join(ROOT, "tests", "cpp", "mlpnp_san.bin")
 KP = np.dtype([("x", "<f4"), ("y", "<f4"), ("response", "<i4"), ("size", "<f4"), ("octave", "<i4"), ("angle", "<f4")])
 HOST_CASES = [c for c in MS.CASES if c[1] != 49]  # every scene that runs hypotheses
 INT32 = ("solved", "n_inliers", "no_more", "N", "min_inliers", "max_its", "total_iterations", "exit_kind", "returning_iteration", "n_candidates")
 
-_built = []
+_built = {}
 
 
-def _build():
-    if _built:  # once per session
-        return
-    _built.append(1)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "mlpnp.cpp"), "-o", BIN, "-L", CSRC, "-lorbfe", "-Wl,-rpath," + CSRC,
-                           "-Wl,-rpath,/opt/rocm/lib"])
+def _build(san=False):
+    out = BIN_SAN if san else BIN
+    if out in _built:  # once per session
+        return out
+    _built[out] = 1
+    flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if san else ["-O2"]
+    subprocess.check_call(["g++"] + flags + ["-std=c++17", "-Wall", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
+                                             os.path.join(ROOT, "tests", "cpp", "mlpnp.cpp"), "-o", out, "-L", CSRC, "-lorbfe",
+                                             "-Wl,-rpath," + CSRC, "-Wl,-rpath,/opt/rocm/lib"])
+    return out
 
 
 def write_scene(path, sc):
@@ -85,11 +91,11 @@ def test_mlpnp_program_links(built):
 
 @pytest.mark.parametrize("case", HOST_CASES, ids=MS.case_id)
 def test_host_loop_equals_restatement(built, tmp_path, case):
-    """the program's own S13 against mlpnp_ref.ransac: every byte, no GPU"""
-    _build()
+    """the program's own S13, built with AddressSanitizer and UBSan, against mlpnp_ref.ransac: every byte, no GPU"""
+    exe = _build(san=True)
     sc = MS.make_case(case)
     write_scene(tmp_path / "scene.bin", sc)
-    subprocess.check_output([BIN, str(tmp_path / "scene.bin"), str(tmp_path / "out.bin"), "host"])
+    subprocess.check_output([exe, str(tmp_path / "scene.bin"), str(tmp_path / "out.bin"), "host"])
     same(read_result(tmp_path / "out.bin", len(sc["kp_xy"])), MS.ref(sc), MS.case_id(case))
 
 

@@ -19,7 +19,7 @@ BIN = os.path.join(ROOT, "tests", "cpp", "newpoints.bin")
 
 
 def _build():
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
                            os.path.join(ROOT, "tests", "cpp", "newpoints.cpp"), "-o", BIN, "-L", CSRC, "-lorbfe", "-Wl,-rpath," + CSRC,
                            "-Wl,-rpath,/opt/rocm/lib"])
 

@@ -1,8 +1,9 @@
 """tests/cpp/two_view.cpp: TwoViewReconstruction::Reconstruct from a plain C++ program through include/orbfe_adaptor.hpp's
 TwoViewReconstruction class.  The program carries its own host loop of SPEC DECISION S12 (single-thread, and H || F on two
-threads as src/TwoViewReconstruction.cc:102-107): a third implementation next to twoview_ref.py and the kernels.  Without a
-GPU the loop is compared with the numpy restatement byte for byte; on the GPU the library's results through the adaptor must
-equal both."""
+threads as src/TwoViewReconstruction.cc:102-107): the library's arithmetic for the CPU -- csrc's host-safe headers compiled as host
+C++, with only the ordering of the team-parallel parts restated; twoview_ref.py is the independent oracle of both.  The host loop is
+built stand-alone with -fsanitize=address,undefined (a program with its own main, never loaded into Python) and compared with the
+numpy restatement byte for byte without a GPU; on the GPU the library's results through the adaptor must equal both."""
 import os
 import re
 import subprocess
@@ -15,21 +16,25 @@ import twoview_scenarios as TS
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "orb_slam3_v1.0_amd", "csrc")
 BIN = os.path.join(ROOT, "tests", "cpp", "two_view.bin")
+BIN_SAN = os.path.join(ROOT, "tests", "cpp", "two_view_san.bin")
 KP = np.dtype([("x", "<f4"), ("y", "<f4"), ("response", "<i4"), ("size", "<f4"), ("octave", "<i4"), ("angle", "<f4")])
 HOST_CASES = [("general", 300, 0.3, 200), ("plane", 300, 0.0, 200), ("lowpar", 300, 0.0, 200), ("rotation", 300, 0.0, 200),
               ("static", 100, 0.0, 200), ("few", 63, 0.3, 200), ("tinysigma", 100, 1.0, 200), ("general", 65, 0.0, 200)]
 
 
-_built = []
+_built = {}
 
 
-def _build():
-    if _built:  # once per session
-        return
-    _built.append(1)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-pthread", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "two_view.cpp"), "-o", BIN, "-L", CSRC, "-lorbfe", "-Wl,-rpath," + CSRC,
-                           "-Wl,-rpath,/opt/rocm/lib"])
+def _build(san=False):
+    out = BIN_SAN if san else BIN
+    if out in _built:  # once per session
+        return out
+    _built[out] = 1
+    flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if san else ["-O2"]
+    subprocess.check_call(["g++"] + flags + ["-std=c++17", "-Wall", "-ffp-contract=off", "-pthread", "-I", os.path.join(ROOT, "include"),
+                                             "-I", CSRC, os.path.join(ROOT, "tests", "cpp", "two_view.cpp"), "-o", out, "-L", CSRC,
+                                             "-lorbfe", "-Wl,-rpath," + CSRC, "-Wl,-rpath,/opt/rocm/lib"])
+    return out
 
 
 def write_scene(path, sc):
@@ -80,11 +85,12 @@ def test_two_view_program_links(built):
 
 @pytest.mark.parametrize("case", HOST_CASES, ids=TS.case_id)
 def test_host_loop_equals_restatement(built, tmp_path, case):
-    """the program's own S12 (one thread and two) against twoview_ref.reconstruct: every byte, no GPU"""
-    _build()
+    """the program's own S12 (one thread and two), built with AddressSanitizer and UBSan, against twoview_ref.reconstruct: every byte,
+    no GPU"""
+    exe = _build(san=True)
     sc = TS.make(case[0], case[1], 0, case[2], case[3])
     write_scene(tmp_path / "scene.bin", sc)
-    out = subprocess.check_output([BIN, str(tmp_path / "scene.bin"), str(tmp_path / "out.bin"), "host"]).decode()
+    out = subprocess.check_output([exe, str(tmp_path / "scene.bin"), str(tmp_path / "out.bin"), "host"]).decode()
     assert "threads_same=1" in out, out
     same(read_result(tmp_path / "out.bin", len(sc["kp1"]), case[3]), TS.ref(sc), TS.case_id(case))
 

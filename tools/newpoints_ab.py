@@ -34,7 +34,8 @@ import numpy as np  # noqa: E402
 
 
 def build(lib_dir, lib_name, out, search_only):
-    cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "newpoints.cpp"),
+    cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "orb_slam3_v1.0_amd", "csrc"),
+           os.path.join(ROOT, "tests", "cpp", "newpoints.cpp"),
            "-o", out, "-L", lib_dir, "-l" + lib_name, "-Wl,-rpath," + lib_dir, "-Wl,-rpath,/opt/rocm/lib"]
     if search_only:
         cmd.insert(1, "-DNEWPOINTS_SEARCH_ONLY")
