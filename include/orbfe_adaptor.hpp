@@ -1408,14 +1408,16 @@ public:
         p_.iterations = iterations;
     }
     // mvSets for N matches (:64-94)
-    std::vector<int> DrawSets(int N) const
+    std::vector<int> DrawSets(int N) const { return DrawSets(N, p_.iterations); }
+    // the same draw without an object (and so without a GPU): what DrawSets(N) of a solver with `iterations` returns
+    static std::vector<int> DrawSets(int N, int iterations)
     {
         static const bool seeded = (srand(0), true);  // DUtils::Random::SeedRandOnce(0)
         (void)seeded;
-        std::vector<int> sets((size_t)p_.iterations * 8, 0);
+        std::vector<int> sets((size_t)iterations * 8, 0);
         std::vector<int> all((size_t)N), avail;
         for (int i = 0; i < N; i++) all[(size_t)i] = i;
-        for (int it = 0; it < p_.iterations; it++) {
+        for (int it = 0; it < iterations; it++) {
             avail = all;
             for (int j = 0; j < 8; j++) {
                 const int d = (int)avail.size();
@@ -1506,15 +1508,20 @@ public:
         p_.n_iterations = nIterations;
         int minInliers = 0, maxIts = 0, total = 0;
         orbfe_detail::check(orbfe_mlpnp_plan(&p_, N_, &minInliers, &maxIts, &total), nullptr, "orbfe_mlpnp_plan");
-        std::vector<int> sets((size_t)total * p_.min_set, 0);
-        std::vector<int> all((size_t)N_), avail;
-        for (int i = 0; i < N_; i++) all[(size_t)i] = i;
+        return DrawSets(N_, total, p_.min_set);
+    }
+    // the same draw without an object (and so without a GPU): `total` min-sets of `minSet` out of N correspondences
+    static std::vector<int> DrawSets(int N, int total, int minSet)
+    {
+        std::vector<int> sets((size_t)total * minSet, 0);
+        std::vector<int> all((size_t)N), avail;
+        for (int i = 0; i < N; i++) all[(size_t)i] = i;
         for (int it = 0; it < total; it++) {
             avail = all;
-            for (int j = 0; j < p_.min_set; j++) {
+            for (int j = 0; j < minSet; j++) {
                 const int d = (int)avail.size();
                 const int randi = int(((double)rand() / ((double)RAND_MAX + 1.0)) * d);
-                sets[(size_t)it * p_.min_set + j] = avail[(size_t)randi];
+                sets[(size_t)it * minSet + j] = avail[(size_t)randi];
                 avail[(size_t)randi] = avail.back();
                 avail.pop_back();
             }

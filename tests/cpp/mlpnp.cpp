@@ -415,6 +415,15 @@ static double median_us(int reps, F&& fn)
 
 int main(int argc, char** argv)
 {
+    if (argc == 6 && !std::strcmp(argv[1], "drawsets")) {  // drawsets seed N total minSet: the min-sets a process draws after srand(seed); no GPU
+        const int N = std::atoi(argv[3]), total = std::atoi(argv[4]), minSet = std::atoi(argv[5]);
+        if (minSet < 1 || N < minSet || total < 1) return 2;
+        srand((unsigned)std::atoi(argv[2]));  // MLPnPsolver never seeds: in the reference TwoViewReconstruction's SeedRandOnce(0) came before it
+        const std::vector<int> sets = MLPnPsolver::DrawSets(N, total, minSet);
+        for (int it = 0; it < total; it++)
+            for (int j = 0; j < minSet; j++) std::printf("%d%c", sets[(size_t)it * minSet + j], j == minSet - 1 ? '\n' : ' ');
+        return 0;
+    }
     if (argc < 3) {
         std::printf("%s\n", orbfe_version());
         return 0;

@@ -94,6 +94,29 @@ static std::vector<uint8_t> slurp(const char* p)
 
 int main(int argc, char** argv)
 {
+    if (argc == 6 && !std::strcmp(argv[1], "vocload")) {  // vocload voc.txt desc.bin levelsup out.txt: the text loader alone
+        // ORBVocabulary::loadFromTextFile uploads the tree, so it needs a handle (and a GPU); what it loaded shows in
+        // transform()'s maps, printed in the layout of oracle/dbow2_ref_driver.cpp's `transform`
+        ORBextractor ex(500, 2000, 1.2f, 4, 20, 7, 320, 240);
+        ORBVocabulary voc(ex.handle());
+        if (!voc.loadFromTextFile(argv[2])) { std::puts("vocabulary load failed"); return 3; }
+        const auto d = slurp(argv[3]);
+        std::map<unsigned, double> bowVec;
+        std::map<unsigned, std::vector<unsigned>> featVec;
+        voc.transform(d.data(), (int)(d.size() / 32), bowVec, featVec, atoi(argv[4]));
+        FILE* fo = fopen(argv[5], "w");
+        if (!fo) return 4;
+        std::fprintf(fo, "%zu %zu %u\n", bowVec.size(), featVec.size(), voc.size());
+        for (auto& e : bowVec) std::fprintf(fo, "%u %a\n", e.first, e.second);
+        for (auto& e : featVec) {
+            std::fprintf(fo, "%u %zu", e.first, e.second.size());
+            for (unsigned i : e.second) std::fprintf(fo, " %u", i);
+            std::fprintf(fo, "\n");
+        }
+        fclose(fo);
+        std::printf("vocload k=%d L=%d words=%u\n", voc.getBranchingFactor(), voc.getDepthLevels(), voc.size());
+        return 0;
+    }
     if (argc < 7) { std::printf("%s\n", orbfe_version()); return 0; }  // link smoke test (no GPU needed)
     const int W = atoi(argv[1]), H = atoi(argv[2]), M = atoi(argv[5]);
     const auto img = slurp(argv[3]);

@@ -412,6 +412,14 @@ static bool same(const s12::Result& a, const s12::Result& b)
 
 int main(int argc, char** argv)
 {
+    if (argc == 4 && !std::strcmp(argv[1], "drawsets")) {  // drawsets N iterations: a fresh process's first mvSets, one set per line; no GPU
+        const int N = std::atoi(argv[2]), iterations = std::atoi(argv[3]);
+        if (N < 8 || iterations < 1) return 2;
+        const std::vector<int> sets = TwoViewReconstruction::DrawSets(N, iterations);
+        for (int it = 0; it < iterations; it++)
+            for (int j = 0; j < 8; j++) std::printf("%d%c", sets[(size_t)it * 8 + j], j == 7 ? '\n' : ' ');
+        return 0;
+    }
     if (argc < 3) {
         std::printf("%s\n", orbfe_version());
         return 0;

@@ -4,15 +4,16 @@ centres that force first-minimum tie-breaks -- is what the descent has to get ri
 import numpy as np
 
 
-def make_tree(k=10, L=4, seed=0, early_leaf_p=0.08, dup_p=0.1, stop_p=0.05):
-    """Breadth-first ids like loadFromTextFile produces are NOT assumed by the kernels, so ids are assigned
+def make_tree(k=10, L=4, seed=0, early_leaf_p=0.08, dup_p=0.1, stop_p=0.05, children=None):
+    """children(parent id, parent depth) -> the child count of that node where it is not k everywhere (k stays the header's).
+    Breadth-first ids like loadFromTextFile produces are NOT assumed by the kernels, so ids are assigned
     depth-first here (children of one node are not contiguous)."""
     rng = np.random.default_rng(seed)
     parent, depth, desc = [0], [0], [np.zeros(32, np.uint8)]
     kids = [[]]
 
     def grow(pid, d, centre):
-        nk = k if d > 0 else k
+        nk = k if children is None else children(pid, d)
         prev = None
         for j in range(nk):
             nid = len(parent)
@@ -83,7 +84,7 @@ def features_near(tree, n, seed=1, noise_bits=20):
 
 def write_text(tree, path, scoring=0, weighting=0):
     """ORBvoc.txt layout (TemplatedVocabulary::saveToTextFile): nodes in id order need parents before children;
-    make_tree's depth-first ids satisfy that."""
+    make_tree's depth-first ids satisfy that.  Ends with a newline, as saveToTextFile's output and ORBvoc.txt do."""
     with open(path, "w") as f:
         f.write("%d %d %d %d\n" % (tree["k"], tree["L"], scoring, weighting))
         n = len(tree["parent"])
