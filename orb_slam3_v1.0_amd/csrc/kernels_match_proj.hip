@@ -286,12 +286,39 @@ __global__ __launch_bounds__(1024) void proj_prepare_kernel(ProjArgs A)
 // 32-bit keys).  A block owns 256 map points of one frame, ordered by (level, tile): the storage segment
 // of the levels they can match is staged in LDS (records + descriptors, 48 B per keypoint), because the
 // per-lane gathers of this loop are ~8x cheaper from LDS than through the vector L1.
+// A lane does not insert a key where it finds it: it parks up to kTopkPend keys in registers and the wave inserts in
+// rounds (topk_insert_round below) -- 34 executions of the 25-instruction insert per wave instead of 99.
 constexpr int kTopkLds = 768;  // staged keypoints per block (36 KB -> 4 blocks per CU); larger segments read global memory
 
 struct TopkLds {
     int4 rec[kTopkLds];
     unsigned long long desc[kTopkLds][4];
 };
+
+// Pending keys.  The sorted insert is 24 x v_med3_u32 + v_min_u32 for the whole wave whenever ONE lane has a key to
+// insert: on the bench stream some lane has one in 88 % of the iterations, with 18 % of the lanes active.  So a lane
+// does not insert where it finds a key: it parks it in pend[] (registers, static indices only: shift up, store at 0),
+// and the wave runs ONE insert round -- every lane pops pend[0] and runs the chain -- only when some lane is full,
+// then drains after the loops.  An empty slot is kKey32None (no real key: distance < 256), so there is no count to
+// keep: "full" is pend[kTopkPend-1] != none, and a lane with nothing pending runs the chain on none, which changes
+// nothing (med3(a, none, b) = b for a <= b).
+// Exact, whatever the order of the inserts: keys are unique (the rank is unique per frame); the chain leaves the list
+// holding the kTopK smallest of {list, key}, sorted, for ANY key; so the final list is the kTopK smallest of all
+// parked keys.  The pre-test against a keys[kTopK-1] that pending keys have not lowered yet only admits extra keys,
+// which the chain drops; everything the immediate insert would have inserted is still inserted.
+// A lane is full only between the end of an iteration's body and the round that follows it, so a push never overflows.
+__device__ __forceinline__ void topk_insert_round(uint32_t (&keys)[kTopK], uint32_t (&pend)[kTopkPend])
+{
+    const uint32_t key = pend[0];
+#pragma unroll
+    for (int t = 0; t < kTopkPend - 1; t++) pend[t] = pend[t + 1];
+    pend[kTopkPend - 1] = kKey32None;
+    // sorted insert without a dependency chain: after the insert, slot t holds the median of
+    // (old keys[t-1], key, old keys[t]) -- one v_med3_u32 per slot, all 24 independent (top-down, in place)
+#pragma unroll
+    for (int t = kTopK - 1; t > 0; t--) keys[t] = umed3(keys[t - 1], key, keys[t]);
+    keys[0] = min(keys[0], key);
+}
 
 template <bool LDS, bool WIDE>
 __device__ __forceinline__ int topk_scan(const ProjArgs& A, const MpWindow& w, const int* cs, int tabStride, const int4* rec,
@@ -300,6 +327,9 @@ __device__ __forceinline__ int topk_scan(const ProjArgs& A, const MpWindow& w, c
                                          unsigned long long d3, uint32_t (&keys)[kTopK])
 {
     int total = 0;
+    uint32_t pend[kTopkPend];  // found, not yet inserted (topk_insert_round)
+#pragma unroll
+    for (int t = 0; t < kTopkPend; t++) pend[t] = kKey32None;
     // One contiguous slot range per level: all rows of the window's grid columns (columns are contiguous in the
     // level-major visit order); the cell-row test runs per keypoint on the record.  Compared with one range per
     // (level, column) this visits about 1.6x more records, but needs 4 table loads per map point instead of ~60
@@ -329,30 +359,32 @@ __device__ __forceinline__ int topk_scan(const ProjArgs& A, const MpWindow& w, c
                 else qn = rec[p + 1];
             }
             const int cy = q.y >> 8;
-            if (cy < w.minCY || cy > w.maxCY) continue;
             const float dx = __int_as_float(q.z) - w.x, dy = __int_as_float(q.w) - w.y;
-            if (!(fabsf(dx) < w.r && fabsf(dy) < w.r)) continue;  // src/Frame.cc:461
-            int dist;
-            if constexpr (LDS) {
-                const unsigned long long* kd = S->desc[p - segBase];
-                dist = hamming256(kd, d0, d1, d2, d3);
-            } else {
-                const unsigned long long* kd = descS + (size_t)p * 4;
-                dist = hamming256(kd, d0, d1, d2, d3);
-            }
-            if (dist >= A.dCut) continue;  // cannot change the verdict (proj_dcut)
-            total++;
-            uint32_t key = make_key32(dist, q.x);
-            if (key < keys[kTopK - 1]) {
-                // sorted insert without a dependency chain: after the insert, slot t holds the median of
-                // (old keys[t-1], key, old keys[t]) -- one v_med3_u32 per slot, all 24 independent (top-down, in place)
+            if (cy >= w.minCY && cy <= w.maxCY && fabsf(dx) < w.r && fabsf(dy) < w.r) {  // src/Frame.cc:461
+                int dist;
+                if constexpr (LDS) {
+                    const unsigned long long* kd = S->desc[p - segBase];
+                    dist = hamming256(kd, d0, d1, d2, d3);
+                } else {
+                    const unsigned long long* kd = descS + (size_t)p * 4;
+                    dist = hamming256(kd, d0, d1, d2, d3);
+                }
+                if (dist < A.dCut) {  // a larger distance cannot change the verdict (proj_dcut)
+                    total++;
+                    const uint32_t key = make_key32(dist, q.x);
+                    if (key < keys[kTopK - 1]) {  // park it (the lane holds fewer than kTopkPend keys here)
 #pragma unroll
-                for (int t = kTopK - 1; t > 0; t--) keys[t] = umed3(keys[t - 1], key, keys[t]);
-                keys[0] = min(keys[0], key);
+                        for (int t = kTopkPend - 1; t > 0; t--) pend[t] = pend[t - 1];
+                        pend[0] = key;
+                    }
+                }
             }
+            // all lanes of the iteration are back together here: one round for the wave as soon as some lane is full
+            if (__ballot(pend[kTopkPend - 1] != kKey32None)) topk_insert_round(keys, pend);
         }
     }
     }
+    while (__ballot(pend[0] != kKey32None)) topk_insert_round(keys, pend);  // drain
     return total;
 }
 
@@ -390,7 +422,8 @@ __global__ __launch_bounds__(256) void proj_topk_kernel(ProjArgs A)
     if (useLds) {
         // records and descriptors of the segment are contiguous: 48 B per keypoint as 3 x 16-byte pieces, four
         // loads in flight per thread before the LDS stores (a load / store pair per iteration would serialise
-        // the global latency)
+        // the global latency).  v[] is written on every path: left unset where j is out of range, the compiler kept
+        // the array in scratch memory (80 B per lane) and waited for each load in turn to store it there.
         const int nSeg = segEnd - segBase;
         const uint4* gRec = reinterpret_cast<const uint4*>(rec + segBase);
         const uint4* gDesc = reinterpret_cast<const uint4*>(descS + (size_t)segBase * 4);
@@ -401,6 +434,7 @@ __global__ __launch_bounds__(256) void proj_topk_kernel(ProjArgs A)
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 const int j = j0 + k * 256 + (int)threadIdx.x;
+                v[k] = make_uint4(0u, 0u, 0u, 0u);
                 if (j < nSeg * 2) v[k] = gDesc[j];
             }
 #pragma unroll
@@ -414,6 +448,7 @@ __global__ __launch_bounds__(256) void proj_topk_kernel(ProjArgs A)
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 const int j = j0 + k * 256 + (int)threadIdx.x;
+                v[k] = make_uint4(0u, 0u, 0u, 0u);
                 if (j < nSeg) v[k] = gRec[j];
             }
 #pragma unroll
@@ -1072,10 +1107,11 @@ int proj_launch(hipStream_t s, ProjArgs& A, std::string& err)
     MCHK(hipMemsetAsync(A.dbg, 0, (size_t)A.B * 4 * sizeof(int), s));
 #endif
     proj_prepare_launch(s, A, true);
-    // Large launches: thread per map point (164 VALU + 38 SALU instructions per map point, 0.27 ms for 256 x 2000).
+    // Large launches: thread per map point (5942 VALU + 2466 SALU instructions per wave of 64 map points, i.e. 93 + 39 per
+    // map point, on the bench stream at 512 x 2000; 6736 + 2469 before the pending keys of topk_insert_round).
     // Small launches (a single frame has 8 blocks of 256 map points): the wave-per-map-point form spreads the frame's
-    // map points over the chip -- it costs more instructions (181 VALU + 138 SALU per map point, 0.70 ms at the large
-    // size) but a live per-frame call finishes 10-17 % sooner.
+    // map points over the chip -- it costs more instructions (181 VALU + 138 SALU per map point by the earlier count that
+    // gave the thread form 164 + 38; 0.70 ms against 0.27 ms for 256 x 2000) but a live per-frame call finishes 10-17 % sooner.
     const int blocks256 = (A.M + 255) / 256;
     if ((long long)blocks256 * A.B >= 128) {
         if (A.mode == kModeReloc)

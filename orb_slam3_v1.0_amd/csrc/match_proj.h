@@ -12,6 +12,8 @@ constexpr int kClaimFree = 0x7fffffff;
 constexpr int kResolveThreads = 1024;
 constexpr int kResolveBatchedMinFrames = 384;  // launches of at least this many frames take the batched resolve form (proj_launch: measured)
 constexpr int kTopK = 24;         // stored candidates per map point
+// keys a lane of proj_topk_kernel parks before the wave inserts (topk_insert_round); 2 / 4 / 8 measured, DESIGN.md section 4.6
+constexpr int kTopkPend = 4;
 constexpr uint32_t kKey32None = 0xffffffffu;
 constexpr int kRankBits = 20;
 constexpr uint32_t kRankMask = (1u << kRankBits) - 1u;
