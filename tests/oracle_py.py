@@ -1,4 +1,5 @@
 """ctypes loader for the CPU oracle (oracle/liborb_oracle.so).  Tests / bench cpu_baseline only."""
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -123,6 +124,30 @@ def lib():
                                                    ci, ci, ci, vp]
         _lib = L
     return _lib
+
+
+def bind(path):
+    """A second build of the oracle's sources (tests/gate_mutants.py), bound beside the cached library with the signatures
+    lib() declares: they are copied from it, function by function.  Only what lib() has typed is copied: a wrapper that types
+    a function itself must do so on every call, through lib(), as fuse_search_right and search_for_triangulation do -- typed once on
+    first use it would call a library bound here with the default conversions."""
+    ref, L = lib(), C.CDLL(path)
+    for name, f in list(vars(ref).items()):
+        if isinstance(f, ref._FuncPtr):
+            g = getattr(L, name)
+            g.argtypes, g.restype = f.argtypes, f.restype
+    return L
+
+
+@contextlib.contextmanager
+def using(L):
+    """Inside the block every wrapper of this module calls the library `L` (from bind), after it the cached one again."""
+    global _lib
+    cached, _lib = lib(), L
+    try:
+        yield L
+    finally:
+        _lib = cached
 
 
 def _p(a):
