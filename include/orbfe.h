@@ -1018,6 +1018,66 @@ int orbfe_pose_optimization_batch_device(orbfe_handle *h, const orbfe_pose_opt_p
                                          float *d_pose_out, uint8_t *d_outlier, int *d_n_inliers, void *stream);
 
 /* -------------------------------------------------------------------------------------------
+ * Bundle adjustment of the initial map: the line behind orbfe_two_view_reconstruct (src/Tracking.cc:698)
+ * ---------------------------------------------------------------------------------------- */
+/* the camera and the constants of Optimizer::GlobalBundleAdjustemnt(map, 20) (src/Optimizer.cc:60-369); versioned by struct_size */
+typedef struct orbfe_initial_ba_params {
+    int struct_size;          /* sizeof(orbfe_initial_ba_params) at the caller's compile time */
+    int camera_model;         /* ORBFE_CAMERA_PINHOLE; ORBFE_CAMERA_KANNALA_BRANDT8 -> ORBFE_ERR_UNSUPPORTED */
+    float cam[8];             /* fx fy cx cy k1 k2 k3 k4 (mvParameters; only the first four are read) */
+    double huber_delta2;      /* thHuber2D = (float) sqrt(5.99) (:139; 5.99, not 5.991): > 0 */
+    int robust;               /* bRobust (:185): 1 = every edge carries the Huber kernel, 0 = none does */
+    int iterations;           /* nIterations, 20 (src/Tracking.cc:698): [1, 64] */
+    int stereo;               /* 0; anything else (mvuRight >= 0, the ToBody edges) -> ORBFE_ERR_UNSUPPORTED */
+} orbfe_initial_ba_params;
+#define ORBFE_INITIAL_BA_PARAMS_INIT {(int)sizeof(orbfe_initial_ba_params), 0, {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, 5.99, 1, 20, 0}
+
+/* every intermediate of one orbfe_initial_bundle_adjustment call (optional: info may be NULL).  Point p is the p-th i, ascending,
+ * with matches12[i] >= 0; edge 0 of a point is its observation in key frame 1, edge 1 the one in key frame 2.  Entries of
+ * iterations that did not run are zero. */
+typedef struct orbfe_initial_ba_info {
+    int struct_size;          /* sizeof(orbfe_initial_ba_info) at the caller's compile time */
+    int N;                    /* points */
+    int n_iterations;         /* Levenberg iterations started */
+    int n_trials;             /* damped solves tried, all iterations */
+    int exit_kind;            /* ORBFE_POSE_OPT_EXIT_* */
+    int trials[64];           /* damped solves tried in the iteration */
+    double cost[64];          /* the sum of rho0 the iteration ended with (its last accepted trial's, else its build's) */
+    double lambda[64];        /* the damping the iteration ended with */
+    double pose[12];          /* the final pose 2: R (9, row-major) then t (3) in binary64 */
+    double *chi2;             /* [2][N], caller-owned, may be NULL: chi2 of every edge at the final estimate, edge-major */
+    uint8_t *depth_positive;  /* [2][N], caller-owned, may be NULL: isDepthPositive() of every edge at the final estimate */
+} orbfe_initial_ba_info;
+
+/* replaces Optimizer::GlobalBundleAdjustemnt(mpAtlas->GetCurrentMap(), 20) in CreateInitialMapMonocular (src/Tracking.cc:698 ->
+ * src/Optimizer.cc:60-369), the only BundleAdjustment call this fork has: two key frames of which the first is fixed (:133), N map
+ * points each observed once in either frame, EdgeSE3ProjectXYZ, pinhole, one Levenberg run with a Huber kernel and no outlier
+ * rounds.  Numerics: SPEC DECISION S17; tests/initial_ba_ref.py is the normative restatement and the call
+ * equals it byte for byte.
+ * kp1 (n1) / kp2 (n2) = the two key frames' mvKeysUn (x, y, octave are read; the handle's mvInvLevelSigma2 is the information);
+ * matches12 (n1) = vIniMatches (an index into kp2, or negative); points (n1 x 3 floats) = vIniP3D, read where matches12[i] >= 0.
+ * Rcw1 / tcw1 = the fixed pose of key frame 1, Rcw2 / tcw2 = the start of key frame 2's (9 row-major / 3 floats each).
+ * Tcw2_out (16, row-major) = the adjusted pose of key frame 2; points_out (n1 x 3) = the adjusted points, rows with
+ * matches12[i] < 0 as they went in (points_out may be `points`).  The call returns values: where the reference puts them
+ * (SetPose / SetWorldPos, or mTcwGBA / mPosGBA from the second map on) is the caller's matter, see INTEGRATION.md.
+ * No match at all: ORBFE_OK, the outputs equal the inputs, nothing is launched.  That return and every refusal below are
+ * decided from the arguments and the handle's level count before the device is touched.
+ * The whole call -- every iteration and every trial -- is ONE kernel launch of one block; one submission, one synchronisation.
+ * HOST pointers.
+ * ORBFE_ERR_INVALID_ARG: a wrong struct_size (params or info), a parameter outside its range, a match >= n2, an octave of a
+ * matched keypoint (either frame) outside the handle's levels, n1 or n2 > 65536.  ORBFE_ERR_UNSUPPORTED: KannalaBrandt8 (for
+ * S14's reason), stereo != 0; more than two key frames and a free first pose are not offered at all.
+ * NOT the reference's function in these stated respects: g2o is an empty submodule in the reference tree, so the
+ * Levenberg loop, the Schur complement over the points and SE3Quat::exp are restated from the published algorithm (parity with
+ * a g2o build is unpinned, as in S14); the poses are kept as matrices and take no quaternion round trip -- pose 1 is returned by
+ * nobody, where the reference writes it back through a quaternion; the reference's edge order follows a std::map keyed by
+ * pointer, here edge 0 comes first. */
+int orbfe_initial_bundle_adjustment(orbfe_handle *h, const orbfe_initial_ba_params *p, int n1, const orbfe_keypoint *kp1, int n2,
+                                    const orbfe_keypoint *kp2, const int *matches12, const float *points, const float *Rcw1,
+                                    const float *tcw1, const float *Rcw2, const float *tcw2, float *Tcw2_out, float *points_out,
+                                    orbfe_initial_ba_info *info);
+
+/* -------------------------------------------------------------------------------------------
  * Multi-device pool: the batched many-frame mode with host frames, sharded over several GPUs
  * ---------------------------------------------------------------------------------------- */
 /* A pool owns N members.  Member k is a handle made from *params with device_id = devices[k] (params->device_id is ignored),

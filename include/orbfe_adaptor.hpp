@@ -15,12 +15,14 @@
 // classes in the reference tree and against light mock types in tests/cpp/test_adaptor.cpp.
 #pragma once
 
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <memory>
 #include <optional>
@@ -1617,6 +1619,77 @@ struct PoseOptimizer {
         if ((int)(points.size() / 3) < 3) return 0;  // (:949-950: the pose is not touched)
         setPose(pFrame, Tcw.data());
         return nInliers;
+    }
+};
+
+// The numerical core of Tracking::CreateInitialMapMonocular (src/Tracking.cc:698-729) as ONE device call and a host step:
+// Optimizer::GlobalBundleAdjustemnt(map, 20) -- two key frames of which the first is fixed, every initial map point seen once in
+// either -- is orbfe_initial_bundle_adjustment (SPEC DECISION S17); KeyFrame::ComputeSceneMedianDepth(2) (src/KeyFrame.cc:859-892)
+// and the rescale of the baseline and the points (:700-729) run here in binary32, as the reference's floats do:
+//   z = ((r20 X + r21 Y) + r22 Z) + t2 with pose 1 and the adjusted points, sorted ascending, element (N - 1) / 2;
+//   invMedianDepth = 4.0f / median when inertial (IMU_MONOCULAR, :702-703), else 1.0f / median.
+// keys1 / keys2 = the two key frames' mvKeysUn, matches12 = vIniMatches, points = vIniP3D as n1 x 3 floats (in: the triangulated
+// points; out: adjusted, and scaled when the result is true; rows without a match are left alone), Rcw1 / tcw1 = pose 1 (fixed),
+// Rcw2 / tcw2 = pose 2 (in: the start; out: adjusted, tcw2 scaled when the result is true).
+// false = the reference's "Wrong initialization, reseting" (:707): median < 0 or fewer than 50 points -- or a NaN among the depths,
+// which the reference would hand to std::sort (undefined behaviour there, a refusal here).  The outputs then hold the adjusted,
+// unscaled values.
+struct InitialMapAdjuster {
+    static bool Adjust(ORBextractor& extractor, int cameraModel, const std::array<float, 8>& cameraParameters, const std::vector<KeyPoint>& keys1,
+                       const std::vector<KeyPoint>& keys2, const std::vector<int>& matches12, std::vector<float>& points, const float* Rcw1,
+                       const float* tcw1, float* Rcw2, float* tcw2, bool inertial, float* medianDepth = nullptr,
+                       orbfe_initial_ba_info* info = nullptr)
+    {
+        orbfe_initial_ba_params p = ORBFE_INITIAL_BA_PARAMS_INIT;
+        p.camera_model = cameraModel;
+        for (int i = 0; i < 8; i++) p.cam[i] = cameraParameters[(size_t)i];
+        const int n1 = (int)keys1.size(), n2 = (int)keys2.size();
+        if ((int)matches12.size() != n1 || (int)points.size() != 3 * n1) throw std::invalid_argument("InitialMapAdjuster::Adjust: sizes");
+        std::array<float, 16> Tcw;
+        orbfe_handle* h = extractor.handle();
+        orbfe_detail::check(orbfe_initial_bundle_adjustment(h, &p, n1, reinterpret_cast<const orbfe_keypoint*>(keys1.data()), n2,
+                                                            reinterpret_cast<const orbfe_keypoint*>(keys2.data()), matches12.data(),
+                                                            points.data(), Rcw1, tcw1, Rcw2, tcw2, Tcw.data(), points.data(), info),
+                            h, "orbfe_initial_bundle_adjustment");
+        for (int i = 0; i < 3; i++) {
+            for (int j = 0; j < 3; j++) Rcw2[3 * i + j] = Tcw[(size_t)(4 * i + j)];
+            tcw2[i] = Tcw[(size_t)(4 * i + 3)];
+        }
+        return MedianDepthScale(matches12, points, Rcw1, tcw1, tcw2, inertial, medianDepth);
+    }
+
+    // The host step of Adjust on the C call's outputs (src/KeyFrame.cc:859-892, src/Tracking.cc:700-729): the median depth of the
+    // matched rows of `points` in key frame 1, then -- when the result is true -- tcw2 and those rows scaled by 1 / median (4 / median
+    // when inertial).  It touches no device: tests/cpp/initial_ba.cpp runs this text on its host loop's results.
+    static bool MedianDepthScale(const std::vector<int>& matches12, std::vector<float>& points, const float* Rcw1, const float* tcw1,
+                                 float* tcw2, bool inertial, float* medianDepth = nullptr)
+    {
+        const int n1 = (int)matches12.size();
+        std::vector<float> depths;
+        bool nan = false;
+        for (int i = 0; i < n1; i++) {
+            if (matches12[(size_t)i] < 0) continue;
+            const float* X = &points[3 * (size_t)i];
+            const float z = ((Rcw1[6] * X[0] + Rcw1[7] * X[1]) + Rcw1[8] * X[2]) + tcw1[2];
+            nan = nan || z != z;
+            depths.push_back(z);
+        }
+        if (medianDepth) *medianDepth = 0.0f;
+        if (depths.empty()) return false;
+        if (nan) {
+            if (medianDepth) *medianDepth = std::numeric_limits<float>::quiet_NaN();
+            return false;
+        }
+        std::sort(depths.begin(), depths.end());
+        const float median = depths[(depths.size() - 1) / 2];
+        if (medianDepth) *medianDepth = median;
+        if (median < 0 || depths.size() < 50) return false;
+        const float invMedianDepth = (inertial ? 4.0f : 1.0f) / median;
+        for (int i = 0; i < 3; i++) tcw2[i] = tcw2[i] * invMedianDepth;
+        for (int i = 0; i < n1; i++)
+            if (matches12[(size_t)i] >= 0)
+                for (int k = 0; k < 3; k++) points[3 * (size_t)i + k] = points[3 * (size_t)i + k] * invMedianDepth;
+        return true;
     }
 };
 

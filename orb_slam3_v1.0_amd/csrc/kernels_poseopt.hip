@@ -7,7 +7,7 @@
 // Levenberg loop and SE3Quat::exp are restated from g2o's published algorithm; the 6 x 6 solve is S13's ldlt_solve6, sin / cos are
 // spec_math.h's sequences.  tests/poseopt_ref.py is the normative restatement; every byte this file produces is compared with it.
 // What one thread computes for one edge (poseopt_math.h) is host-safe text that tests/cpp/poseopt.cpp includes; this file holds the
-// tree, the loop around it and the host calls.
+// loop around the tree and the host calls; the tree itself (block_tree.h) is shared with kernels_initial_ba.hip (S17).
 //
 // pose_opt_kernel: ONE block per frame runs the whole call -- the compaction of the matched keypoints into edges, four rounds, every
 // iteration and every trial -- with no host step and no second launch.
@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "match_common.h"
+#include "block_tree.h"
 #include "ldlt.h"
 #include "poseopt_math.h"
 
@@ -35,10 +36,9 @@ namespace orbfe {
 
 namespace {
 
-constexpr int kPoseOptThreads = 256;
+constexpr int kPoseOptThreads = kTreeThreads;
 constexpr int kPoseOptMaxKp = 65536;
-constexpr int kPoseOptMaxWaves = kPoseOptThreads / 64;
-constexpr int kPoseOptStack = 8;           // log2(kPoseOptMaxKp / kPoseOptThreads): the deepest run of one thread
+constexpr int kPoseOptMaxWaves = kTreeMaxWaves;
 constexpr int kPoseOptTrials = 10;
 
 struct PoseOptRounds {   // what the kernel reports per call (host call only)
@@ -70,76 +70,10 @@ struct PoseOptArgs {
     float invSigma2[kMaxLevels];
 };
 
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, false);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-
-// level l of the tree inside a wave: every lane adds the sum held by the other half of its 2^(l+1)-lane group.  All 64 lanes active.
-__device__ __forceinline__ double wave_level_add(double v, int l)
-{
-    switch (l) {
-    case 0: return v + dpp_f64<0xB1>(v);    // quad_perm [1,0,3,2]
-    case 1: return v + dpp_f64<0x4E>(v);    // quad_perm [2,3,0,1]
-    case 2: return v + dpp_f64<0x141>(v);   // row_half_mirror: a lane of the other quad, which holds that quad's sum
-    case 3: return v + dpp_f64<0x140>(v);   // row_mirror
-    case 4: return v + __shfl_xor(v, 16);
-    default: return v + __shfl_xor(v, 32);
-    }
-}
-
 struct PoseOptShared {
     double part[2][kPoseOptMaxWaves][kNV];
     int waveCount[kPoseOptMaxWaves];
 };
-
-// the shape of the tree for this block
-struct TreeShape {
-    int run;        // edges per thread
-    int lvWave;     // levels inside a wave
-    int lvCross;    // levels across waves
-};
-
-// sums NV per-thread values over the block by the tree; every thread returns the sums.  `flip` is the block-uniform parity of the
-// LDS buffer: a wave that writes buffer f again has passed the barrier of the sum in between, which every wave reaches only after it
-// has read f.
-template <int NV>
-__device__ __forceinline__ void block_tree(PoseOptShared& S, const TreeShape& T, int& flip, double (&v)[NV])
-{
-    for (int l = 0; l < T.lvWave; l++) {
-#pragma unroll
-        for (int k = 0; k < NV; k++) v[k] = wave_level_add(v[k], l);
-    }
-    if (blockDim.x == 64) {   // lanes past P hold sums of padding only: every lane takes lane 0's
-#pragma unroll
-        for (int k = 0; k < NV; k++)
-            v[k] = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v[k])), __builtin_amdgcn_readfirstlane(__double2loint(v[k])));
-        return;
-    }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    // This barrier sits inside loops (iterations, trials) whose trip counts depend on computed values.  It is reached by all threads
-    // or by none because those values are bit-identical in every thread: each reads the same sums from LDS below and runs the same
-    // contraction-free sequence on them.  Anything that made a thread's copy differ (a per-thread shortcut, a fast-math flag) would
-    // hang the block here.
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < NV; k++) S.part[flip][wave][k] = v[k];
-    }
-    __syncthreads();
-    const int nw = 1 << T.lvCross;   // 1, 2 or 4
-#pragma unroll
-    for (int k = 0; k < NV; k++) {
-        const double a = S.part[flip][0][k];
-        if (nw == 1) v[k] = a;
-        else if (nw == 2) v[k] = a + S.part[flip][1][k];
-        else v[k] = (a + S.part[flip][1][k]) + (S.part[flip][2][k] + S.part[flip][3][k]);
-    }
-    flip ^= 1;
-}
 
 // the frame as one thread sees it: where its run of edges is and how to fetch one
 struct FrameView {
@@ -165,42 +99,6 @@ __device__ __forceinline__ EdgeD load_edge(const PoseOptArgs& G, const FrameView
     E.Y = (double)p[1];
     E.Z = (double)p[2];
     return E;
-}
-
-// The per-thread part of a sum: term(k, v) fills the NV values of the k-th edge of the run (+0.0 when it is inactive or past N_e).
-// RUN = 1, 2, 4: unrolled; RUN = 0: a run of `run` = 2^m > 4 edges walked with a binary counter, so that v(2i) + v(2i + 1) are
-// added first, then pairs of pairs: the same tree.
-template <int RUN, int NV, class Term>
-__device__ __forceinline__ void run_tree(int run, double (&out)[NV], Term term)
-{
-    if (RUN == 1) {
-        term(0, out);
-    } else if (RUN == 2) {
-        double b[NV];
-        term(0, out);
-        term(1, b);
-#pragma unroll
-        for (int k = 0; k < NV; k++) out[k] = out[k] + b[k];
-    } else if (RUN == 4) {
-        double b[NV], c[NV], d[NV];
-        term(0, out);
-        term(1, b);
-        term(2, c);
-        term(3, d);
-#pragma unroll
-        for (int k = 0; k < NV; k++) out[k] = (out[k] + b[k]) + (c[k] + d[k]);
-    } else {
-        double st[kPoseOptStack][NV];
-        for (int i = 0; i < run; i++) {
-            term(i, out);
-            int lvl = 0;
-            for (int m = i; m & 1; m >>= 1, lvl++) {
-                for (int k = 0; k < NV; k++) out[k] = st[lvl][k] + out[k];
-            }
-            if (i + 1 < run)
-                for (int k = 0; k < NV; k++) st[lvl][k] = out[k];
-        }
-    }
 }
 
 template <int RUN>

@@ -43,6 +43,21 @@ ORBFE_HD inline double det3d(const double* a)
     const double c20 = a[3] * a[7] - a[4] * a[6];
     return (a[0] * c00 + a[1] * c10) + a[2] * c20;
 }
+// the inverse of a symmetric 3 x 3 given as its six distinct entries (00 01 02 11 12 22), returned the same way (S17): the six
+// distinct cofactors in the order of S12's adjugate (jacobi.h inv3), the determinant by the first row, one reciprocal
+ORBFE_HD inline void inv3_sym(const double (&a)[6], double (&o)[6])
+{
+    const double c00 = a[3] * a[5] - a[4] * a[4];
+    const double c01 = a[2] * a[4] - a[1] * a[5];
+    const double c02 = a[1] * a[4] - a[2] * a[3];
+    const double c11 = a[0] * a[5] - a[2] * a[2];
+    const double c12 = a[2] * a[1] - a[0] * a[4];
+    const double c22 = a[0] * a[3] - a[1] * a[1];
+    const double det = (a[0] * c00 + a[1] * c01) + a[2] * c02;
+    const double inv = 1.0 / det;
+    o[0] = c00 * inv; o[1] = c01 * inv; o[2] = c02 * inv;
+    o[3] = c11 * inv; o[4] = c12 * inv; o[5] = c22 * inv;
+}
 ORBFE_HD inline void cross3(const double* a, const double* b, double* o)
 {
     o[0] = a[1] * b[2] - a[2] * b[1];

@@ -88,6 +88,16 @@ int pose_opt_batch_device(MatchScratch& m, hipStream_t s, const orbfe_pose_opt_p
                           int batch, const orbfe_keypoint* dKp, const int* dN, int kpStride, const int* dMatch, int nMapPoints,
                           const orbfe_world_point* dPoints, int pointStrideFrames, const float* dPoseIn, float* dPoseOut,
                           uint8_t* dOutlier, int* dNInliers, std::string& err);
+
+// kernels_initial_ba.hip (the bundle adjustment of the initial map, SPEC DECISION S17)
+int initial_ba_check(const orbfe_initial_ba_params* P, const orbfe_initial_ba_info* info, std::string& err);
+int initial_ba_begin(const orbfe_initial_ba_params* P, int nLevels, int n1, const orbfe_keypoint* kp1, int n2, const orbfe_keypoint* kp2,
+                     const int* matches12, const float* points, const float* Rcw2, const float* tcw2, float* TcwOut, float* pointsOut,
+                     orbfe_initial_ba_info* info, std::vector<int>& first, std::string& err);
+int initial_ba_run_host(MatchScratch& m, hipStream_t s, const orbfe_initial_ba_params* P, const float* invLevelSigma2,
+                        const orbfe_keypoint* kp1, const orbfe_keypoint* kp2, const int* matches12, const float* points, const float* Rcw1,
+                        const float* tcw1, const float* Rcw2, const float* tcw2, const std::vector<int>& first, float* TcwOut,
+                        float* pointsOut, orbfe_initial_ba_info* info, std::string& err);
 // kernels_distinct.hip (MapPoint::ComputeDistinctiveDescriptors for a batch)
 int distinctive_run(MatchScratch& m, hipStream_t s, int nSets, const int* setOff, const uint8_t* desc, int* bestIdx,
                     int* bestMedian, std::string& err);

@@ -2584,6 +2584,36 @@ int orbfe_pose_optimization_batch_device(orbfe_handle* h, const orbfe_pose_opt_p
     return rc;
 }
 
+int orbfe_initial_bundle_adjustment(orbfe_handle* h, const orbfe_initial_ba_params* p, int n1, const orbfe_keypoint* kp1, int n2,
+                                    const orbfe_keypoint* kp2, const int* matches12, const float* points, const float* Rcw1,
+                                    const float* tcw1, const float* Rcw2, const float* tcw2, float* Tcw2_out, float* points_out,
+                                    orbfe_initial_ba_info* info)
+{
+    if (!p) return ORBFE_ERR_INVALID_ARG;
+    std::string err;
+    int rc = initial_ba_check(p, info, err);  // struct sizes, unsupported branches and ranges need no handle
+    if (rc == ORBFE_OK && (!h || n1 < 0 || n2 < 0 || !Rcw1 || !tcw1 || !Rcw2 || !tcw2 || !Tcw2_out ||
+                           (n1 > 0 && (!kp1 || !matches12 || !points || !points_out)) || (n2 > 0 && !kp2)))
+        return ORBFE_ERR_INVALID_ARG;
+    if (!h) return rc;
+    std::lock_guard<std::mutex> lk(h->mu);
+    std::vector<int> first;
+    // the other refusals and the return for no match at all read the handle's level count only: the device is not touched
+    if (rc == ORBFE_OK) rc = initial_ba_begin(p, h->nLevels, n1, kp1, n2, kp2, matches12, points, Rcw2, tcw2, Tcw2_out, points_out, info, first, err);
+    if (rc != ORBFE_OK) {
+        h->err = err;
+        return rc;
+    }
+    if (first.empty()) return ORBFE_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    MatchScope scope_(h, h->stream);
+    if (scope_.rc != ORBFE_OK) return scope_.rc;
+    rc = initial_ba_run_host(h->match, h->stream, p, h->invSig2, kp1, kp2, matches12, points, Rcw1, tcw1, Rcw2, tcw2, first, Tcw2_out,
+                             points_out, info, err);
+    if (rc != ORBFE_OK) h->err = err;
+    return rc;
+}
+
 int orbfe_triangulation_select(int n1, const int* raw_match12, const uint8_t* raw_bin, const uint8_t* has_mp1_now,
                                int check_orientation, int* matches12_out, int* n_matches)
 {

@@ -204,6 +204,27 @@ class PoseOptInfo(C.Structure):
 POSE_OPT_EXIT_RAN_ALL, POSE_OPT_EXIT_TRIALS, POSE_OPT_EXIT_RHO_ZERO = 0, 1, 2
 
 
+class InitialBAParams(C.Structure):
+    """orbfe_initial_ba_params: the camera and the constants of Optimizer::GlobalBundleAdjustemnt(map, 20) (src/Optimizer.cc:60-369)."""
+    _fields_ = [("struct_size", C.c_int), ("camera_model", C.c_int), ("cam", C.c_float * 8), ("huber_delta2", C.c_double),
+                ("robust", C.c_int), ("iterations", C.c_int), ("stereo", C.c_int)]
+
+    def __init__(self, cam=(0.0,) * 8, camera_model=0, huber_delta2=5.99, robust=1, iterations=20, stereo=0):
+        super().__init__(C.sizeof(InitialBAParams), int(camera_model), (C.c_float * 8)(*[float(x) for x in cam]), huber_delta2, int(robust),
+                         iterations, stereo)
+
+
+class InitialBAInfo(C.Structure):
+    """orbfe_initial_ba_info: every intermediate of one orbfe_initial_bundle_adjustment call."""
+    _fields_ = [("struct_size", C.c_int), ("N", C.c_int), ("n_iterations", C.c_int), ("n_trials", C.c_int), ("exit_kind", C.c_int),
+                ("trials", C.c_int * 64), ("cost", C.c_double * 64), ("lambda_", C.c_double * 64), ("pose", C.c_double * 12),
+                ("chi2", C.c_void_p), ("depth_positive", C.c_void_p)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(InitialBAInfo)
+
+
 class TrackParams(C.Structure):
     """orbfe_track_params: frame grid statics (src/Frame.cc:101-105) + the call parameters of SearchByProjection."""
     _fields_ = [("struct_size", C.c_int), ("grid_cols", C.c_int), ("grid_rows", C.c_int), ("min_x", C.c_float),
@@ -239,7 +260,7 @@ SYMBOLS = [
     "orbfe_debug_clock_probe", "orbfe_keyframe_set_grid", "orbfe_fuse_search_keyframe", "orbfe_fuse_search_keyframes", "orbfe_fuse_select",
     "orbfe_init_frame_create", "orbfe_init_frame_destroy", "orbfe_init_frame_size", "orbfe_track_initialization",
     "orbfe_set_stream_priority", "orbfe_two_view_reconstruct", "orbfe_mlpnp_plan", "orbfe_mlpnp_ransac",
-    "orbfe_pose_optimization", "orbfe_pose_optimization_batch_device",
+    "orbfe_pose_optimization", "orbfe_pose_optimization_batch_device", "orbfe_initial_bundle_adjustment",
     "orbfe_shard_range", "orbfe_pool_create", "orbfe_pool_destroy", "orbfe_pool_size", "orbfe_pool_member",
     "orbfe_pool_member_frames", "orbfe_pool_last_error", "orbfe_pool_extract", "orbfe_pool_enable_track",
     "orbfe_pool_map_update", "orbfe_pool_track",
@@ -369,6 +390,9 @@ def lib():
         L.orbfe_pose_optimization.argtypes = [vp, C.POINTER(PoseOptParams), ci, vp, vp, ci, vp, vp, vp, vp, vp, C.POINTER(ci),
                                               C.POINTER(PoseOptInfo)]
         L.orbfe_pose_optimization_batch_device.argtypes = [vp, C.POINTER(PoseOptParams), ci, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp]
+    if hasattr(L, "orbfe_initial_bundle_adjustment"):  # (as above)
+        L.orbfe_initial_bundle_adjustment.argtypes = [vp, C.POINTER(InitialBAParams), ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                      C.POINTER(InitialBAInfo)]
     L.orbfe_distinctive_descriptors.argtypes = [vp, ci, vp, vp, vp, vp]
     L.orbfe_vocab_create.argtypes = [vp, ci, vp, vp, vp, vp, vp, ci, C.POINTER(vp)]
     L.orbfe_vocab_destroy.argtypes = [vp]
@@ -1293,6 +1317,42 @@ def pose_optimization_batch_device(extractor, params, batch, d_kp_ptr, d_n_ptr, 
                                                                      int(kp_stride), d_match_ptr, int(n_map_points), d_points_ptr,
                                                                      int(point_stride_frames), d_pose_in_ptr, d_pose_out_ptr, d_outlier_ptr,
                                                                      d_n_inliers_ptr, stream), "orbfe_pose_optimization_batch_device")
+
+
+def initial_bundle_adjustment(extractor, params, kp1, kp2, matches12, points, Rcw1, tcw1, Rcw2, tcw2, want_info=True):
+    """orbfe_initial_bundle_adjustment: the bundle adjustment of the initial map (src/Tracking.cc:698 -> src/Optimizer.cc:60-369), two key
+    frames with the first fixed, mono pinhole, SPEC DECISION S17.  kp1 / kp2: KP_DTYPE arrays (mvKeysUn), matches12 [n1] (an index into
+    kp2 or negative), points [n1, 3] float32 (vIniP3D), Rcw* [9] / tcw* [3] float32 -> dict(Tcw2 [4, 4], points [n1, 3]) plus, with
+    want_info, the fields of orbfe_initial_ba_info as N, iterations, trials, exit, it_cost / it_lambda / it_trials (cut to the
+    iterations that ran), pose [12], chi2 [2, N] and depth_positive [2, N]."""
+    kp1 = np.ascontiguousarray(kp1, KP_DTYPE)
+    kp2 = np.ascontiguousarray(kp2, KP_DTYPE)
+    m12 = np.ascontiguousarray(matches12, np.int32)
+    pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    assert len(m12) == len(kp1) and len(pts) == len(kp1)
+    Ra, ta = np.ascontiguousarray(Rcw1, np.float32).reshape(9), np.ascontiguousarray(tcw1, np.float32).reshape(3)
+    Rb, tb = np.ascontiguousarray(Rcw2, np.float32).reshape(9), np.ascontiguousarray(tcw2, np.float32).reshape(3)
+    n1 = len(kp1)
+    N = int((m12 >= 0).sum())
+    Tcw, out_pts = np.zeros((4, 4), np.float32), np.zeros((max(n1, 1), 3), np.float32)
+    info = None
+    if want_info:
+        info = InitialBAInfo()
+        chi2, front = np.zeros((2, max(N, 1)), np.float64), np.zeros((2, max(N, 1)), np.uint8)
+        info.chi2, info.depth_positive = chi2.ctypes.data, front.ctypes.data
+    h = extractor.h if extractor is not None else None
+    rc = lib().orbfe_initial_bundle_adjustment(h, C.byref(params), n1, _p(kp1), len(kp2), _p(kp2), _p(m12), _p(pts), _p(Ra), _p(ta), _p(Rb),
+                                               _p(tb), _p(Tcw), _p(out_pts), C.byref(info) if want_info else None)
+    if rc != 0:
+        raise OrbfeError(rc, "orbfe_initial_bundle_adjustment", lib().orbfe_last_error(h).decode() if h else "")
+    out = dict(Tcw2=Tcw, points=out_pts[:n1])
+    if want_info:
+        ni, N = info.n_iterations, info.N
+        out.update(N=N, iterations=ni, trials=info.n_trials, exit=info.exit_kind, it_cost=np.array(info.cost, np.float64)[:ni],
+                   it_lambda=np.array(info.lambda_, np.float64)[:ni], it_trials=np.array(info.trials, np.int32)[:ni],
+                   pose=np.array(info.pose, np.float64), chi2=chi2.reshape(-1)[:2 * N].reshape(2, N),
+                   depth_positive=front.reshape(-1)[:2 * N].reshape(2, N))
+    return out
 
 
 def triangulation_select(raw_match12, raw_bin, hasMP1_now, checkOrientation=True):
