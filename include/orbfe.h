@@ -990,7 +990,8 @@ typedef struct orbfe_pose_opt_info {
  * ORBFE_ERR_INVALID_ARG: a wrong struct_size (params or info), a parameter outside its range, an mp_index >= n_points, an octave
  * of a matched keypoint outside the handle's levels, n > 65536.  ORBFE_ERR_UNSUPPORTED: KannalaBrandt8 (its project() mixes
  * atan2f / sqrtf with binary64 while projectJac uses atan2: a binary64 atan2 sequence has to be pinned first), stereo != 0,
- * and the inertial variants are not offered at all (their edges belong to G2oTypes.cc).
+ * Of the inertial variants, PoseInertialOptimizationLastKeyFrame is orbfe_pose_inertial_optimization_last_keyframe below (S19);
+ * PoseInertialOptimizationLastFrame is not offered.
  * NOT the reference's function in three stated respects:
  *   - g2o is an empty submodule in the reference tree: the Levenberg loop (OptimizationAlgorithmLevenberg + LinearSolverDense)
  *     and SE3Quat::exp are restated from the published algorithm and adopted as this project's definition; parity with a g2o
@@ -1016,6 +1017,113 @@ int orbfe_pose_optimization_batch_device(orbfe_handle *h, const orbfe_pose_opt_p
                                          const int *d_n, int kp_stride, const int *d_match, int n_map_points,
                                          const orbfe_world_point *d_points, int point_stride_frames, const float *d_pose_in,
                                          float *d_pose_out, uint8_t *d_outlier, int *d_n_inliers, void *stream);
+
+/* -------------------------------------------------------------------------------------------
+ * Inertial pose optimisation against the last key frame: the line behind orbfe_track_frame once the IMU is initialised
+ * (src/Tracking.cc:952)
+ * ---------------------------------------------------------------------------------------- */
+/* the frame's camera and the constants of Optimizer::PoseInertialOptimizationLastKeyFrame (src/Optimizer.cc:3447-3844); versioned
+ * by struct_size */
+typedef struct orbfe_pose_inertial_params {
+    int struct_size;          /* sizeof(orbfe_pose_inertial_params) at the caller's compile time */
+    int camera_model;         /* ORBFE_CAMERA_PINHOLE; ORBFE_CAMERA_KANNALA_BRANDT8 -> ORBFE_ERR_UNSUPPORTED */
+    float cam[8];             /* fx fy cx cy k1 k2 k3 k4 (mvParameters; only the first four are read) */
+    float chi2[4];            /* chi2Mono[it] (:3658): 12, 7.5, 5.991, 5.991; each >= 0 */
+    double close_factor;      /* chi2close = (float)(1.5 * chi2Mono[it]) (:3686): >= 0 */
+    float close_depth;        /* bClose = mTrackDepth < 10.f (:3701) */
+    float recover_chi2;       /* chi2MonoOut = 24.f (:3768) */
+    int recover_below;        /* the recovery runs when the last round left fewer inliers than this: 30 (:3765) */
+    int iterations;           /* its[it] (:3661), 15 in every round: [1, 64] */
+    int rounds;               /* 4 (:3669): [1, 4]; the Huber kernel is dropped after round index 2 as written (:3717) */
+    int rec_init;             /* bRecInit: != 0 switches the recovery off (:3765) */
+    double huber_delta2;      /* thHuberMono = (float) sqrt(5.991) (:3498): > 0 */
+    float gravity;            /* IMU::GRAVITY_VALUE (include/ImuTypes.h): g = (0, 0, -gravity) */
+    int stereo;               /* 0; anything else (mvuRight >= 0, a second camera, Nleft != -1) -> ORBFE_ERR_UNSUPPORTED */
+} orbfe_pose_inertial_params;
+#define ORBFE_POSE_INERTIAL_PARAMS_INIT {(int)sizeof(orbfe_pose_inertial_params), 0, {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, \
+                                         {12.f, 7.5f, 5.991f, 5.991f}, 1.5, 10.f, 24.f, 30, 15, 4, 0, 5.991, 9.81f, 0}
+
+/* What the fixed vertices of the last key frame contribute, computed by the caller with the reference's own code, and the
+ * camera-body extrinsics.  3 x 3 and 9 x 9 matrices are row-major.  With pInt = pFrame->mpImuPreintegrated, pKF =
+ * pFrame->mpLastKeyFrame and b1 = pKF's bias: dR / dV / dP = pInt->GetDeltaRotation / GetDeltaVelocity / GetDeltaPosition(b1),
+ * dt = pInt->dT, info9 = EdgeInertial(pInt).information() (the inverse of C.block<9,9>(0,0), symmetrised, eigenvalues below 1e-12
+ * clamped to 0: src/G2oTypes.cc:500-508), infoG / infoA = C.block<3,3>(9,9) / (12,12) .cast<double>().inverse() (:3645,:3652). */
+typedef struct orbfe_imu_link {
+    int struct_size;          /* sizeof(orbfe_imu_link) at the caller's compile time */
+    int reserved;             /* 0 */
+    float Rwb1[9], twb1[3];   /* pKF->GetImuRotation(), GetImuPosition() */
+    float v1[3];              /* pKF->GetVelocity() */
+    float bg1[3], ba1[3];     /* pKF->GetGyroBias(), GetAccBias() */
+    float dR[9], dV[3], dP[3];
+    float dt;
+    float Rcb[9], tcb[3];     /* mImuCalib.mTcb */
+    float tbc[3];             /* mImuCalib.mTbc.translation() */
+    double info9[81];
+    double infoG[9], infoA[9];
+} orbfe_imu_link;
+
+/* every intermediate of one orbfe_pose_inertial_optimization_last_keyframe call (optional: info may be NULL).  Edge c is the c-th
+ * keypoint i with mp_index[i] >= 0; a state is Rwb (9, row-major), twb, v, bg, ba in binary64.  Entries of rounds that did not run
+ * are zero. */
+typedef struct orbfe_pose_inertial_info {
+    int struct_size;          /* sizeof(orbfe_pose_inertial_info) at the caller's compile time */
+    int N_e;
+    int rounds_run;
+    int recovered;            /* 1: the recovery (:3765-3792) ran */
+    int iterations[4];        /* Gauss-Newton iterations started in the round */
+    int ok[4];                /* 0: the round ended on a solve whose pivots were not all positive (the state of before it is kept) */
+    int n_bad[4];             /* nBad after the round */
+    double state[4][21];      /* the round's final state */
+    uint8_t *outlier;         /* [4][N_e], caller-owned, may be NULL: the flags after each round, by edge */
+} orbfe_pose_inertial_info;
+
+/* replaces Optimizer::PoseInertialOptimizationLastKeyFrame(pFrame, bRecInit) (src/Optimizer.cc:3447-3844; the call:
+ * src/Tracking.cc:952) for the branch this fork takes: one pinhole camera, EdgeMonoOnlyPose edges, one EdgeInertial, EdgeGyroRW,
+ * EdgeAccRW; 15 unknowns (pose rotation, pose translation, velocity, gyro bias, accelerometer bias).  Numerics: SPEC DECISION S19
+ * (DESIGN.md section 2); tests/pose_inertial_ref.py is the normative restatement and the call equals it byte for byte.
+ * kp (n) = mvKeysUn (x, y, octave are read; the handle's mvInvLevelSigma2 is the information); mp_index[i] = the row of `points`
+ * (x y z floats, n_points rows) and of track_depth (mTrackDepth, n_points floats) of the map point matched to keypoint i, or -1.
+ * Rcw (9) / tcw (3) = pFrame->GetPose(); Rwb / twb / v = GetImuRotation / GetImuPosition / GetVelocity; bg / ba = mImuBias.
+ * Rwb_out .. ba_out: what the reference hands to SetImuPoseVelocity and mImuBias, as floats; H_out (225 doubles, row-major) = the
+ * H it hands to new ConstraintPoseImu(..., H), raw: the eigenvalue clamp of that constructor stays with the caller.  outlier_out
+ * (n) = mvbOutlier; *n_inliers = the return value (nInitialCorrespondences - nBad).  No matched keypoint at all is valid: the
+ * inertial edges alone give a full-rank system (the reference has no early return).
+ * The whole call -- four rounds, every iteration, the scoring, the recovery and the Hessian -- is ONE kernel launch of one block;
+ * one submission, one synchronisation.  HOST pointers.
+ * ORBFE_ERR_INVALID_ARG: a wrong struct_size (params, link or info), a parameter outside its range, an mp_index >= n_points, an
+ * octave of a matched keypoint outside the handle's levels, n > 65536; decided from the arguments and the handle's level count
+ * before the device is touched.  ORBFE_ERR_UNSUPPORTED: KannalaBrandt8 (S14's reason), stereo != 0.
+ * PoseInertialOptimizationLastFrame (src/Tracking.cc:946) is not offered: it needs 30 unknowns, the EdgePriorPoseImu prior and
+ * Optimizer::Marginalize; H_out is the 15 x 15 Hessian its prior is made from.
+ * NOT the reference's function in these stated respects:
+ *   - g2o is an empty submodule in the reference tree: OptimizationAlgorithmGaussNewton + LinearSolverDense are restated from the
+ *     published algorithm; parity with a g2o build is unpinned, as in S14 and S17;
+ *   - NormalizeRotation (an SVD, in ExpSO3 and in every third Update) is not applied: Rwb drifts from orthonormal by rounding
+ *     only (measured: tests/test_pose_inertial.py);
+ *   - the flags are scored on fresh errors at the round's final state; g2o's active edges hold the errors of before the last update;
+ *   - the input state takes no quaternion or Sophus round trip. */
+int orbfe_pose_inertial_optimization_last_keyframe(orbfe_handle *h, const orbfe_pose_inertial_params *p, const orbfe_imu_link *link,
+                                                   int n, const orbfe_keypoint *kp, const int *mp_index, int n_points,
+                                                   const float *points, const float *track_depth, const float *Rcw, const float *tcw,
+                                                   const float *Rwb, const float *twb, const float *v, const float *bg, const float *ba,
+                                                   float *Rwb_out, float *twb_out, float *v_out, float *bg_out, float *ba_out,
+                                                   double *H_out, uint8_t *outlier_out, int *n_inliers,
+                                                   orbfe_pose_inertial_info *info);
+
+/* Batched, HBM-resident form: grid = batch, one block per frame, one orbfe_imu_link (d_links[b]) and one state per frame.  Keypoints,
+ * counts, matches and points are laid out as for orbfe_pose_optimization_batch_device; d_track_depth holds one float per point
+ * record with the same frame stride (d_track_depth[b * point_stride_frames ..]; point_stride_frames == 0: shared).  d_state_in: 33
+ * floats per frame -- Rcw (9), tcw (3), Rwb (9), twb, v, bg, ba; d_state_out: 21 floats per frame -- Rwb, twb, v, bg, ba; d_H_out:
+ * 225 doubles per frame.  A match outside [0, n_map_points) or on a keypoint whose octave is outside the handle's levels is no edge.
+ * DEVICE pointers; asynchronous on `stream` (NULL == the handle's stream): one launch, no host synchronisation.  Frame b's results
+ * are byte-equal to orbfe_pose_inertial_optimization_last_keyframe on the same data.  d_links[b].struct_size cannot be checked by
+ * a device call. */
+int orbfe_pose_inertial_optimization_batch_device(orbfe_handle *h, const orbfe_pose_inertial_params *p, int batch,
+                                                  const orbfe_imu_link *d_links, const orbfe_keypoint *d_kp, const int *d_n,
+                                                  int kp_stride, const int *d_match, int n_map_points,
+                                                  const orbfe_world_point *d_points, int point_stride_frames,
+                                                  const float *d_track_depth, const float *d_state_in, float *d_state_out,
+                                                  double *d_H_out, uint8_t *d_outlier, int *d_n_inliers, void *stream);
 
 /* -------------------------------------------------------------------------------------------
  * Bundle adjustment of the initial map: the line behind orbfe_two_view_reconstruct (src/Tracking.cc:698)

@@ -1572,7 +1572,8 @@ private:
 // Optimizer::PoseOptimization(pFrame) (src/Optimizer.cc:765-1067) as ONE call (orbfe_pose_optimization): the line behind the MLPnP
 // solve in Tracking::TrackReferenceKeyFrame (src/Tracking.cc:869) and behind SearchLocalPoints in TrackLocalMap (:935).  It is NOT
 // named Optimizer: unlike the classes above it replaces one function, not a class -- Tracking.cc keeps including Optimizer.h for
-// GlobalBundleAdjustemnt (:698) and the PoseInertialOptimization* calls (:946, :952), so ORB_SLAM3::Optimizer stays the reference's.
+// GlobalBundleAdjustemnt (:698) and PoseInertialOptimizationLastFrame (:946), so ORB_SLAM3::Optimizer stays the reference's
+// (PoseInertialOptimizationLastKeyFrame, :952, is the second wrapper below).
 // `F` needs mNumKeypoints, mvKeysUn (shared_ptr<vector<KeyPoint>>), mvpMapPoints (entries with GetWorldPos()[0..2]), mvbOutlier,
 // mvuRight and mpCamera2; getPose(F, Rcw[9], tcw[3]) reads pFrame->GetPose() row-major, setPose(F, Tcw[16]) is pFrame->SetPose
 // (:1062-1065).  It fills mp_index / points from mvpMapPoints, writes mvbOutlier, sets the pose and returns
@@ -1618,6 +1619,57 @@ struct PoseOptimizer {
             if (mpIndex[(size_t)i] >= 0) pFrame->mvbOutlier[(size_t)i] = outlier[(size_t)i] != 0;  // (:822: false when nothing ran)
         if ((int)(points.size() / 3) < 3) return 0;  // (:949-950: the pose is not touched)
         setPose(pFrame, Tcw.data());
+        return nInliers;
+    }
+
+    // Optimizer::PoseInertialOptimizationLastKeyFrame(pFrame, bRecInit) (src/Optimizer.cc:3447-3844; the call: src/Tracking.cc:952) as
+    // ONE call (orbfe_pose_inertial_optimization_last_keyframe, SPEC DECISION S19).  `link` holds what the fixed key-frame vertices
+    // contribute, computed by the caller with the reference's own code (which calls produce dR / dV / dP / info9 /
+    // infoG / infoA), and the extrinsics.  `F` needs what PoseOptimization needs, and its map points mTrackDepth.
+    // getState(F, s[33]) fills Rcw (9), tcw (3) = GetPose(), Rwb (9), twb, v = GetImuRotation / GetImuPosition / GetVelocity, bg, ba =
+    // mImuBias; setState(F, s[21], H) receives Rwb, twb, v (SetImuPoseVelocity), bg, ba (mImuBias) and the raw 15 x 15 row-major H
+    // for new ConstraintPoseImu(Rwb, twb, v, bg, ba, H) (:3795-3839).  It writes mvbOutlier and returns nInitialCorrespondences - nBad.
+    // The stated departures are those of include/orbfe.h (no NormalizeRotation, fresh errors at the end of a round, no quaternion round
+    // trip, g2o's Gauss-Newton restated).
+    template <class FramePtr, class GetState, class SetState>
+    static int PoseInertialOptimizationLastKeyFrame(ORBextractor& extractor, FramePtr pFrame, bool bRecInit, int cameraModel,
+                                                    const std::array<float, 8>& cameraParameters, const orbfe_imu_link& link,
+                                                    GetState getState, SetState setState, orbfe_pose_inertial_info* info = nullptr)
+    {
+        orbfe_pose_inertial_params p = ORBFE_POSE_INERTIAL_PARAMS_INIT;
+        p.camera_model = cameraModel;
+        p.rec_init = bRecInit ? 1 : 0;
+        for (int i = 0; i < 8; i++) p.cam[i] = cameraParameters[(size_t)i];
+        if (pFrame->mpCamera2) p.stereo = 1;
+        const int n = pFrame->mNumKeypoints;
+        std::vector<int> mpIndex((size_t)(n > 0 ? n : 1), -1);
+        std::vector<float> points, depth;
+        for (int i = 0; i < n; i++) {
+            auto pMP = pFrame->mvpMapPoints[(size_t)i];
+            if (!pMP) continue;
+            if (pFrame->mvuRight[(size_t)i] >= 0) p.stereo = 1;
+            const auto P = pMP->GetWorldPos();
+            mpIndex[(size_t)i] = (int)depth.size();
+            points.push_back(P[0]);
+            points.push_back(P[1]);
+            points.push_back(P[2]);
+            depth.push_back(pMP->mTrackDepth);
+        }
+        float s[33], o[21];
+        getState(pFrame, s);
+        std::array<double, 225> H;
+        std::vector<uint8_t> outlier((size_t)(n > 0 ? n : 1));
+        int nInliers = 0;
+        orbfe_handle* h = extractor.handle();
+        orbfe_detail::check(orbfe_pose_inertial_optimization_last_keyframe(
+                                h, &p, &link, n, reinterpret_cast<const orbfe_keypoint*>(pFrame->mvKeysUn->data()), mpIndex.data(),
+                                (int)depth.size(), points.empty() ? nullptr : points.data(), depth.empty() ? nullptr : depth.data(), s, s + 9,
+                                s + 12, s + 21, s + 24, s + 27, s + 30, o, o + 9, o + 12, o + 15, o + 18, H.data(), outlier.data(), &nInliers,
+                                info),
+                            h, "orbfe_pose_inertial_optimization_last_keyframe");
+        for (int i = 0; i < n; i++)
+            if (mpIndex[(size_t)i] >= 0) pFrame->mvbOutlier[(size_t)i] = outlier[(size_t)i] != 0;
+        setState(pFrame, o, H.data());
         return nInliers;
     }
 };

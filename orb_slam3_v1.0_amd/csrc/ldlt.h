@@ -109,4 +109,74 @@ ORBFE_HD inline void ldlt_solve6(double (&A)[6][6], const double (&b)[6], double
     }
 }
 
+// The indexed form of exactly the arithmetic and pivot rule above, for any N (S19: the 15 x 15 Gauss-Newton step of
+// PoseInertialOptimizationLastKeyFrame).  One thread, run-time indices: the host loops and the restatements read this; a kernel
+// maps the same operations onto a wave (kernels_poseimu.hip) or, for N = 6, uses ldlt_solve6.
+template <int N>
+ORBFE_HD inline void ldlt_solve_n(double (&A)[N][N], const double (&b)[N], double (&x)[N], bool* positive = nullptr)
+{
+    double L[N][N], d[N];
+    int perm[N];
+    for (int i = 0; i < N; i++) {
+        perm[i] = i;
+        for (int j = 0; j < N; j++) L[i][j] = 0.0;
+    }
+    for (int k = 0; k < N; k++) {
+        int best = k;
+        double bestAbs = fabs(A[k][k]);
+        for (int i = k + 1; i < N; i++) {
+            const double v = fabs(A[i][i]);
+            if (v > bestAbs) { best = i; bestAbs = v; }
+        }
+        if (best != k) {
+            for (int j = 0; j < N; j++) {
+                const double a = A[k][j], l = L[k][j];
+                A[k][j] = A[best][j];
+                A[best][j] = a;
+                L[k][j] = L[best][j];
+                L[best][j] = l;
+            }
+            const int p = perm[k];
+            perm[k] = perm[best];
+            perm[best] = p;
+            for (int r = 0; r < N; r++) {
+                const double a = A[r][k];
+                A[r][k] = A[r][best];
+                A[r][best] = a;
+            }
+        }
+        const double dk = A[k][k];
+        d[k] = dk;
+        double col[N];
+        for (int i = 0; i < N; i++) col[i] = A[i][k];
+        for (int i = k + 1; i < N; i++) {
+            const double li = dk == 0.0 ? 0.0 : col[i] / dk;
+            L[i][k] = li;
+            for (int j = k + 1; j <= i; j++) {
+                const double val = A[i][j] - li * col[j];
+                A[i][j] = val;
+                A[j][i] = val;
+            }
+        }
+    }
+    double z[N], w[N], xs[N];
+    for (int i = 0; i < N; i++) {
+        double acc = b[perm[i]];
+        for (int j = 0; j < i; j++) acc = acc - L[i][j] * z[j];
+        z[i] = acc;
+    }
+    for (int i = 0; i < N; i++) w[i] = d[i] == 0.0 ? 0.0 : z[i] / d[i];
+    for (int i = N - 1; i >= 0; i--) {
+        double acc = w[i];
+        for (int j = i + 1; j < N; j++) acc = acc - L[j][i] * xs[j];
+        xs[i] = acc;
+    }
+    for (int i = 0; i < N; i++) x[perm[i]] = xs[i];
+    if (positive) {
+        bool pos = true;
+        for (int i = 0; i < N; i++) pos = pos && d[i] > 0.0;
+        *positive = pos;
+    }
+}
+
 }  // namespace orbfe

@@ -88,6 +88,19 @@ int pose_opt_batch_device(MatchScratch& m, hipStream_t s, const orbfe_pose_opt_p
                           int batch, const orbfe_keypoint* dKp, const int* dN, int kpStride, const int* dMatch, int nMapPoints,
                           const orbfe_world_point* dPoints, int pointStrideFrames, const float* dPoseIn, float* dPoseOut,
                           uint8_t* dOutlier, int* dNInliers, std::string& err);
+// kernels_poseimu.hip (Optimizer::PoseInertialOptimizationLastKeyFrame, SPEC DECISION S19)
+int pose_imu_check(const orbfe_pose_inertial_params* P, const orbfe_imu_link* link, const orbfe_pose_inertial_info* info, std::string& err);
+int pose_imu_begin(const orbfe_pose_inertial_params* P, const orbfe_imu_link* link, int nLevels, int n, const orbfe_keypoint* kp,
+                   const int* mpIndex, int nPoints, orbfe_pose_inertial_info* info, std::vector<int>& first, std::string& err);
+int pose_imu_run(MatchScratch& m, hipStream_t s, const orbfe_pose_inertial_params* P, const orbfe_imu_link* link,
+                 const float* invLevelSigma2, int nLevels, int n, const orbfe_keypoint* kp, const int* mpIndex, const float* points,
+                 const float* trackDepth, const float* stateIn, const std::vector<int>& first, float* stateOut, double* Hout,
+                 uint8_t* outlier, int* nInliers, orbfe_pose_inertial_info* info, std::string& err);
+int pose_imu_batch_device(MatchScratch& m, hipStream_t s, const orbfe_pose_inertial_params* P, const float* invLevelSigma2, int nLevels,
+                          int batch, const orbfe_imu_link* dLinks, const orbfe_keypoint* dKp, const int* dN, int kpStride,
+                          const int* dMatch, int nMapPoints, const orbfe_world_point* dPoints, int pointStrideFrames,
+                          const float* dTrackDepth, const float* dStateIn, float* dStateOut, double* dHout, uint8_t* dOutlier,
+                          int* dNInliers, std::string& err);
 
 // kernels_initial_ba.hip (the bundle adjustment of the initial map, SPEC DECISION S17)
 int initial_ba_check(const orbfe_initial_ba_params* P, const orbfe_initial_ba_info* info, std::string& err);

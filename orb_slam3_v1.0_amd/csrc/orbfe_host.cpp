@@ -2584,6 +2584,87 @@ int orbfe_pose_optimization_batch_device(orbfe_handle* h, const orbfe_pose_opt_p
     return rc;
 }
 
+int orbfe_pose_inertial_optimization_last_keyframe(orbfe_handle* h, const orbfe_pose_inertial_params* p, const orbfe_imu_link* link,
+                                                   int n, const orbfe_keypoint* kp, const int* mp_index, int n_points,
+                                                   const float* points, const float* track_depth, const float* Rcw, const float* tcw,
+                                                   const float* Rwb, const float* twb, const float* v, const float* bg, const float* ba,
+                                                   float* Rwb_out, float* twb_out, float* v_out, float* bg_out, float* ba_out,
+                                                   double* H_out, uint8_t* outlier_out, int* n_inliers, orbfe_pose_inertial_info* info)
+{
+    if (!p) return ORBFE_ERR_INVALID_ARG;
+    std::string err;
+    int rc = pose_imu_check(p, link, info, err);  // struct sizes, unsupported branches and ranges need no handle
+    if (rc == ORBFE_OK && (!h || !link || n < 0 || n_points < 0 || !Rcw || !tcw || !Rwb || !twb || !v || !bg || !ba || !Rwb_out ||
+                           !twb_out || !v_out || !bg_out || !ba_out || !H_out || !n_inliers ||
+                           (n > 0 && (!kp || !mp_index || !outlier_out)) || (n_points > 0 && (!points || !track_depth))))
+        return ORBFE_ERR_INVALID_ARG;
+    if (!h) return rc;
+    std::lock_guard<std::mutex> lk(h->mu);
+    std::vector<int> first;
+    // the other refusals read the handle's level count only: the device is not touched
+    if (rc == ORBFE_OK) rc = pose_imu_begin(p, link, h->nLevels, n, kp, mp_index, n_points, info, first, err);
+    if (rc != ORBFE_OK) {
+        h->err = err;
+        return rc;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    MatchScope scope_(h, h->stream);
+    if (scope_.rc != ORBFE_OK) return scope_.rc;
+    float in[33], out[21];
+    memcpy(in, Rcw, 9 * sizeof(float));
+    memcpy(in + 9, tcw, 3 * sizeof(float));
+    memcpy(in + 12, Rwb, 9 * sizeof(float));
+    memcpy(in + 21, twb, 3 * sizeof(float));
+    memcpy(in + 24, v, 3 * sizeof(float));
+    memcpy(in + 27, bg, 3 * sizeof(float));
+    memcpy(in + 30, ba, 3 * sizeof(float));
+    rc = pose_imu_run(h->match, h->stream, p, link, h->invSig2, h->nLevels, n, kp, mp_index, points, track_depth, in, first, out, H_out,
+                      outlier_out, n_inliers, info, err);
+    if (rc != ORBFE_OK) {
+        h->err = err;
+        return rc;
+    }
+    memcpy(Rwb_out, out, 9 * sizeof(float));
+    memcpy(twb_out, out + 9, 3 * sizeof(float));
+    memcpy(v_out, out + 12, 3 * sizeof(float));
+    memcpy(bg_out, out + 15, 3 * sizeof(float));
+    memcpy(ba_out, out + 18, 3 * sizeof(float));
+    return rc;
+}
+
+int orbfe_pose_inertial_optimization_batch_device(orbfe_handle* h, const orbfe_pose_inertial_params* p, int batch,
+                                                  const orbfe_imu_link* d_links, const orbfe_keypoint* d_kp, const int* d_n,
+                                                  int kp_stride, const int* d_match, int n_map_points,
+                                                  const orbfe_world_point* d_points, int point_stride_frames,
+                                                  const float* d_track_depth, const float* d_state_in, float* d_state_out,
+                                                  double* d_H_out, uint8_t* d_outlier, int* d_n_inliers, void* stream_)
+{
+    if (!p) return ORBFE_ERR_INVALID_ARG;
+    std::string err;
+    const int crc = pose_imu_check(p, nullptr, nullptr, err);
+    if (crc != ORBFE_OK) {
+        if (h) {
+            std::lock_guard<std::mutex> lk(h->mu);
+            h->err = err;
+        }
+        return crc;
+    }
+    if (!h || batch < 1 || !d_links || !d_kp || !d_n || kp_stride < 1 || !d_match || n_map_points < 0 ||
+        (n_map_points > 0 && (!d_points || !d_track_depth)) || point_stride_frames < 0 || !d_state_in || !d_state_out || !d_H_out ||
+        !d_outlier || !d_n_inliers)
+        return ORBFE_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = stream_ ? (hipStream_t)stream_ : h->stream;
+    MatchScope scope_(h, s);
+    if (scope_.rc != ORBFE_OK) return scope_.rc;
+    const int rc = pose_imu_batch_device(h->match, s, p, h->invSig2, h->nLevels, batch, d_links, d_kp, d_n, kp_stride, d_match, n_map_points,
+                                         d_points, point_stride_frames, d_track_depth, d_state_in, d_state_out, d_H_out, d_outlier,
+                                         d_n_inliers, err);
+    if (rc != ORBFE_OK) h->err = err;
+    return rc;
+}
+
 int orbfe_initial_bundle_adjustment(orbfe_handle* h, const orbfe_initial_ba_params* p, int n1, const orbfe_keypoint* kp1, int n2,
                                     const orbfe_keypoint* kp2, const int* matches12, const float* points, const float* Rcw1,
                                     const float* tcw1, const float* Rcw2, const float* tcw2, float* Tcw2_out, float* points_out,

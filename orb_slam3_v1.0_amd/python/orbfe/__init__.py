@@ -204,6 +204,51 @@ class PoseOptInfo(C.Structure):
 POSE_OPT_EXIT_RAN_ALL, POSE_OPT_EXIT_TRIALS, POSE_OPT_EXIT_RHO_ZERO = 0, 1, 2
 
 
+class PoseInertialParams(C.Structure):
+    """orbfe_pose_inertial_params: the frame's camera and the constants of Optimizer::PoseInertialOptimizationLastKeyFrame
+    (src/Optimizer.cc:3447-3844)."""
+    _fields_ = [("struct_size", C.c_int), ("camera_model", C.c_int), ("cam", C.c_float * 8), ("chi2", C.c_float * 4),
+                ("close_factor", C.c_double), ("close_depth", C.c_float), ("recover_chi2", C.c_float), ("recover_below", C.c_int),
+                ("iterations", C.c_int), ("rounds", C.c_int), ("rec_init", C.c_int), ("huber_delta2", C.c_double), ("gravity", C.c_float),
+                ("stereo", C.c_int)]
+
+    def __init__(self, cam=(0.0,) * 8, camera_model=0, chi2=(12.0, 7.5, 5.991, 5.991), close_factor=1.5, close_depth=10.0,
+                 recover_chi2=24.0, recover_below=30, iterations=15, rounds=4, rec_init=0, huber_delta2=5.991, gravity=9.81, stereo=0):
+        super().__init__(C.sizeof(PoseInertialParams), int(camera_model), (C.c_float * 8)(*[float(x) for x in cam]),
+                         (C.c_float * 4)(*[float(x) for x in chi2]), close_factor, close_depth, recover_chi2, int(recover_below),
+                         int(iterations), int(rounds), int(rec_init), huber_delta2, gravity, int(stereo))
+
+
+class ImuLink(C.Structure):
+    """orbfe_imu_link: the fixed last key frame's state, the preintegrated constants and informations the caller computes with the
+    reference's code, and the camera-body extrinsics.  Built from a dict of arrays named like the fields."""
+    _fields_ = [("struct_size", C.c_int), ("reserved", C.c_int), ("Rwb1", C.c_float * 9), ("twb1", C.c_float * 3), ("v1", C.c_float * 3),
+                ("bg1", C.c_float * 3), ("ba1", C.c_float * 3), ("dR", C.c_float * 9), ("dV", C.c_float * 3), ("dP", C.c_float * 3),
+                ("dt", C.c_float), ("Rcb", C.c_float * 9), ("tcb", C.c_float * 3), ("tbc", C.c_float * 3), ("info9", C.c_double * 81),
+                ("infoG", C.c_double * 9), ("infoA", C.c_double * 9)]
+
+    def __init__(self, link=None):
+        super().__init__()
+        self.struct_size = C.sizeof(ImuLink)
+        if link is None:
+            return
+        for name, ctype in self._fields_[2:]:
+            if name == "dt":
+                self.dt = float(link[name])
+            else:
+                setattr(self, name, ctype(*[float(x) for x in np.asarray(link[name]).reshape(-1)]))
+
+
+class PoseInertialInfo(C.Structure):
+    """orbfe_pose_inertial_info: every intermediate of one orbfe_pose_inertial_optimization_last_keyframe call."""
+    _fields_ = [("struct_size", C.c_int), ("N_e", C.c_int), ("rounds_run", C.c_int), ("recovered", C.c_int), ("iterations", C.c_int * 4),
+                ("ok", C.c_int * 4), ("n_bad", C.c_int * 4), ("state", (C.c_double * 21) * 4), ("outlier", C.c_void_p)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(PoseInertialInfo)
+
+
 class InitialBAParams(C.Structure):
     """orbfe_initial_ba_params: the camera and the constants of Optimizer::GlobalBundleAdjustemnt(map, 20) (src/Optimizer.cc:60-369)."""
     _fields_ = [("struct_size", C.c_int), ("camera_model", C.c_int), ("cam", C.c_float * 8), ("huber_delta2", C.c_double),
@@ -261,6 +306,7 @@ SYMBOLS = [
     "orbfe_init_frame_create", "orbfe_init_frame_destroy", "orbfe_init_frame_size", "orbfe_track_initialization",
     "orbfe_set_stream_priority", "orbfe_two_view_reconstruct", "orbfe_mlpnp_plan", "orbfe_mlpnp_ransac",
     "orbfe_pose_optimization", "orbfe_pose_optimization_batch_device", "orbfe_initial_bundle_adjustment",
+    "orbfe_pose_inertial_optimization_last_keyframe", "orbfe_pose_inertial_optimization_batch_device",
     "orbfe_shard_range", "orbfe_pool_create", "orbfe_pool_destroy", "orbfe_pool_size", "orbfe_pool_member",
     "orbfe_pool_member_frames", "orbfe_pool_last_error", "orbfe_pool_extract", "orbfe_pool_enable_track",
     "orbfe_pool_map_update", "orbfe_pool_track",
@@ -390,6 +436,11 @@ def lib():
         L.orbfe_pose_optimization.argtypes = [vp, C.POINTER(PoseOptParams), ci, vp, vp, ci, vp, vp, vp, vp, vp, C.POINTER(ci),
                                               C.POINTER(PoseOptInfo)]
         L.orbfe_pose_optimization_batch_device.argtypes = [vp, C.POINTER(PoseOptParams), ci, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp]
+    if hasattr(L, "orbfe_pose_inertial_optimization_last_keyframe"):  # (as above)
+        L.orbfe_pose_inertial_optimization_last_keyframe.argtypes = [vp, C.POINTER(PoseInertialParams), C.POINTER(ImuLink), ci, vp, vp, ci] + \
+            [vp] * 16 + [C.POINTER(ci), C.POINTER(PoseInertialInfo)]
+        L.orbfe_pose_inertial_optimization_batch_device.argtypes = [vp, C.POINTER(PoseInertialParams), ci, vp, vp, vp, ci, vp, ci, vp, ci, vp,
+                                                                    vp, vp, vp, vp, vp, vp]
     if hasattr(L, "orbfe_initial_bundle_adjustment"):  # (as above)
         L.orbfe_initial_bundle_adjustment.argtypes = [vp, C.POINTER(InitialBAParams), ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                                       C.POINTER(InitialBAInfo)]
@@ -1317,6 +1368,59 @@ def pose_optimization_batch_device(extractor, params, batch, d_kp_ptr, d_n_ptr, 
                                                                      int(kp_stride), d_match_ptr, int(n_map_points), d_points_ptr,
                                                                      int(point_stride_frames), d_pose_in_ptr, d_pose_out_ptr, d_outlier_ptr,
                                                                      d_n_inliers_ptr, stream), "orbfe_pose_optimization_batch_device")
+
+
+def pose_inertial_optimization_last_keyframe(extractor, params, link, kp, mp_index, points, track_depth, Rcw, tcw, Rwb, twb, v, bg, ba,
+                                             want_info=True):
+    """orbfe_pose_inertial_optimization_last_keyframe: Optimizer::PoseInertialOptimizationLastKeyFrame (src/Optimizer.cc:3447-3844), mono
+    pinhole, SPEC DECISION S19.  link: an ImuLink or a dict of its fields; kp: KP_DTYPE array (mvKeysUn), mp_index [n] (row of points /
+    track_depth or -1), points [m, 3] and track_depth [m] float32; Rcw .. ba: the frame's state, float32 -> dict(Rwb [9], twb, v, bg,
+    ba float32, H [15, 15] float64, outlier [n], n_inliers) plus, with want_info, the fields of orbfe_pose_inertial_info as N_e,
+    rounds_run, recovered and round_iterations / round_ok / round_nbad / round_state / round_outlier, cut to the rounds that ran."""
+    kp = np.ascontiguousarray(kp, KP_DTYPE)
+    mi = np.ascontiguousarray(mp_index, np.int32)
+    assert len(mi) == len(kp)
+    pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    dep = np.ascontiguousarray(track_depth, np.float32).reshape(-1)
+    assert len(dep) == len(pts)
+    if link is not None and not isinstance(link, ImuLink):
+        link = ImuLink(link)
+    sin = [np.ascontiguousarray(a, np.float32).reshape(k) for a, k in ((Rcw, 9), (tcw, 3), (Rwb, 9), (twb, 3), (v, 3), (bg, 3), (ba, 3))]
+    sout = [np.zeros(k, np.float32) for k in (9, 3, 3, 3, 3)]
+    n = len(kp)
+    Ne = int((mi >= 0).sum())
+    H, outl = np.zeros((15, 15), np.float64), np.zeros(max(n, 1), np.uint8)
+    n_inl = C.c_int(0)
+    info = None
+    if want_info:
+        info = PoseInertialInfo()
+        rbuf = np.zeros(4 * max(Ne, 1), np.uint8)
+        info.outlier = rbuf.ctypes.data
+    h = extractor.h if extractor is not None else None
+    rc = lib().orbfe_pose_inertial_optimization_last_keyframe(h, C.byref(params), C.byref(link) if link is not None else None, n, _p(kp),
+                                                              _p(mi), len(pts), _p(pts), _p(dep), *[_p(a) for a in sin],
+                                                              *[_p(a) for a in sout], _p(H), _p(outl), C.byref(n_inl),
+                                                              C.byref(info) if want_info else None)
+    if rc != 0:
+        raise OrbfeError(rc, "orbfe_pose_inertial_optimization_last_keyframe", lib().orbfe_last_error(h).decode() if h else "")
+    out = dict(Rwb=sout[0], twb=sout[1], v=sout[2], bg=sout[3], ba=sout[4], H=H, outlier=outl[:n], n_inliers=n_inl.value)
+    if want_info:
+        nr, Ne = info.rounds_run, info.N_e
+        out.update(N_e=Ne, rounds_run=nr, recovered=info.recovered, round_iterations=np.array(info.iterations, np.int32)[:nr],
+                   round_ok=np.array(info.ok, np.int32)[:nr], round_nbad=np.array(info.n_bad, np.int32)[:nr],
+                   round_state=np.array(info.state, np.float64).reshape(4, 21)[:nr], round_outlier=rbuf[:nr * Ne].reshape(nr, Ne))
+    return out
+
+
+def pose_inertial_optimization_batch_device(extractor, params, batch, d_links_ptr, d_kp_ptr, d_n_ptr, kp_stride, d_match_ptr, n_map_points,
+                                            d_points_ptr, point_stride_frames, d_track_depth_ptr, d_state_in_ptr, d_state_out_ptr,
+                                            d_H_out_ptr, d_outlier_ptr, d_n_inliers_ptr, stream=None):
+    """orbfe_pose_inertial_optimization_batch_device: one block per frame, one orbfe_imu_link and one state per frame, everything
+    resident in HBM (raw device pointers as ints); asynchronous on `stream`."""
+    extractor._chk(extractor.L.orbfe_pose_inertial_optimization_batch_device(
+        extractor.h, C.byref(params), int(batch), d_links_ptr, d_kp_ptr, d_n_ptr, int(kp_stride), d_match_ptr, int(n_map_points), d_points_ptr,
+        int(point_stride_frames), d_track_depth_ptr, d_state_in_ptr, d_state_out_ptr, d_H_out_ptr, d_outlier_ptr, d_n_inliers_ptr, stream),
+        "orbfe_pose_inertial_optimization_batch_device")
 
 
 def initial_bundle_adjustment(extractor, params, kp1, kp2, matches12, points, Rcw1, tcw1, Rcw2, tcw2, want_info=True):

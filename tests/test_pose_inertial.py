@@ -1,0 +1,177 @@
+"""The restatement of SPEC DECISION S19 (pose_inertial_ref.py) on the CPU: which branches the scenes of pose_inertial_scenarios reach,
+the stated departure 1 (no NormalizeRotation) as a figure, and the restatement against an independent solver --
+scipy.optimize.least_squares on the same 15 unknowns, written here with scipy's Rotation and plain numpy, nothing shared with the
+restatement.  Residuals are whitened by the Cholesky factors of info9 / infoG / infoA and by sqrt(w).  Round 0 is compared with
+loss='huber' (f_scale = delta) from the same start, round 3 with loss='linear' on round 2's inlier set from round 2's state.
+scipy's Huber acts per residual component and on the inertial residuals too, g2o's per mono edge only; the two agree where no residual
+is beyond delta at the optimum, which the small-noise scenes are built for.
+
+Nobody had measured these distances.  Protocol (S14's and S17's): the figures of seeds 0 and 1 were measured, each gate is twice the
+worst of them, and seeds 2 and 3 must hold them too (the table is at GATES and in DESIGN.md S19)."""
+import collections
+
+import numpy as np
+import pytest
+from scipy.optimize import least_squares
+from scipy.spatial.transform import Rotation
+
+import pose_inertial_ref as R
+import pose_inertial_scenarios as PS
+
+SCIPY_KINDS = ("general", "far", "weak_imu", "strong_imu")
+METRICS = ("rot", "twb", "v", "bg", "ba")
+# Measured, the worst over the four kinds and the two rounds (N_e = 300):
+#            rot [rad]   twb [m]     v [m/s]     bg [rad/s]  ba [m/s^2]
+#   seed 0   2.794e-11   4.121e-10   1.623e-10   0           0
+#   seed 1   1.324e-10   1.786e-09   1.481e-10   0           0
+#   seed 2   2.038e-11   1.901e-10   1.008e-10   0           0          (not used for the gates)
+#   seed 3   2.786e-11   2.943e-10   6.527e-11   0           0          (not used for the gates)
+# These are the termination noise of scipy's trust-region iteration, not a distance between two minima.  The frame's biases appear in
+# the random-walk edges only, whose minimum is the key frame's bias itself: both solvers end on those floats exactly, so that gate is 0.
+GATES = dict(rot=2 * 1.324e-10, twb=2 * 1.786e-09, v=2 * 1.623e-10, bg=0.0, ba=0.0)   # twice the worst of seeds 0 and 1
+ORTHONORMALITY_BOUND = 1e-6   # the caller's Rwb is binary32: each entry is off by up to 2^-24 relative, R R^T - I by a few of those
+
+
+def test_every_branch_is_reached_by_a_scene():
+    R.COUNTS.clear()
+    for case in PS.HOST_CASES:
+        PS.ref(PS.make_case(case), **PS.case_kw(case))
+    for k in ("exp_small", "exp_general", "log_outside", "log_small", "log_general", "invjr_small", "invjr_general",   # the SO(3) branches
+              "not_ok", "few_edges_break", "recovery", "huber_linear_region", "depth_not_positive"):
+        assert R.COUNTS[k] > 0, (k, dict(R.COUNTS))
+    # RightJacobianSO3 is not called by the solver (only a fixed vertex's column uses it): its branches are reached by
+    # test_pose_inertial_cpp.py's direct comparison
+    cnt = collections.Counter()
+    R.right_jacobian_so3(np.zeros(3), cnt), R.right_jacobian_so3(np.array([0.1, 0.2, -0.3]), cnt)
+    assert cnt["jr_small"] == 1 and cnt["jr_general"] == 1
+
+
+def test_what_the_kinds_plant():
+    few = {n: PS.ref_cached(("few", n, 0)) for n in (0, 1, 6, 7)}
+    assert [few[n]["rounds_run"] for n in (0, 1, 6, 7)] == [1, 1, 1, 4]          # N_e + 3 < 10 on either side
+    assert few[0]["n_inliers"] == 0 and few[0]["round_ok"][0] == 1 and np.isfinite(few[0]["H"]).all()   # the inertial edges alone: full rank
+    assert np.linalg.matrix_rank(few[0]["H"]) == 15
+    a, b = PS.ref_cached(("recover", 25, 0)), PS.ref_cached(("recover", 25, 0, 1))
+    assert a["recovered"] == 1 and b["recovered"] == 0 and a["round_nbad"][-1] == b["round_nbad"][-1] > 0
+    assert a["n_inliers"] > b["n_inliers"] and a["outlier"].sum() < b["outlier"].sum()
+    z = PS.ref_cached(("zero_depth", 300, 0))
+    sc = PS.make_case(("zero_depth", 300, 0))
+    assert z["round_ok"][0] == 0 and z["round_iterations"][0] == 1 and z["round_ok"][1] == 1
+    start = np.concatenate([sc[k].astype(np.float64).reshape(-1) for k in ("Rwb", "twb", "v", "bg", "ba")])
+    assert z["round_state"][0].tobytes() == start.tobytes()                      # !ok: the state is kept
+    c = PS.ref_cached(("close_boundary", 257, 0))
+    sc = PS.make_case(("close_boundary", 257, 0))
+    first = np.flatnonzero(sc["mp_index"] >= 0)
+    close = sc["track_depth"][sc["mp_index"][first]] < 10.0
+    last = c["round_outlier"][-1].astype(bool)
+    # the chi2 of every edge at the final state, and the band between chi2Mono and 1.5 chi2Mono of the last round
+    K, S = R.Link(sc["link"]), R.State(*[sc[k] for k in ("Rcw", "tcw", "Rwb", "twb", "v", "bg", "ba")])
+    fin = c["round_state"][-1]
+    S.Rwb, S.twb, S.v, S.bg, S.ba = fin[:9].copy(), fin[9:12].copy(), fin[12:15].copy(), fin[15:18].copy(), fin[18:21].copy()
+    R.update(K, np.zeros(15), S)   # the camera pose of that state (Exp(0) = I and + 0.0 change nothing)
+    _, obs, w, Xw = R.edges_of(sc["level_sigma2"], sc["kp_xy"], sc["kp_octave"], sc["mp_index"], sc["points"])
+    chi2, front = R.score(S, sc["cam"], obs, w, Xw)
+    band = (chi2 > np.float32(5.991)) & (chi2 <= np.float32(1.5 * np.float64(np.float32(5.991)))) & front
+    assert (band & close).sum() > 10 and (band & ~close).sum() > 10      # planted on both sides of track_depth = 10
+    assert not last[band & close].any() and last[band & ~close].all()   # the close ones stay, the others are flagged
+    o = PS.ref_cached(("outliers", 300, 0))
+    changes = (np.diff(o["round_outlier"].astype(int), axis=0) != 0).sum(0)
+    assert changes.max() >= 1 and 80 < o["round_nbad"][-1] < 140
+    o = PS.ref_cached(("outliers", 1000, 0))                                      # an outlier may return: one flag changes twice
+    assert (np.diff(o["round_outlier"].astype(int), axis=0) != 0).sum(0).max() == 2
+    s = PS.ref_cached(("scaled_dR", 65, 0))
+    assert s["round_ok"].all() and s["n_inliers"] == 65
+    bh = PS.ref_cached(("behind", 64, 0))
+    assert bh["round_nbad"][0] >= 12
+
+
+def test_rotation_stays_orthonormal_without_normalize_rotation():
+    """departure 1: || Rwb Rwb^T - I ||_F at the end of every scene stays at the level of the caller's binary32 input"""
+    worst = 0.0
+    for case in PS.HOST_CASES:
+        M = PS.ref_cached(case)["state64"][:9].reshape(3, 3)
+        worst = max(worst, float(np.linalg.norm(M @ M.T - np.eye(3))))
+    print("worst || Rwb Rwb^T - I ||_F over the scenes: %.3e" % worst)
+    assert worst < ORTHONORMALITY_BOUND
+
+
+# ---- the independent solver ----
+def _unpack(x0, x):
+    Rwb = x0["Rwb"] @ Rotation.from_rotvec(x[0:3]).as_matrix()
+    return Rwb, x0["twb"] + x[3:6], x0["v"] + x[6:9], x0["bg"] + x[9:12], x0["ba"] + x[12:15]
+
+
+def _residuals(x, x0, sc, K, obs, w, Xw, keep, gravity):
+    Rwb, twb, v, bg, ba = _unpack(x0, x)
+    Rcb, tcb = K["Rcb"], K["tcb"]
+    Rcw = Rcb @ Rwb.T
+    tcw = Rcb @ (-Rwb.T @ twb) + tcb
+    Xc = Xw[keep] @ Rcw.T + tcw
+    fx, fy, cx, cy = (float(c) for c in sc["cam"][:4])
+    proj = np.stack([fx * Xc[:, 0] / Xc[:, 2] + cx, fy * Xc[:, 1] / Xc[:, 2] + cy], 1)
+    r_mono = ((obs[keep] - proj) * np.sqrt(w[keep])[:, None]).reshape(-1)
+    g = np.array([0.0, 0.0, -gravity])
+    dt = K["dt"]
+    Rbw1 = K["Rwb1"].T
+    er = Rotation.from_matrix(K["dR"].T @ Rbw1 @ Rwb).as_rotvec()
+    ev = Rbw1 @ (v - K["v1"] - g * dt) - K["dV"]
+    ep = Rbw1 @ (twb - K["twb1"] - K["v1"] * dt - g * dt * dt / 2.0) - K["dP"]
+    r_imu = K["L9"].T @ np.concatenate([er, ev, ep])
+    return np.concatenate([r_mono, r_imu, K["LG"].T @ (bg - K["bg1"]), K["LA"].T @ (ba - K["ba1"])])
+
+
+def _link64(link):
+    K = {k: np.asarray(link[k], np.float32).astype(np.float64) for k in ("twb1", "v1", "bg1", "ba1", "dV", "dP", "tcb")}
+    for k in ("Rwb1", "dR", "Rcb"):
+        K[k] = np.asarray(link[k], np.float32).astype(np.float64).reshape(3, 3)
+    K["dt"] = float(np.float32(link["dt"]))
+    # dR as the caller's floats is not exactly a rotation; the independent solver takes the nearest one
+    U, _, Vt = np.linalg.svd(K["dR"])
+    K["dR"] = U @ Vt
+    K["L9"] = np.linalg.cholesky(np.asarray(link["info9"], np.float64).reshape(9, 9))
+    K["LG"] = np.linalg.cholesky(np.asarray(link["infoG"], np.float64).reshape(3, 3))
+    K["LA"] = np.linalg.cholesky(np.asarray(link["infoA"], np.float64).reshape(3, 3))
+    return K
+
+
+def _state(vec):
+    return dict(Rwb=vec[:9].reshape(3, 3), twb=vec[9:12], v=vec[12:15], bg=vec[15:18], ba=vec[18:21])
+
+
+def _distance(vec, x0, x):
+    Rwb, twb, v, bg, ba = _unpack(x0, x)
+    s = _state(vec)
+    rot = float(np.linalg.norm(Rotation.from_matrix(Rwb.T @ s["Rwb"]).as_rotvec()))
+    return (rot,) + tuple(float(np.linalg.norm(a - b)) for a, b in ((twb, s["twb"]), (v, s["v"]), (bg, s["bg"]), (ba, s["ba"])))
+
+
+def measure(kind, seed):
+    """-> {0: distances after round 0, 3: distances after round 3} between the restatement and scipy"""
+    sc = PS.make(kind, 300, seed)
+    ref = PS.ref(sc)
+    assert ref["rounds_run"] == 4 and ref["round_ok"].all()
+    first, obs, w, Xw = R.edges_of(sc["level_sigma2"], sc["kp_xy"], sc["kp_octave"], sc["mp_index"], sc["points"])
+    K = _link64(sc["link"])
+    gravity = float(np.float32(9.81))
+    delta = R.delta_of(5.991)
+    out = {}
+    start = np.concatenate([sc[k].astype(np.float64).reshape(-1) for k in ("Rwb", "twb", "v", "bg", "ba")])
+    for rnd, x0vec, keep, loss in ((0, start, np.ones(len(first), bool), "huber"),
+                                   (3, ref["round_state"][2], ref["round_outlier"][2] == 0, "linear")):
+        x0 = _state(x0vec)
+        sol = least_squares(_residuals, np.zeros(15), args=(x0, sc, K, obs, w, Xw, keep, gravity), loss=loss, f_scale=delta, method="trf",
+                            x_scale="jac", xtol=1e-15, ftol=1e-15, gtol=1e-15, max_nfev=400)
+        out[rnd] = _distance(ref["round_state"][rnd], x0, sol.x)
+    return out
+
+
+@pytest.mark.parametrize("kind", SCIPY_KINDS)
+def test_restatement_against_scipy_least_squares(kind):
+    got = {seed: measure(kind, seed) for seed in (0, 1, 2, 3)}
+    for seed, d in got.items():
+        for rnd in (0, 3):
+            print("%s seed %d round %d: " % (kind, seed, rnd) + "  ".join("%s %.3e" % (m, v) for m, v in zip(METRICS, d[rnd])))
+    for seed, d in got.items():
+        for rnd in (0, 3):
+            for m, v in zip(METRICS, d[rnd]):
+                assert v <= GATES[m], "%s seed %d round %d: %s distance %.3e above the gate %.3e" % (kind, seed, rnd, m, v, GATES[m])

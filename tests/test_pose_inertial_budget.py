@@ -1,0 +1,45 @@
+"""Resource budget of pose_imu_kernel (S19), read from the compiler's resource report for gfx950; no GPU needed.  The kernel uses no
+scratch memory: no thread owns a run of edges (runs are walked by the wave, the binary-counter stack lives in lane registers), the
+15 x 15 factorisation is spread over a wave with compile-time register indices, and a lane's own entry of an array is picked by masking
+bit patterns, not by a select chain the compiler would turn into an indexed load.  One 256-thread block is one wave a SIMD, so 512
+registers a lane are there to be used."""
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "orb_slam3_v1.0_amd", "csrc")
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+
+def _resource_report(tmp_path, source):
+    if not (os.path.exists(HIPCC) or shutil.which("hipcc")):
+        pytest.skip("hipcc not available")
+    hipcc = HIPCC if os.path.exists(HIPCC) else shutil.which("hipcc")
+    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
+           "--cuda-device-only", "-c", os.path.join(CSRC, source), "-o", str(tmp_path / "k.o"),
+           "-Rpass-analysis=kernel-resource-usage"]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    funcs, cur = {}, None
+    for line in p.stderr.splitlines():
+        m = re.search(r"remark:\s+Function Name: (\S+)", line)
+        if m:
+            cur = funcs.setdefault(m.group(1), {})
+            continue
+        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[bytes/(?:lane|block)\])?: (\d+)", line)
+        if m and cur is not None:
+            cur[m.group(1).strip()] = int(m.group(2))
+    return funcs
+
+
+def test_pose_imu_kernel_uses_no_scratch(tmp_path):
+    funcs = _resource_report(tmp_path, "kernels_poseimu.hip")
+    hit = {k: v for k, v in funcs.items() if "pose_imu_kernel" in k}
+    assert len(hit) == 1, sorted(funcs)
+    r = next(iter(hit.values()))
+    assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0, r
+    assert r["VGPRs"] + r.get("AGPRs", 0) <= 512, r          # one 256-thread block: one wave a SIMD
