@@ -1,9 +1,11 @@
-// block_tree.h -- the fixed pairwise tree of S14 / S17 over one block: what kernels_poseopt.hip and kernels_initial_ba.hip share of it.
+// block_tree.h -- the fixed pairwise tree of S14 / S17 / S19 over one block: what kernels_poseopt.hip, kernels_initial_ba.hip and
+// kernels_poseimu.hip share of it.
 // A sum over P = 2^m items (+0.0 for the padding) is taken level by level, item 2i with item 2i + 1 first, then pairs of pairs: the
 // bottom levels inside a thread that owns an aligned run of items (run_tree), the next up to 6 levels inside the wave (wave_level_add:
-// DPP quad swaps, row_half_mirror, row_mirror, then two lane-xor exchanges, so every lane ends with the wave's sum), the last levels
-// across the waves through a double-buffered LDS block that every thread reads (block_tree).  Levels above log2 P are not taken: adding
-// a padding +0.0 would turn a -0.0 sum into +0.0.  Device code only; contraction is off in every including unit.
+// DPP quad swaps, row_half_mirror, row_mirror, then two lane-xor exchanges, so every lane ends with the wave's sum) -- or, for long
+// runs, chunk by chunk by the wave with the six wave levels first (wave_run_tree) --, the last levels across the waves through a
+// double-buffered LDS block that every thread reads (block_tree).  Levels above log2 P are not taken: adding a padding +0.0 would turn
+// a -0.0 sum into +0.0.  Device code only; contraction is off in every including unit.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -37,8 +39,8 @@ __device__ __forceinline__ double wave_level_add(double v, int l)
 
 // the shape of the tree for this block
 struct TreeShape {
-    int run;        // items per thread
-    int lvWave;     // levels inside a wave
+    int run;        // items per thread, or chunks per wave
+    int lvWave;     // levels inside a wave (0 after wave_run_tree, which takes all six per chunk)
     int lvCross;    // levels across waves
 };
 
@@ -133,6 +135,38 @@ __device__ __forceinline__ void run_tree(int run, double (&out)[NV], Term term)
             }
             if (i + 1 < run)
                 for (int k = 0; k < NV; k++) st[lvl][k] = out[k];
+        }
+    }
+}
+
+__device__ __forceinline__ double readlane_f64(double v, int lane)   // `lane` is wave-uniform
+{
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
+}
+
+// The same part for a run of `run` chunks of 64 items walked by the WAVE: term(c, v) fills this lane's item of chunk c, the six wave
+// levels sum the chunk, the binary counter adds chunk 2i to chunk 2i + 1 first; level j of its stack is held by lane j.  64 lanes active.
+template <int NV, class Term>
+__device__ __forceinline__ void wave_run_tree(int run, double (&out)[NV], Term term)
+{
+    const int lane = threadIdx.x & 63;
+    double st[NV];
+#pragma unroll
+    for (int k = 0; k < NV; k++) st[k] = 0.0;
+    for (int c = 0; c < run; c++) {
+        term(c, out);
+        for (int l = 0; l < 6; l++) {
+#pragma unroll
+            for (int k = 0; k < NV; k++) out[k] = wave_level_add(out[k], l);
+        }
+        int lvl = 0;
+        for (int m = c; m & 1; m >>= 1, lvl++) {
+#pragma unroll
+            for (int k = 0; k < NV; k++) out[k] = readlane_f64(st[k], lvl) + out[k];
+        }
+        if (c + 1 < run && lane == lvl) {
+#pragma unroll
+            for (int k = 0; k < NV; k++) st[k] = out[k];
         }
     }
 }

@@ -72,14 +72,10 @@ struct BaShared {
     double part[2][kTreeMaxWaves][kNV + 1];
 };
 
-__device__ __forceinline__ double readlane_f64(double v, int lane)
-{
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
-}
-
 // The part of a sum below the exchange.  RUN = 1, 2: the thread's run (run_tree).  RUN = 0: the wave's run of T.run chunks:
 // term(c, v) fills the values of this lane's point of chunk c, the six wave levels sum the chunk, and the binary counter adds chunk
 // 2i to chunk 2i + 1 first, then pairs of pairs; level j of its stack is held by lane j.
+// The walk is block_tree.h's wave_run_tree written out: calling it re-numbers this kernel's registers and moved its time (r20).
 template <int RUN, int NV, class Term>
 __device__ __forceinline__ void ba_run_tree(const TreeShape& T, double (&out)[NV], Term term)
 {
@@ -387,13 +383,10 @@ int initial_ba_check(const orbfe_initial_ba_params* P, const orbfe_initial_ba_in
         err = kBaSizeErr;
         return ORBFE_ERR_INVALID_ARG;
     }
-    if (P->camera_model == ORBFE_CAMERA_KANNALA_BRANDT8 || P->stereo != 0) {
-        err = "orbfe_initial_bundle_adjustment: only the mono pinhole edges of BundleAdjustment are built (DESIGN.md S17)";
-        return ORBFE_ERR_UNSUPPORTED;
-    }
-    if (P->camera_model != ORBFE_CAMERA_PINHOLE || P->iterations < 1 || P->iterations > kBaMaxIterations || !(P->huber_delta2 > 0.0) ||
-        (P->robust != 0 && P->robust != 1))
-        return ORBFE_ERR_INVALID_ARG;
+    static_assert(kBaMaxIterations == 64, "solver_check_common's range");
+    const int rc = solver_check_common(P, "orbfe_initial_bundle_adjustment", "edges of BundleAdjustment are", "S17", err);
+    if (rc != ORBFE_OK) return rc;
+    if (P->robust != 0 && P->robust != 1) return ORBFE_ERR_INVALID_ARG;
     return ORBFE_OK;
 }
 
@@ -493,11 +486,7 @@ int initial_ba_run_host(MatchScratch& m, hipStream_t s, const orbfe_initial_ba_p
         G.ta[i] = (double)tcw1[i];
         G.t0[i] = (double)tcw2[i];
     }
-    G.cam.fx = (double)P->cam[0];
-    G.cam.fy = (double)P->cam[1];
-    G.cam.cx = (double)P->cam[2];
-    G.cam.cy = (double)P->cam[3];
-    G.cam.delta = (double)(float)sqrt(P->huber_delta2);   // thHuber2D is a float (:139), setDelta takes a double (:189)
+    fill_pose_cam(G.cam, P->cam, P->huber_delta2);
     G.iterations = P->iterations;
     G.huber = P->robust;
     hipLaunchKernelGGL(initial_ba_kernel, dim3(1), dim3(Pw <= 64 ? 64 : kTreeThreads), 0, s, G);

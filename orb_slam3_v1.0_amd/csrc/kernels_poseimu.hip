@@ -12,9 +12,9 @@
 // pose_imu_kernel: ONE block of kTreeThreads per frame runs the whole call -- the compaction of the matched keypoints into edges,
 // four rounds, every iteration, the scoring, the recovery and the Hessian -- with no host step and no second launch.
 //   Mapping of the tree: item e = (wave * run + c) * 64 + lane.  P <= 256: run = 1, thread t takes edge t; the levels inside the
-//   wave and across the waves are block_tree's.  P >= 512: S17's wave-walked run -- wave w owns the aligned run of P / 256 chunks
-//   of 64 consecutive edges, the chunk is summed by the six wave levels and the chunk sums are combined by a binary counter whose
-//   stack level j lives in lane j's registers.  No thread owns a run, so nothing needs a dynamically indexed stack: no scratch
+//   wave and across the waves are block_tree's.  P >= 512: S17's wave-walked run (wave_run_tree of block_tree.h) -- wave w owns the
+//   aligned run of P / 256 chunks of 64 consecutive edges, the chunk is summed by the six wave levels and the chunk sums are combined by
+//   a binary counter whose stack level j lives in lane j's registers.  No thread owns a run, so nothing needs a dynamically indexed stack: no scratch
 //   memory.  An edge is read back from L2 whenever it is needed (24 + 16 bytes); its flag lives in the output array, which only the
 //   lane that takes the edge reads and writes.
 //   The 15 x 15 solve is mapped onto one wave (wave_ldlt15) and every wave runs it redundantly on the same sums, so no result is
@@ -104,43 +104,12 @@ __device__ __forceinline__ EdgeD load_edge(const PoseImuArgs& G, const ImuFrameV
     return E;
 }
 
-__device__ __forceinline__ double readlane_f64(double v, int lane)   // `lane` is wave-uniform
-{
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
-}
-
-// The part of a sum below block_tree's exchange.  run = 1: the thread's one item.  run > 1: the wave's run of chunks, as S17's
-// ba_run_tree walks it (kernels_initial_ba.hip; the text is repeated here and not moved to block_tree.h, because moving it changed
-// the register allocation of initial_ba_kernel, whose code is to stay as it is): term(c, v) fills the values of this lane's item of
-// chunk c, the six wave levels sum the chunk, and the binary counter adds chunk 2i to chunk 2i + 1 first, then pairs of pairs; level
-// j of its stack is held by lane j.
+// The part of a sum below block_tree's exchange.  run = 1: the thread's one item.  run > 1: the wave's run of chunks.
 template <int NV, class Term>
 __device__ __forceinline__ void imu_run_tree(const TreeShape& T, double (&out)[NV], Term term)
 {
-    if (T.run == 1) {
-        term(0, out);
-        return;
-    }
-    const int lane = threadIdx.x & 63;
-    double st[NV];
-#pragma unroll
-    for (int k = 0; k < NV; k++) st[k] = 0.0;
-    for (int c = 0; c < T.run; c++) {
-        term(c, out);
-        for (int l = 0; l < 6; l++) {
-#pragma unroll
-            for (int k = 0; k < NV; k++) out[k] = wave_level_add(out[k], l);
-        }
-        int lvl = 0;
-        for (int m = c; m & 1; m >>= 1, lvl++) {
-#pragma unroll
-            for (int k = 0; k < NV; k++) out[k] = readlane_f64(st[k], lvl) + out[k];
-        }
-        if (c + 1 < T.run && lane == lvl) {
-#pragma unroll
-            for (int k = 0; k < NV; k++) st[k] = out[k];
-        }
-    }
+    if (T.run == 1) term(0, out);
+    else wave_run_tree<NV>(T.run, out, term);
 }
 
 // row `lane` of the 15 x 15 matrix of imu_system (lanes >= 15: zeros); every register index is a compile-time one
@@ -441,6 +410,7 @@ __global__ __launch_bounds__(kTreeThreads) void pose_imu_kernel(PoseImuArgs G)
     int* edgeIdx = G.edgeIdx + base;
     F.edgeIdx = edgeIdx;
     // edges = the matched keypoints in keypoint order: each thread counts a contiguous chunk, the counts are scanned, the indices written
+    // (pose_opt_kernel's prologue, repeated: as a shared function it re-numbers both kernels' registers and moved their times, r20)
     const int per = (n + nT - 1) / nT;
     const int lo = tid * per < n ? tid * per : n, hi = lo + per < n ? lo + per : n;
     auto is_edge = [&](int i) {
@@ -494,11 +464,7 @@ constexpr char kPoseImuSizeErr[] =
 void fill_args(PoseImuArgs& G, const orbfe_pose_inertial_params* P, const float* invLevelSigma2, int nLevels)
 {
     memset(&G, 0, sizeof G);
-    G.cam.fx = (double)P->cam[0];
-    G.cam.fy = (double)P->cam[1];
-    G.cam.cx = (double)P->cam[2];
-    G.cam.cy = (double)P->cam[3];
-    G.cam.delta = (double)(float)sqrt(P->huber_delta2);   // thHuberMono is a float (:3498), setDelta takes a double (:3538)
+    fill_pose_cam(G.cam, P->cam, P->huber_delta2);
     G.gravity = (double)P->gravity;
     for (int i = 0; i < 4; i++) {
         G.chi2[i] = P->chi2[i];
@@ -524,13 +490,9 @@ int pose_imu_check(const orbfe_pose_inertial_params* P, const orbfe_imu_link* li
         err = kPoseImuSizeErr;
         return ORBFE_ERR_INVALID_ARG;
     }
-    if (P->camera_model == ORBFE_CAMERA_KANNALA_BRANDT8 || P->stereo != 0) {
-        err = "orbfe_pose_inertial_optimization: only the mono pinhole branch of PoseInertialOptimizationLastKeyFrame is built (DESIGN.md S19)";
-        return ORBFE_ERR_UNSUPPORTED;
-    }
-    if (P->camera_model != ORBFE_CAMERA_PINHOLE || P->iterations < 1 || P->iterations > 64 || P->rounds < 1 || P->rounds > 4 ||
-        !(P->huber_delta2 > 0.0) || !(P->close_factor >= 0.0) || P->recover_below < 0)
-        return ORBFE_ERR_INVALID_ARG;
+    const int rc = solver_check_common(P, "orbfe_pose_inertial_optimization", "branch of PoseInertialOptimizationLastKeyFrame is", "S19", err);
+    if (rc != ORBFE_OK) return rc;
+    if (P->rounds < 1 || P->rounds > 4 || !(P->close_factor >= 0.0) || P->recover_below < 0) return ORBFE_ERR_INVALID_ARG;
     for (int i = 0; i < 4; i++)
         if (!(P->chi2[i] >= 0.0f)) return ORBFE_ERR_INVALID_ARG;
     return ORBFE_OK;
@@ -577,16 +539,8 @@ int pose_imu_run(MatchScratch& m, hipStream_t s, const orbfe_pose_inertial_param
     uint8_t* hp = static_cast<uint8_t*>(m.hpin);
     uint8_t* dp = static_cast<uint8_t*>(m.d);
     if (n > 0) memcpy(hp + oKp, kp, (size_t)n * sizeof(orbfe_keypoint));
-    int* hMatch = reinterpret_cast<int*>(hp + oMatch);
-    float* hPts = reinterpret_cast<float*>(hp + oPts);
-    float* hDepth = reinterpret_cast<float*>(hp + oDepth);
-    for (int i = 0; i < n; i++) hMatch[i] = -1;
-    for (int cI = 0; cI < Ne; cI++) {
-        const int i = first[(size_t)cI];
-        hMatch[i] = cI;
-        for (int k = 0; k < 3; k++) hPts[3 * cI + k] = points[3 * (size_t)mpIndex[i] + k];
-        hDepth[cI] = trackDepth[mpIndex[i]];
-    }
+    stage_edge_list(n, first, mpIndex, points, reinterpret_cast<int*>(hp + oMatch), reinterpret_cast<float*>(hp + oPts), trackDepth,
+                    reinterpret_cast<float*>(hp + oDepth));
     memcpy(hp + oState, stateIn, kImuStateIn * sizeof(float));
     memcpy(hp + oLink, link, sizeof(orbfe_imu_link));
     MCHK(hipMemcpyAsync(dp, hp, inBytes, hipMemcpyHostToDevice, s));

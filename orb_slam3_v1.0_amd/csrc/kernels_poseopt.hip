@@ -7,7 +7,7 @@
 // Levenberg loop and SE3Quat::exp are restated from g2o's published algorithm; the 6 x 6 solve is S13's ldlt_solve6, sin / cos are
 // spec_math.h's sequences.  tests/poseopt_ref.py is the normative restatement; every byte this file produces is compared with it.
 // What one thread computes for one edge (poseopt_math.h) is host-safe text that tests/cpp/poseopt.cpp includes; this file holds the
-// loop around the tree and the host calls; the tree itself (block_tree.h) is shared with kernels_initial_ba.hip (S17).
+// loop around the tree and the host calls; the tree itself (block_tree.h) is shared with the kernels of S17 and S19.
 //
 // pose_opt_kernel: ONE block per frame runs the whole call -- the compaction of the matched keypoints into edges, four rounds, every
 // iteration and every trial -- with no host step and no second launch.
@@ -55,7 +55,7 @@ struct PoseOptArgs {
     const int* match;            // [batch][kpStride]
     int nPoints;
     const float* pts;            // records of ptRec floats, x y z first
-    size_t ptFrameStride;        // floats between two frames' points (0: shared)
+    size_t ptFrameFloats;        // FLOATS between two frames' points (0: shared); PoseImuArgs::ptFrameStride counts records
     int ptRec;
     const float* poseIn;         // [batch][12]
     float* poseOut;              // [batch][12]
@@ -298,7 +298,7 @@ __global__ __launch_bounds__(kPoseOptThreads) void pose_opt_kernel(PoseOptArgs G
     FrameView F;
     F.kp = G.kp + base;
     F.match = G.match + base;
-    F.pts = G.pts + (size_t)frame * G.ptFrameStride;
+    F.pts = G.pts + (size_t)frame * G.ptFrameFloats;
     F.outlier = G.outlier + base;
     int* edgeIdx = G.edgeIdx + base;
     F.edgeIdx = edgeIdx;
@@ -371,11 +371,7 @@ constexpr char kPoseOptSizeErr[] =
 void fill_args(PoseOptArgs& G, const orbfe_pose_opt_params* P, const float* invLevelSigma2, int nLevels)
 {
     memset(&G, 0, sizeof G);
-    G.cam.fx = (double)P->cam[0];
-    G.cam.fy = (double)P->cam[1];
-    G.cam.cx = (double)P->cam[2];
-    G.cam.cy = (double)P->cam[3];
-    G.cam.delta = (double)(float)sqrt(P->huber_delta2);   // deltaMono is a float (:805), setDelta takes a double (:837)
+    fill_pose_cam(G.cam, P->cam, P->huber_delta2);
     G.chi2Thr = P->chi2_threshold;
     G.iterations = P->iterations;
     G.nRounds = P->rounds;
@@ -392,13 +388,9 @@ int pose_opt_check(const orbfe_pose_opt_params* P, const orbfe_pose_opt_info* in
         err = kPoseOptSizeErr;
         return ORBFE_ERR_INVALID_ARG;
     }
-    if (P->camera_model == ORBFE_CAMERA_KANNALA_BRANDT8 || P->stereo != 0) {
-        err = "orbfe_pose_optimization: only the mono pinhole branch of PoseOptimization is built (DESIGN.md S14)";
-        return ORBFE_ERR_UNSUPPORTED;
-    }
-    if (P->camera_model != ORBFE_CAMERA_PINHOLE || P->iterations < 1 || P->iterations > 64 || P->rounds < 1 || P->rounds > 4 ||
-        !(P->huber_delta2 > 0.0) || !(P->chi2_threshold >= 0.0f))
-        return ORBFE_ERR_INVALID_ARG;
+    const int rc = solver_check_common(P, "orbfe_pose_optimization", "branch of PoseOptimization is", "S14", err);
+    if (rc != ORBFE_OK) return rc;
+    if (P->rounds < 1 || P->rounds > 4 || !(P->chi2_threshold >= 0.0f)) return ORBFE_ERR_INVALID_ARG;
     return ORBFE_OK;
 }
 
@@ -453,14 +445,7 @@ int pose_opt_run(MatchScratch& m, hipStream_t s, const orbfe_pose_opt_params* P,
     uint8_t* hp = static_cast<uint8_t*>(m.hpin);
     uint8_t* dp = static_cast<uint8_t*>(m.d);
     memcpy(hp + oKp, kp, (size_t)n * sizeof(orbfe_keypoint));
-    int* hMatch = reinterpret_cast<int*>(hp + oMatch);
-    float* hPts = reinterpret_cast<float*>(hp + oPts);
-    for (int i = 0; i < n; i++) hMatch[i] = -1;
-    for (int cI = 0; cI < Ne; cI++) {
-        const int i = first[(size_t)cI];
-        hMatch[i] = cI;
-        for (int k = 0; k < 3; k++) hPts[3 * cI + k] = points[3 * (size_t)mpIndex[i] + k];
-    }
+    stage_edge_list(n, first, mpIndex, points, reinterpret_cast<int*>(hp + oMatch), reinterpret_cast<float*>(hp + oPts));
     float* hPose = reinterpret_cast<float*>(hp + oPose);
     for (int i = 0; i < 9; i++) hPose[i] = Rcw[i];
     for (int i = 0; i < 3; i++) hPose[9 + i] = tcw[i];
@@ -529,7 +514,7 @@ int pose_opt_batch_device(MatchScratch& m, hipStream_t s, const orbfe_pose_opt_p
     G.nPoints = nMapPoints;
     G.pts = reinterpret_cast<const float*>(dPoints);
     G.ptRec = (int)(sizeof(orbfe_world_point) / sizeof(float));
-    G.ptFrameStride = (size_t)pointStrideFrames * G.ptRec;
+    G.ptFrameFloats = (size_t)pointStrideFrames * G.ptRec;
     G.poseIn = dPoseIn;
     G.poseOut = dPoseOut;
     G.outlier = dOutlier;

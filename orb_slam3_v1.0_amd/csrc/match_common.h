@@ -1,10 +1,11 @@
 // match_common.h -- pieces shared by the matcher translation units: descriptor distance, the rotation-consistency filter,
-// wave64 reductions, scratch arenas.
+// wave64 reductions, scratch arenas; and the host pieces the solver units share (the edge list, Tcw, the camera, the refusal ladder).
 #pragma once
 #include <string>
 #include <vector>
 
 #include "match.h"
+#include "poseopt_math.h"
 
 namespace orbfe {
 
@@ -214,6 +215,43 @@ inline void fill_tcw(const T* R, const T* t, float* Tcw)
         for (int j = 0; j < 3; j++) Tcw[4 * i + j] = (float)R[3 * i + j];
         Tcw[4 * i + 3] = (float)t[i];
     }
+}
+
+// ---- host side of the solvers (S14, S17, S19) ----
+// the reference keeps the Huber delta in a float (deltaMono, thHuberMono, thHuber2D: Optimizer.cc:805, :3498, :139), setDelta takes a double
+inline void fill_pose_cam(PoseCam& C, const float* cam, double huber_delta2)
+{
+    C.fx = (double)cam[0];
+    C.fy = (double)cam[1];
+    C.cx = (double)cam[2];
+    C.cy = (double)cam[3];
+    C.delta = (double)(float)sqrt(huber_delta2);
+}
+
+// the upload of the edge list `first`: hMatch[n] keypoint -> edge (-1: none); hPts[N_e][3] and, with trackDepth, hDepth[N_e] in edge order
+inline void stage_edge_list(int n, const std::vector<int>& first, const int* mpIndex, const float* points, int* hMatch, float* hPts,
+                            const float* trackDepth = nullptr, float* hDepth = nullptr)
+{
+    for (int i = 0; i < n; i++) hMatch[i] = -1;
+    for (size_t c = 0; c < first.size(); c++) {
+        const int i = first[c];
+        hMatch[i] = (int)c;
+        for (int k = 0; k < 3; k++) hPts[3 * c + k] = points[3 * (size_t)mpIndex[i] + k];
+        if (trackDepth) hDepth[c] = trackDepth[mpIndex[i]];
+    }
+}
+
+// the rungs every solver's refusal ladder has after the struct sizes: the branches that are not built, then the common ranges
+template <class Params>
+inline int solver_check_common(const Params* P, const char* entry, const char* built, const char* section, std::string& err)
+{
+    if (P->camera_model == ORBFE_CAMERA_KANNALA_BRANDT8 || P->stereo != 0) {
+        err = std::string(entry) + ": only the mono pinhole " + built + " built (DESIGN.md " + section + ")";
+        return ORBFE_ERR_UNSUPPORTED;
+    }
+    if (P->camera_model != ORBFE_CAMERA_PINHOLE || P->iterations < 1 || P->iterations > 64 || !(P->huber_delta2 > 0.0))
+        return ORBFE_ERR_INVALID_ARG;
+    return ORBFE_OK;
 }
 
 #define MCHK(call)                                                                          \

@@ -6,38 +6,24 @@ restatement byte for byte without a GPU; on the GPU the library's results throug
 depth and rescale (InitialMapAdjuster::MedianDepthScale: one text, run by the host mode on the host loop's results and by Adjust on the
 library's) must equal their numpy restatement (initial_ba_ref.median_depth_scale) on scenes that take each return: true, N < 50,
 median < 0 (the `behind` scene) and a NaN depth (the `nan_depth` scene)."""
-import os
 import re
 import subprocess
 
 import numpy as np
 import pytest
 
+import cpp_build
 import initial_ba_ref as R
 import initial_ba_scenarios as BS
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "orb_slam3_v1.0_amd", "csrc")
-BIN = os.path.join(ROOT, "tests", "cpp", "initial_ba.bin")
-BIN_SAN = os.path.join(ROOT, "tests", "cpp", "initial_ba_san.bin")
 KP = np.dtype([("x", "<f4"), ("y", "<f4"), ("response", "<i4"), ("size", "<f4"), ("octave", "<i4"), ("angle", "<f4")])
 SCALARS = ("N", "iterations", "trials", "exit")
 FIELDS = (("Tcw2", np.float32), ("points", np.float32), ("pose", np.float64), ("it_cost", np.float64), ("it_lambda", np.float64),
           ("it_trials", np.int32), ("chi2", np.float64), ("depth_positive", np.uint8))
 
-_built = {}
-
 
 def _build(san=False):
-    out = BIN_SAN if san else BIN
-    if out in _built:  # once per session
-        return out
-    _built[out] = 1
-    flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if san else ["-O2"]
-    subprocess.check_call(["g++"] + flags + ["-std=c++17", "-Wall", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
-                                             os.path.join(ROOT, "tests", "cpp", "initial_ba.cpp"), "-o", out, "-L", CSRC, "-lorbfe",
-                                             "-Wl,-rpath," + CSRC, "-Wl,-rpath,/opt/rocm/lib"])
-    return out
+    return cpp_build.build("initial_ba", san)
 
 
 def keypoints(xy, octave, dtype=KP):

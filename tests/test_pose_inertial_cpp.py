@@ -5,37 +5,23 @@ loop is built stand-alone with -fsanitize=address,undefined (a program with its 
 the numpy restatement byte for byte without a GPU, on one case of every kind; so are the four SO(3) functions on inputs of every
 branch, and ldlt_solve_n<6> against ldlt_solve6.  On the GPU the library's results through the adaptor must equal both."""
 import collections
-import os
 import re
 import subprocess
 
 import numpy as np
 import pytest
 
+import cpp_build
 import pose_inertial_ref as R
 import pose_inertial_scenarios as PS
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "orb_slam3_v1.0_amd", "csrc")
-BIN = os.path.join(ROOT, "tests", "cpp", "pose_inertial.bin")
-BIN_SAN = os.path.join(ROOT, "tests", "cpp", "pose_inertial_san.bin")
 KP = np.dtype([("x", "<f4"), ("y", "<f4"), ("response", "<i4"), ("size", "<f4"), ("octave", "<i4"), ("angle", "<f4")])
 LINK_FLOATS = ("Rwb1", "twb1", "v1", "bg1", "ba1", "dR", "dV", "dP", "dt", "Rcb", "tcb", "tbc")
 SCALARS = ("n_inliers", "N_e", "rounds_run", "recovered")
 
-_built = {}
-
 
 def _build(san=False, opt="-O2"):
-    out = BIN_SAN if san else BIN
-    if out in _built:  # once per session
-        return out
-    _built[out] = 1
-    flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if san else [opt]
-    subprocess.check_call(["g++"] + flags + ["-std=c++17", "-Wall", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
-                                             os.path.join(ROOT, "tests", "cpp", "pose_inertial.cpp"), "-o", out, "-L", CSRC, "-lorbfe",
-                                             "-Wl,-rpath," + CSRC, "-Wl,-rpath,/opt/rocm/lib"])
-    return out
+    return cpp_build.build("pose_inertial", san, opt)
 
 
 def link_bytes(link):

@@ -3,36 +3,22 @@ carries its own single-thread host loop of SPEC DECISION S14 (the kernel's arith
 independent oracle of both).  The host loop is built stand-alone with -fsanitize=address,undefined (a program with its own main, never
 loaded into Python) and compared with the numpy restatement byte for byte without a GPU; on the GPU the library's results through the
 adaptor must equal both."""
-import os
 import re
 import subprocess
 
 import numpy as np
 import pytest
 
+import cpp_build
 import poseopt_scenarios as PS
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "orb_slam3_v1.0_amd", "csrc")
-BIN = os.path.join(ROOT, "tests", "cpp", "poseopt.bin")
-BIN_SAN = os.path.join(ROOT, "tests", "cpp", "poseopt_san.bin")
 KP = np.dtype([("x", "<f4"), ("y", "<f4"), ("response", "<i4"), ("size", "<f4"), ("octave", "<i4"), ("angle", "<f4")])
 HOST_CASES = [("general", 300, 0), ("outliers", 300, 1), ("far", 65, 0), ("zero_depth", 10, 0), ("general", 2, 0), ("general", 9, 0)]
 SCALARS = ("n_inliers", "N_e", "rounds_run")
 
-_built = {}
-
 
 def _build(san=False):
-    out = BIN_SAN if san else BIN
-    if out in _built:  # once per session
-        return out
-    _built[out] = 1
-    flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if san else ["-O2"]
-    subprocess.check_call(["g++"] + flags + ["-std=c++17", "-Wall", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
-                                             os.path.join(ROOT, "tests", "cpp", "poseopt.cpp"), "-o", out, "-L", CSRC, "-lorbfe",
-                                             "-Wl,-rpath," + CSRC, "-Wl,-rpath,/opt/rocm/lib"])
-    return out
+    return cpp_build.build("poseopt", san)
 
 
 def write_scene(path, sc, iterations=25, rounds=4, chi2_threshold=5.991, huber_delta2=7.815):
