@@ -991,7 +991,7 @@ typedef struct orbfe_pose_opt_info {
  * of a matched keypoint outside the handle's levels, n > 65536.  ORBFE_ERR_UNSUPPORTED: KannalaBrandt8 (its project() mixes
  * atan2f / sqrtf with binary64 while projectJac uses atan2: a binary64 atan2 sequence has to be pinned first), stereo != 0,
  * Of the inertial variants, PoseInertialOptimizationLastKeyFrame is orbfe_pose_inertial_optimization_last_keyframe below (S19);
- * PoseInertialOptimizationLastFrame is not offered.
+ * PoseInertialOptimizationLastFrame is orbfe_pose_inertial_optimization_last_frame (S20).
  * NOT the reference's function in three stated respects:
  *   - g2o is an empty submodule in the reference tree: the Levenberg loop (OptimizationAlgorithmLevenberg + LinearSolverDense)
  *     and SE3Quat::exp are restated from the published algorithm and adopted as this project's definition; parity with a g2o
@@ -1093,8 +1093,8 @@ typedef struct orbfe_pose_inertial_info {
  * ORBFE_ERR_INVALID_ARG: a wrong struct_size (params, link or info), a parameter outside its range, an mp_index >= n_points, an
  * octave of a matched keypoint outside the handle's levels, n > 65536; decided from the arguments and the handle's level count
  * before the device is touched.  ORBFE_ERR_UNSUPPORTED: KannalaBrandt8 (S14's reason), stereo != 0.
- * PoseInertialOptimizationLastFrame (src/Tracking.cc:946) is not offered: it needs 30 unknowns, the EdgePriorPoseImu prior and
- * Optimizer::Marginalize; H_out is the 15 x 15 Hessian its prior is made from.
+ * PoseInertialOptimizationLastFrame (src/Tracking.cc:946) -- 30 unknowns, the EdgePriorPoseImu prior and Optimizer::Marginalize --
+ * is orbfe_pose_inertial_optimization_last_frame below (S20); H_out is the 15 x 15 Hessian its first prior is made from.
  * NOT the reference's function in these stated respects:
  *   - g2o is an empty submodule in the reference tree: OptimizationAlgorithmGaussNewton + LinearSolverDense are restated from the
  *     published algorithm; parity with a g2o build is unpinned, as in S14 and S17;
@@ -1124,6 +1124,121 @@ int orbfe_pose_inertial_optimization_batch_device(orbfe_handle *h, const orbfe_p
                                                   const orbfe_world_point *d_points, int point_stride_frames,
                                                   const float *d_track_depth, const float *d_state_in, float *d_state_out,
                                                   double *d_H_out, uint8_t *d_outlier, int *d_n_inliers, void *stream);
+
+/* -------------------------------------------------------------------------------------------
+ * Inertial pose optimisation against the last frame: the commonest tracking call once the IMU is initialised
+ * (src/Tracking.cc:946)
+ * ---------------------------------------------------------------------------------------- */
+/* the frame's camera and the constants of Optimizer::PoseInertialOptimizationLastFrame (src/Optimizer.cc:3846-4275); versioned by
+ * struct_size */
+typedef struct orbfe_pose_inertial_prev_params {
+    int struct_size;          /* sizeof(orbfe_pose_inertial_prev_params) at the caller's compile time */
+    int camera_model;         /* ORBFE_CAMERA_PINHOLE; ORBFE_CAMERA_KANNALA_BRANDT8 -> ORBFE_ERR_UNSUPPORTED */
+    float cam[8];             /* fx fy cx cy k1 k2 k3 k4 (mvParameters; only the first four are read) */
+    float chi2[4];            /* chi2Mono[it] (:4075): 5.991 four times; each >= 0 */
+    double close_factor;      /* chi2close = (float)(1.5 * chi2Mono[it]) (:4100): >= 0 */
+    float close_depth;        /* bClose = mTrackDepth < 10.f (:4107) */
+    float recover_chi2;       /* chi2MonoOut = 24.f (:4178) */
+    int recover_below;        /* the recovery runs when the last round left fewer inliers than this: 30 (:4175) */
+    int iterations;           /* its[it] (:4077), 15 in every round: [1, 64] */
+    int rounds;               /* 4 (:4085): [1, 4]; the mono edges' Huber kernel is dropped after round index 2 (:4130) */
+    int rec_init;             /* bRecInit: != 0 switches the recovery off (:4175) */
+    double huber_delta2;      /* thHuberMono = (float) sqrt(5.991) (:3897): > 0 */
+    double prior_huber_delta; /* rkp->setDelta(5) (:4070): > 0; this kernel is never dropped */
+    int inlier_threshold;     /* inlierThreshold: accepted = (return value >= inlier_threshold) (:4208); Tracking passes 8 */
+    float gravity;            /* IMU::GRAVITY_VALUE (include/ImuTypes.h): g = (0, 0, -gravity) */
+    int stereo;               /* 0; anything else (mvuRight >= 0, a second camera, Nleft != -1) -> ORBFE_ERR_UNSUPPORTED */
+    int reserved;             /* 0 */
+} orbfe_pose_inertial_prev_params;
+#define ORBFE_POSE_INERTIAL_PREV_PARAMS_INIT {(int)sizeof(orbfe_pose_inertial_prev_params), 0, {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, \
+                                              {5.991f, 5.991f, 5.991f, 5.991f}, 1.5, 10.f, 24.f, 30, 15, 4, 0, 5.991, 5.0, 8, 9.81f, 0, 0}
+
+/* The previous frame's state (free here, the start of its four vertices), the preintegration between the two frames at its own
+ * bias with the Jacobians that carry it to another bias, and the camera-body extrinsics.  3 x 3 and 9 x 9 matrices are row-major.
+ * With pInt = pFrame->mpImuPreintegratedFrame and pFp = pFrame->mpPrevFrame: Rwb1 .. ba1 = pFp's GetImuRotation / GetImuPosition /
+ * GetVelocity / mImuBias; dR0 / dV0 / dP0 = pInt->dR / dV / dP; bg0 / ba0 = pInt->b (bwx bwy bwz / bax bay baz); JRg .. JPa and dt =
+ * pInt's; info9 = EdgeInertial(pInt).information() (src/G2oTypes.cc:500-508); infoG / infoA = pFrame->mpImuPreintegrated->C
+ * .block<3,3>(9,9) / (12,12) .cast<double>().inverse() (:4046, :4053). */
+typedef struct orbfe_imu_link_free {
+    int struct_size;          /* sizeof(orbfe_imu_link_free) at the caller's compile time */
+    int reserved;             /* 0 */
+    float Rwb1[9], twb1[3], v1[3], bg1[3], ba1[3];
+    float dR0[9], dV0[3], dP0[3];
+    float bg0[3], ba0[3];     /* the bias the preintegration was made at */
+    float JRg[9], JVg[9], JVa[9], JPg[9], JPa[9];
+    float dt;
+    float Rcb[9], tcb[3];     /* mImuCalib.mTcb */
+    float tbc[3];             /* mImuCalib.mTbc.translation() */
+    float reserved2;          /* 0 */
+    double info9[81];
+    double infoG[9], infoA[9];
+} orbfe_imu_link_free;
+
+/* pFp->mpcpi, the prior on the previous frame's state (include/G2oTypes.h ConstraintPoseImu), as it stands -- H after the
+ * constructor's eigenvalue clamp; row-major */
+typedef struct orbfe_pose_imu_prior {
+    int struct_size;          /* sizeof(orbfe_pose_imu_prior) at the caller's compile time */
+    int reserved;             /* 0 */
+    double Rwb[9], twb[3], vwb[3], bg[3], ba[3];
+    double H[225];
+} orbfe_pose_imu_prior;
+
+/* every intermediate of one orbfe_pose_inertial_optimization_last_frame call (optional: info may be NULL).  A state is the frame's
+ * Rwb (9, row-major), twb, v, bg, ba, then the previous frame's, in binary64.  Entries of rounds that did not run are zero. */
+typedef struct orbfe_pose_inertial_prev_info {
+    int struct_size;          /* sizeof(orbfe_pose_inertial_prev_info) at the caller's compile time */
+    int N_e;
+    int rounds_run;
+    int recovered;            /* 1: the recovery (:4175-4203) ran */
+    int iterations[4];        /* Gauss-Newton iterations started in the round */
+    int ok[4];                /* 0: the round ended on a solve whose pivots were not all positive (the state of before it is kept) */
+    int n_bad[4];             /* nBad after the round */
+    double state[4][42];      /* the round's final state, both frames */
+    double prior_chi2[4];     /* e^T H e of the prior edge at the round's final state */
+    double prior_weight[4];   /* its Huber weight there: 1 while chi2 <= prior_huber_delta^2 */
+    uint8_t *outlier;         /* [4][N_e], caller-owned, may be NULL: the flags after each round, by edge */
+} orbfe_pose_inertial_prev_info;
+
+/* replaces Optimizer::PoseInertialOptimizationLastFrame(pFrame, inlierThreshold, bRecInit) (src/Optimizer.cc:3846-4275; the call:
+ * src/Tracking.cc:946) for the branch this fork takes: one pinhole camera, EdgeMonoOnlyPose edges, one EdgeInertial with all six
+ * vertices free, EdgeGyroRW, EdgeAccRW, EdgePriorPoseImu; 30 unknowns.  Numerics: SPEC DECISION S20;
+ * tests/pose_inertial_prev_ref.py is the normative restatement and the call equals it byte for byte.
+ * Keypoints, matches, points, depths and the frame's state are those of orbfe_pose_inertial_optimization_last_keyframe.  The caller
+ * returns 1000 itself when pFp->mpcpi is missing (:4057-4060).
+ * ALL outputs are always written; the caller applies them only when *accepted != 0, as :4208 does.  Rwb_out .. ba_out: the frame's
+ * state as floats; H30_out (900 doubles, row-major): the 30 x 30 Hessian of :4216-4264 in the reference's order (rows 0-14 the
+ * previous frame, 15-29 the frame); Hprior_out (225 doubles; may be NULL: the marginalisation is skipped): Marginalize(H, 0, 14)
+ * .block<15,15>(15,15), raw -- the eigenvalue clamp of new ConstraintPoseImu stays with the caller.  outlier_out (n) = mvbOutlier;
+ * *n_inliers = the return value (nInitialCorrespondences - nBad); *accepted = (*n_inliers >= inlier_threshold).
+ * One kernel launch of one block; one submission, one synchronisation.  HOST pointers.
+ * ORBFE_ERR_INVALID_ARG / ORBFE_ERR_UNSUPPORTED: as for orbfe_pose_inertial_optimization_last_keyframe (the struct sizes of params,
+ * link, prior and info).  NOT the reference's function in S19's four respects and in one more: the preintegrated
+ * rotation at a new bias is dR0 ExpSO3(JRg dbg) in binary64 without NormalizeRotation, where the reference takes it in binary32
+ * through Sophus and an SVD; and Optimizer::Marginalize's JacobiSVD is a pinned symmetric Jacobi eigen-decomposition. */
+int orbfe_pose_inertial_optimization_last_frame(orbfe_handle *h, const orbfe_pose_inertial_prev_params *p,
+                                                const orbfe_imu_link_free *link, const orbfe_pose_imu_prior *prior, int n,
+                                                const orbfe_keypoint *kp, const int *mp_index, int n_points, const float *points,
+                                                const float *track_depth, const float *Rcw, const float *tcw, const float *Rwb,
+                                                const float *twb, const float *v, const float *bg, const float *ba, float *Rwb_out,
+                                                float *twb_out, float *v_out, float *bg_out, float *ba_out, double *H30_out,
+                                                double *Hprior_out, uint8_t *outlier_out, int *n_inliers, int *accepted,
+                                                orbfe_pose_inertial_prev_info *info);
+
+/* Batched, HBM-resident form: as orbfe_pose_inertial_optimization_batch_device, with one orbfe_imu_link_free (d_links[b]) and one
+ * orbfe_pose_imu_prior (d_priors[b]) per frame; d_H30_out: 900 doubles per frame; d_Hprior_out: 225 doubles per frame (may be NULL);
+ * d_accepted: one int per frame.  Frame b's results are byte-equal to orbfe_pose_inertial_optimization_last_frame on the same data. */
+int orbfe_pose_inertial_optimization_last_frame_batch_device(orbfe_handle *h, const orbfe_pose_inertial_prev_params *p, int batch,
+                                                             const orbfe_imu_link_free *d_links, const orbfe_pose_imu_prior *d_priors,
+                                                             const orbfe_keypoint *d_kp, const int *d_n, int kp_stride,
+                                                             const int *d_match, int n_map_points, const orbfe_world_point *d_points,
+                                                             int point_stride_frames, const float *d_track_depth,
+                                                             const float *d_state_in, float *d_state_out, double *d_H30_out,
+                                                             double *d_Hprior_out, uint8_t *d_outlier, int *d_n_inliers,
+                                                             int *d_accepted, void *stream);
+
+/* Optimizer::Marginalize(H, 0, 14).block<15,15>(15,15) of a 30 x 30 row-major H on the HOST (no handle, no device): the same text
+ * as the kernel's epilogue (csrc/marginalize.h), byte-equal to Hprior_out for the call's H30_out.  ORBFE_ERR_INVALID_ARG: a NULL. */
+int orbfe_marginalize_pose_imu(const double *H, double *Hp);
 
 /* -------------------------------------------------------------------------------------------
  * Bundle adjustment of the initial map: the line behind orbfe_two_view_reconstruct (src/Tracking.cc:698)

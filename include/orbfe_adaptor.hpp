@@ -1672,6 +1672,62 @@ struct PoseOptimizer {
         setState(pFrame, o, H.data());
         return nInliers;
     }
+
+    // Optimizer::PoseInertialOptimizationLastFrame(pFrame, inlierThreshold, bRecInit) (src/Optimizer.cc:3846-4275; the call:
+    // src/Tracking.cc:946) as ONE call (orbfe_pose_inertial_optimization_last_frame, SPEC DECISION S20).  `link` holds the previous
+    // frame's state, pFrame->mpImuPreintegratedFrame at its own bias with its bias Jacobians, the informations and the extrinsics
+    // (which members fill it); `prior` is pFrame->mpPrevFrame->mpcpi as an orbfe_pose_imu_prior, or nullptr when it
+    // does not exist: 1000 is returned and nothing is touched (:4057-4060).  getState is PoseInertialOptimizationLastKeyFrame's;
+    // setState(F, s[21], Hprior, H30) is called ONLY when the result is accepted (:4208): it receives Rwb, twb, v (SetImuPoseVelocity),
+    // bg, ba (mImuBias), the raw 15 x 15 row-major Hprior for new ConstraintPoseImu(Rwb, twb, v, bg, ba, Hprior) -- its eigenvalue clamp
+    // runs there -- and the 30 x 30 Hessian; it deletes the previous frame's mpcpi (:4268-4270).  mvbOutlier is written either way, as
+    // the reference does.  Returns nInitialCorrespondences - nBad.
+    template <class FramePtr, class GetState, class SetState>
+    static int PoseInertialOptimizationLastFrame(ORBextractor& extractor, FramePtr pFrame, int inlierThreshold, bool bRecInit, int cameraModel,
+                                                 const std::array<float, 8>& cameraParameters, const orbfe_imu_link_free& link,
+                                                 const orbfe_pose_imu_prior* prior, GetState getState, SetState setState,
+                                                 orbfe_pose_inertial_prev_info* info = nullptr, bool* acceptedOut = nullptr)
+    {
+        if (acceptedOut) *acceptedOut = false;
+        if (!prior) return 1000;
+        orbfe_pose_inertial_prev_params p = ORBFE_POSE_INERTIAL_PREV_PARAMS_INIT;
+        p.camera_model = cameraModel;
+        p.rec_init = bRecInit ? 1 : 0;
+        p.inlier_threshold = inlierThreshold;
+        for (int i = 0; i < 8; i++) p.cam[i] = cameraParameters[(size_t)i];
+        if (pFrame->mpCamera2) p.stereo = 1;
+        const int n = pFrame->mNumKeypoints;
+        std::vector<int> mpIndex((size_t)(n > 0 ? n : 1), -1);
+        std::vector<float> points, depth;
+        for (int i = 0; i < n; i++) {
+            auto pMP = pFrame->mvpMapPoints[(size_t)i];
+            if (!pMP) continue;
+            if (pFrame->mvuRight[(size_t)i] >= 0) p.stereo = 1;
+            const auto P = pMP->GetWorldPos();
+            mpIndex[(size_t)i] = (int)depth.size();
+            points.push_back(P[0]);
+            points.push_back(P[1]);
+            points.push_back(P[2]);
+            depth.push_back(pMP->mTrackDepth);
+        }
+        float s[33], o[21];
+        getState(pFrame, s);
+        std::vector<double> H30(900), Hp(225);
+        std::vector<uint8_t> outlier((size_t)(n > 0 ? n : 1));
+        int nInliers = 0, accepted = 0;
+        orbfe_handle* h = extractor.handle();
+        orbfe_detail::check(orbfe_pose_inertial_optimization_last_frame(
+                                h, &p, &link, prior, n, reinterpret_cast<const orbfe_keypoint*>(pFrame->mvKeysUn->data()), mpIndex.data(),
+                                (int)depth.size(), points.empty() ? nullptr : points.data(), depth.empty() ? nullptr : depth.data(), s, s + 9,
+                                s + 12, s + 21, s + 24, s + 27, s + 30, o, o + 9, o + 12, o + 15, o + 18, H30.data(), Hp.data(),
+                                outlier.data(), &nInliers, &accepted, info),
+                            h, "orbfe_pose_inertial_optimization_last_frame");
+        for (int i = 0; i < n; i++)
+            if (mpIndex[(size_t)i] >= 0) pFrame->mvbOutlier[(size_t)i] = outlier[(size_t)i] != 0;
+        if (accepted) setState(pFrame, o, Hp.data(), H30.data());
+        if (acceptedOut) *acceptedOut = accepted != 0;
+        return nInliers;
+    }
 };
 
 // The numerical core of Tracking::CreateInitialMapMonocular (src/Tracking.cc:698-729) as ONE device call and a host step:

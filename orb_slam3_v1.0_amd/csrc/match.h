@@ -101,6 +101,23 @@ int pose_imu_batch_device(MatchScratch& m, hipStream_t s, const orbfe_pose_inert
                           const int* dMatch, int nMapPoints, const orbfe_world_point* dPoints, int pointStrideFrames,
                           const float* dTrackDepth, const float* dStateIn, float* dStateOut, double* dHout, uint8_t* dOutlier,
                           int* dNInliers, std::string& err);
+// kernels_poseimu_prev.hip (Optimizer::PoseInertialOptimizationLastFrame, SPEC DECISION S20)
+int pose_prev_check(const orbfe_pose_inertial_prev_params* P, const orbfe_imu_link_free* link, const orbfe_pose_imu_prior* prior,
+                    const orbfe_pose_inertial_prev_info* info, std::string& err);
+int pose_prev_begin(const orbfe_pose_inertial_prev_params* P, const orbfe_imu_link_free* link, const orbfe_pose_imu_prior* prior, int nLevels,
+                    int n, const orbfe_keypoint* kp, const int* mpIndex, int nPoints, orbfe_pose_inertial_prev_info* info,
+                    std::vector<int>& first, std::string& err);
+int pose_prev_run(MatchScratch& m, hipStream_t s, const orbfe_pose_inertial_prev_params* P, const orbfe_imu_link_free* link,
+                  const orbfe_pose_imu_prior* prior, const float* invLevelSigma2, int nLevels, int n, const orbfe_keypoint* kp,
+                  const int* mpIndex, const float* points, const float* trackDepth, const float* stateIn, const std::vector<int>& first,
+                  float* stateOut, double* H30out, double* HpriorOut, uint8_t* outlier, int* nInliers, int* accepted,
+                  orbfe_pose_inertial_prev_info* info, std::string& err);
+int pose_prev_batch_device(MatchScratch& m, hipStream_t s, const orbfe_pose_inertial_prev_params* P, const float* invLevelSigma2,
+                           int nLevels, int batch, const orbfe_imu_link_free* dLinks, const orbfe_pose_imu_prior* dPriors,
+                           const orbfe_keypoint* dKp, const int* dN, int kpStride, const int* dMatch, int nMapPoints,
+                           const orbfe_world_point* dPoints, int pointStrideFrames, const float* dTrackDepth, const float* dStateIn,
+                           float* dStateOut, double* dH30, double* dHprior, uint8_t* dOutlier, int* dNInliers, int* dAccepted,
+                           std::string& err);
 
 // kernels_initial_ba.hip (the bundle adjustment of the initial map, SPEC DECISION S17)
 int initial_ba_check(const orbfe_initial_ba_params* P, const orbfe_initial_ba_info* info, std::string& err);

@@ -25,6 +25,7 @@
 #include "match_common.h"
 #include "match_proj.h"
 #include "keyframe.h"
+#include "marginalize.h"
 #include "prep.h"
 #include "vocab.h"
 
@@ -2663,6 +2664,100 @@ int orbfe_pose_inertial_optimization_batch_device(orbfe_handle* h, const orbfe_p
                                          d_n_inliers, err);
     if (rc != ORBFE_OK) h->err = err;
     return rc;
+}
+
+int orbfe_pose_inertial_optimization_last_frame(orbfe_handle* h, const orbfe_pose_inertial_prev_params* p,
+                                                const orbfe_imu_link_free* link, const orbfe_pose_imu_prior* prior, int n,
+                                                const orbfe_keypoint* kp, const int* mp_index, int n_points, const float* points,
+                                                const float* track_depth, const float* Rcw, const float* tcw, const float* Rwb,
+                                                const float* twb, const float* v, const float* bg, const float* ba, float* Rwb_out,
+                                                float* twb_out, float* v_out, float* bg_out, float* ba_out, double* H30_out,
+                                                double* Hprior_out, uint8_t* outlier_out, int* n_inliers, int* accepted,
+                                                orbfe_pose_inertial_prev_info* info)
+{
+    if (!p) return ORBFE_ERR_INVALID_ARG;
+    std::string err;
+    int rc = pose_prev_check(p, link, prior, info, err);  // struct sizes, unsupported branches and ranges need no handle
+    if (rc == ORBFE_OK && (!h || !link || !prior || n < 0 || n_points < 0 || !Rcw || !tcw || !Rwb || !twb || !v || !bg || !ba || !Rwb_out ||
+                           !twb_out || !v_out || !bg_out || !ba_out || !H30_out || !n_inliers || !accepted ||
+                           (n > 0 && (!kp || !mp_index || !outlier_out)) || (n_points > 0 && (!points || !track_depth))))
+        return ORBFE_ERR_INVALID_ARG;
+    if (!h) return rc;
+    std::lock_guard<std::mutex> lk(h->mu);
+    std::vector<int> first;
+    // the other refusals read the handle's level count only: the device is not touched
+    if (rc == ORBFE_OK) rc = pose_prev_begin(p, link, prior, h->nLevels, n, kp, mp_index, n_points, info, first, err);
+    if (rc != ORBFE_OK) {
+        h->err = err;
+        return rc;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    MatchScope scope_(h, h->stream);
+    if (scope_.rc != ORBFE_OK) return scope_.rc;
+    float in[33], out[21];
+    memcpy(in, Rcw, 9 * sizeof(float));
+    memcpy(in + 9, tcw, 3 * sizeof(float));
+    memcpy(in + 12, Rwb, 9 * sizeof(float));
+    memcpy(in + 21, twb, 3 * sizeof(float));
+    memcpy(in + 24, v, 3 * sizeof(float));
+    memcpy(in + 27, bg, 3 * sizeof(float));
+    memcpy(in + 30, ba, 3 * sizeof(float));
+    rc = pose_prev_run(h->match, h->stream, p, link, prior, h->invSig2, h->nLevels, n, kp, mp_index, points, track_depth, in, first, out,
+                       H30_out, Hprior_out, outlier_out, n_inliers, accepted, info, err);
+    if (rc != ORBFE_OK) {
+        h->err = err;
+        return rc;
+    }
+    memcpy(Rwb_out, out, 9 * sizeof(float));
+    memcpy(twb_out, out + 9, 3 * sizeof(float));
+    memcpy(v_out, out + 12, 3 * sizeof(float));
+    memcpy(bg_out, out + 15, 3 * sizeof(float));
+    memcpy(ba_out, out + 18, 3 * sizeof(float));
+    return rc;
+}
+
+int orbfe_pose_inertial_optimization_last_frame_batch_device(orbfe_handle* h, const orbfe_pose_inertial_prev_params* p, int batch,
+                                                             const orbfe_imu_link_free* d_links, const orbfe_pose_imu_prior* d_priors,
+                                                             const orbfe_keypoint* d_kp, const int* d_n, int kp_stride,
+                                                             const int* d_match, int n_map_points, const orbfe_world_point* d_points,
+                                                             int point_stride_frames, const float* d_track_depth,
+                                                             const float* d_state_in, float* d_state_out, double* d_H30_out,
+                                                             double* d_Hprior_out, uint8_t* d_outlier, int* d_n_inliers,
+                                                             int* d_accepted, void* stream_)
+{
+    if (!p) return ORBFE_ERR_INVALID_ARG;
+    std::string err;
+    const int crc = pose_prev_check(p, nullptr, nullptr, nullptr, err);
+    if (crc != ORBFE_OK) {
+        if (h) {
+            std::lock_guard<std::mutex> lk(h->mu);
+            h->err = err;
+        }
+        return crc;
+    }
+    if (!h || batch < 1 || !d_links || !d_priors || !d_kp || !d_n || kp_stride < 1 || !d_match || n_map_points < 0 ||
+        (n_map_points > 0 && (!d_points || !d_track_depth)) || point_stride_frames < 0 || !d_state_in || !d_state_out || !d_H30_out ||
+        !d_outlier || !d_n_inliers || !d_accepted)
+        return ORBFE_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = stream_ ? (hipStream_t)stream_ : h->stream;
+    MatchScope scope_(h, s);
+    if (scope_.rc != ORBFE_OK) return scope_.rc;
+    const int rc = pose_prev_batch_device(h->match, s, p, h->invSig2, h->nLevels, batch, d_links, d_priors, d_kp, d_n, kp_stride, d_match,
+                                          n_map_points, d_points, point_stride_frames, d_track_depth, d_state_in, d_state_out, d_H30_out,
+                                          d_Hprior_out, d_outlier, d_n_inliers, d_accepted, err);
+    if (rc != ORBFE_OK) h->err = err;
+    return rc;
+}
+
+int orbfe_marginalize_pose_imu(const double* H, double* Hp)
+{
+    if (!H || !Hp) return ORBFE_ERR_INVALID_ARG;
+    orbfe::SeqExec X;
+    orbfe::MargWork W;
+    orbfe::marginalize_run(X, W, H, Hp);
+    return ORBFE_OK;
 }
 
 int orbfe_initial_bundle_adjustment(orbfe_handle* h, const orbfe_initial_ba_params* p, int n1, const orbfe_keypoint* kp1, int n2,

@@ -249,6 +249,73 @@ class PoseInertialInfo(C.Structure):
         self.struct_size = C.sizeof(PoseInertialInfo)
 
 
+class PoseInertialPrevParams(C.Structure):
+    """orbfe_pose_inertial_prev_params: the frame's camera and the constants of Optimizer::PoseInertialOptimizationLastFrame
+    (src/Optimizer.cc:3846-4275)."""
+    _fields_ = [("struct_size", C.c_int), ("camera_model", C.c_int), ("cam", C.c_float * 8), ("chi2", C.c_float * 4),
+                ("close_factor", C.c_double), ("close_depth", C.c_float), ("recover_chi2", C.c_float), ("recover_below", C.c_int),
+                ("iterations", C.c_int), ("rounds", C.c_int), ("rec_init", C.c_int), ("huber_delta2", C.c_double),
+                ("prior_huber_delta", C.c_double), ("inlier_threshold", C.c_int), ("gravity", C.c_float), ("stereo", C.c_int),
+                ("reserved", C.c_int)]
+
+    def __init__(self, cam=(0.0,) * 8, camera_model=0, chi2=(5.991, 5.991, 5.991, 5.991), close_factor=1.5, close_depth=10.0,
+                 recover_chi2=24.0, recover_below=30, iterations=15, rounds=4, rec_init=0, huber_delta2=5.991, prior_huber_delta=5.0,
+                 inlier_threshold=8, gravity=9.81, stereo=0):
+        super().__init__(C.sizeof(PoseInertialPrevParams), int(camera_model), (C.c_float * 8)(*[float(x) for x in cam]),
+                         (C.c_float * 4)(*[float(x) for x in chi2]), close_factor, close_depth, recover_chi2, int(recover_below),
+                         int(iterations), int(rounds), int(rec_init), huber_delta2, prior_huber_delta, int(inlier_threshold), gravity,
+                         int(stereo), 0)
+
+
+class ImuLinkFree(C.Structure):
+    """orbfe_imu_link_free: the previous frame's state, the preintegration at its own bias with its bias Jacobians, the informations
+    and the camera-body extrinsics.  Built from a dict of arrays named like the fields."""
+    _fields_ = [("struct_size", C.c_int), ("reserved", C.c_int), ("Rwb1", C.c_float * 9), ("twb1", C.c_float * 3), ("v1", C.c_float * 3),
+                ("bg1", C.c_float * 3), ("ba1", C.c_float * 3), ("dR0", C.c_float * 9), ("dV0", C.c_float * 3), ("dP0", C.c_float * 3),
+                ("bg0", C.c_float * 3), ("ba0", C.c_float * 3), ("JRg", C.c_float * 9), ("JVg", C.c_float * 9), ("JVa", C.c_float * 9),
+                ("JPg", C.c_float * 9), ("JPa", C.c_float * 9), ("dt", C.c_float), ("Rcb", C.c_float * 9), ("tcb", C.c_float * 3),
+                ("tbc", C.c_float * 3), ("reserved2", C.c_float), ("info9", C.c_double * 81), ("infoG", C.c_double * 9),
+                ("infoA", C.c_double * 9)]
+
+    def __init__(self, link=None):
+        super().__init__()
+        self.struct_size = C.sizeof(ImuLinkFree)
+        if link is None:
+            return
+        for name, ctype in self._fields_[2:]:
+            if name == "reserved2":
+                continue
+            if name == "dt":
+                self.dt = float(link[name])
+            else:
+                setattr(self, name, ctype(*[float(x) for x in np.asarray(link[name]).reshape(-1)]))
+
+
+class PoseImuPrior(C.Structure):
+    """orbfe_pose_imu_prior: ConstraintPoseImu of the previous frame.  Built from a dict of arrays named like the fields."""
+    _fields_ = [("struct_size", C.c_int), ("reserved", C.c_int), ("Rwb", C.c_double * 9), ("twb", C.c_double * 3), ("vwb", C.c_double * 3),
+                ("bg", C.c_double * 3), ("ba", C.c_double * 3), ("H", C.c_double * 225)]
+
+    def __init__(self, prior=None):
+        super().__init__()
+        self.struct_size = C.sizeof(PoseImuPrior)
+        if prior is None:
+            return
+        for name, ctype in self._fields_[2:]:
+            setattr(self, name, ctype(*[float(x) for x in np.asarray(prior[name], np.float64).reshape(-1)]))
+
+
+class PoseInertialPrevInfo(C.Structure):
+    """orbfe_pose_inertial_prev_info: every intermediate of one orbfe_pose_inertial_optimization_last_frame call."""
+    _fields_ = [("struct_size", C.c_int), ("N_e", C.c_int), ("rounds_run", C.c_int), ("recovered", C.c_int), ("iterations", C.c_int * 4),
+                ("ok", C.c_int * 4), ("n_bad", C.c_int * 4), ("state", (C.c_double * 42) * 4), ("prior_chi2", C.c_double * 4),
+                ("prior_weight", C.c_double * 4), ("outlier", C.c_void_p)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(PoseInertialPrevInfo)
+
+
 class InitialBAParams(C.Structure):
     """orbfe_initial_ba_params: the camera and the constants of Optimizer::GlobalBundleAdjustemnt(map, 20) (src/Optimizer.cc:60-369)."""
     _fields_ = [("struct_size", C.c_int), ("camera_model", C.c_int), ("cam", C.c_float * 8), ("huber_delta2", C.c_double),
@@ -307,6 +374,8 @@ SYMBOLS = [
     "orbfe_set_stream_priority", "orbfe_two_view_reconstruct", "orbfe_mlpnp_plan", "orbfe_mlpnp_ransac",
     "orbfe_pose_optimization", "orbfe_pose_optimization_batch_device", "orbfe_initial_bundle_adjustment",
     "orbfe_pose_inertial_optimization_last_keyframe", "orbfe_pose_inertial_optimization_batch_device",
+    "orbfe_pose_inertial_optimization_last_frame", "orbfe_pose_inertial_optimization_last_frame_batch_device",
+    "orbfe_marginalize_pose_imu",
     "orbfe_shard_range", "orbfe_pool_create", "orbfe_pool_destroy", "orbfe_pool_size", "orbfe_pool_member",
     "orbfe_pool_member_frames", "orbfe_pool_last_error", "orbfe_pool_extract", "orbfe_pool_enable_track",
     "orbfe_pool_map_update", "orbfe_pool_track",
@@ -441,6 +510,13 @@ def lib():
             [vp] * 16 + [C.POINTER(ci), C.POINTER(PoseInertialInfo)]
         L.orbfe_pose_inertial_optimization_batch_device.argtypes = [vp, C.POINTER(PoseInertialParams), ci, vp, vp, vp, ci, vp, ci, vp, ci, vp,
                                                                     vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "orbfe_pose_inertial_optimization_last_frame"):  # (as above)
+        L.orbfe_pose_inertial_optimization_last_frame.argtypes = [vp, C.POINTER(PoseInertialPrevParams), C.POINTER(ImuLinkFree),
+                                                                  C.POINTER(PoseImuPrior), ci, vp, vp, ci] + [vp] * 17 + \
+            [C.POINTER(ci), C.POINTER(ci), C.POINTER(PoseInertialPrevInfo)]
+        L.orbfe_pose_inertial_optimization_last_frame_batch_device.argtypes = [vp, C.POINTER(PoseInertialPrevParams), ci, vp, vp, vp, vp, ci,
+                                                                               vp, ci, vp, ci] + [vp] * 9
+        L.orbfe_marginalize_pose_imu.argtypes = [vp, vp]
     if hasattr(L, "orbfe_initial_bundle_adjustment"):  # (as above)
         L.orbfe_initial_bundle_adjustment.argtypes = [vp, C.POINTER(InitialBAParams), ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                                       C.POINTER(InitialBAInfo)]
@@ -1421,6 +1497,78 @@ def pose_inertial_optimization_batch_device(extractor, params, batch, d_links_pt
         extractor.h, C.byref(params), int(batch), d_links_ptr, d_kp_ptr, d_n_ptr, int(kp_stride), d_match_ptr, int(n_map_points), d_points_ptr,
         int(point_stride_frames), d_track_depth_ptr, d_state_in_ptr, d_state_out_ptr, d_H_out_ptr, d_outlier_ptr, d_n_inliers_ptr, stream),
         "orbfe_pose_inertial_optimization_batch_device")
+
+
+def pose_inertial_optimization_last_frame(extractor, params, link, prior, kp, mp_index, points, track_depth, Rcw, tcw, Rwb, twb, v, bg, ba,
+                                          want_info=True, want_prior=True):
+    """orbfe_pose_inertial_optimization_last_frame: Optimizer::PoseInertialOptimizationLastFrame (src/Optimizer.cc:3846-4275), mono
+    pinhole, SPEC DECISION S20.  link: an ImuLinkFree or a dict of its fields; prior: a PoseImuPrior or a dict; the other arguments as
+    for pose_inertial_optimization_last_keyframe -> dict(Rwb [9], twb, v, bg, ba float32, H30 [30, 30] and Hprior [15, 15] float64
+    (Hprior None without want_prior: the marginalisation is skipped), outlier [n], n_inliers, accepted) plus, with want_info, the
+    fields of orbfe_pose_inertial_prev_info cut to the rounds that ran.  All outputs are written whatever `accepted` says."""
+    kp = np.ascontiguousarray(kp, KP_DTYPE)
+    mi = np.ascontiguousarray(mp_index, np.int32)
+    assert len(mi) == len(kp)
+    pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    dep = np.ascontiguousarray(track_depth, np.float32).reshape(-1)
+    assert len(dep) == len(pts)
+    if link is not None and not isinstance(link, ImuLinkFree):
+        link = ImuLinkFree(link)
+    if prior is not None and not isinstance(prior, PoseImuPrior):
+        prior = PoseImuPrior(prior)
+    sin = [np.ascontiguousarray(a, np.float32).reshape(k) for a, k in ((Rcw, 9), (tcw, 3), (Rwb, 9), (twb, 3), (v, 3), (bg, 3), (ba, 3))]
+    sout = [np.zeros(k, np.float32) for k in (9, 3, 3, 3, 3)]
+    n = len(kp)
+    Ne = int((mi >= 0).sum())
+    H30, outl = np.zeros((30, 30), np.float64), np.zeros(max(n, 1), np.uint8)
+    Hp = np.zeros((15, 15), np.float64) if want_prior else None
+    n_inl, acc = C.c_int(0), C.c_int(0)
+    info = None
+    if want_info:
+        info = PoseInertialPrevInfo()
+        rbuf = np.zeros(4 * max(Ne, 1), np.uint8)
+        info.outlier = rbuf.ctypes.data
+    h = extractor.h if extractor is not None else None
+    rc = lib().orbfe_pose_inertial_optimization_last_frame(h, C.byref(params), C.byref(link) if link is not None else None,
+                                                           C.byref(prior) if prior is not None else None, n, _p(kp), _p(mi), len(pts),
+                                                           _p(pts), _p(dep), *[_p(a) for a in sin], *[_p(a) for a in sout], _p(H30),
+                                                           _p(Hp) if want_prior else None, _p(outl), C.byref(n_inl), C.byref(acc),
+                                                           C.byref(info) if want_info else None)
+    if rc != 0:
+        raise OrbfeError(rc, "orbfe_pose_inertial_optimization_last_frame", lib().orbfe_last_error(h).decode() if h else "")
+    out = dict(Rwb=sout[0], twb=sout[1], v=sout[2], bg=sout[3], ba=sout[4], H30=H30, Hprior=Hp, outlier=outl[:n], n_inliers=n_inl.value,
+               accepted=acc.value)
+    if want_info:
+        nr, Ne = info.rounds_run, info.N_e
+        out.update(N_e=Ne, rounds_run=nr, recovered=info.recovered, round_iterations=np.array(info.iterations, np.int32)[:nr],
+                   round_ok=np.array(info.ok, np.int32)[:nr], round_nbad=np.array(info.n_bad, np.int32)[:nr],
+                   round_state=np.array(info.state, np.float64).reshape(4, 42)[:nr],
+                   round_prior_chi2=np.array(info.prior_chi2, np.float64)[:nr],
+                   round_prior_weight=np.array(info.prior_weight, np.float64)[:nr], round_outlier=rbuf[:nr * Ne].reshape(nr, Ne))
+    return out
+
+
+def pose_inertial_optimization_last_frame_batch_device(extractor, params, batch, d_links_ptr, d_priors_ptr, d_kp_ptr, d_n_ptr, kp_stride,
+                                                       d_match_ptr, n_map_points, d_points_ptr, point_stride_frames, d_track_depth_ptr,
+                                                       d_state_in_ptr, d_state_out_ptr, d_H30_out_ptr, d_Hprior_out_ptr, d_outlier_ptr,
+                                                       d_n_inliers_ptr, d_accepted_ptr, stream=None):
+    """orbfe_pose_inertial_optimization_last_frame_batch_device: one block per frame, one orbfe_imu_link_free, one orbfe_pose_imu_prior
+    and one state per frame, everything resident in HBM (raw device pointers as ints); asynchronous on `stream`."""
+    extractor._chk(extractor.L.orbfe_pose_inertial_optimization_last_frame_batch_device(
+        extractor.h, C.byref(params), int(batch), d_links_ptr, d_priors_ptr, d_kp_ptr, d_n_ptr, int(kp_stride), d_match_ptr,
+        int(n_map_points), d_points_ptr, int(point_stride_frames), d_track_depth_ptr, d_state_in_ptr, d_state_out_ptr, d_H30_out_ptr,
+        d_Hprior_out_ptr, d_outlier_ptr, d_n_inliers_ptr, d_accepted_ptr, stream), "orbfe_pose_inertial_optimization_last_frame_batch_device")
+
+
+def marginalize_pose_imu(H):
+    """orbfe_marginalize_pose_imu: Optimizer::Marginalize(H, 0, 14).block<15,15>(15,15) of a 30 x 30 H on the host (S20), the text of
+    the kernel's epilogue -> [15, 15] float64"""
+    H = np.ascontiguousarray(H, np.float64).reshape(900)
+    Hp = np.zeros((15, 15), np.float64)
+    rc = lib().orbfe_marginalize_pose_imu(_p(H), _p(Hp))
+    if rc != 0:
+        raise OrbfeError(rc, "orbfe_marginalize_pose_imu", "")
+    return Hp
 
 
 def initial_bundle_adjustment(extractor, params, kp1, kp2, matches12, points, Rcw1, tcw1, Rcw2, tcw2, want_info=True):
