@@ -1043,8 +1043,8 @@ typedef struct orbfe_pose_inertial_params {
 #define ORBFE_POSE_INERTIAL_PARAMS_INIT {(int)sizeof(orbfe_pose_inertial_params), 0, {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, \
                                          {12.f, 7.5f, 5.991f, 5.991f}, 1.5, 10.f, 24.f, 30, 15, 4, 0, 5.991, 9.81f, 0}
 
-/* What the fixed vertices of the last key frame contribute, computed by the caller with the reference's own code, and the
- * camera-body extrinsics.  3 x 3 and 9 x 9 matrices are row-major.  With pInt = pFrame->mpImuPreintegrated, pKF =
+/* What the fixed vertices of the last key frame contribute, and the camera-body extrinsics: written whole by orbfe_imu_predict /
+ * orbfe_imu_frame_batch_device with ORBFE_IMU_FROM_KEYFRAME (SPEC DECISION S22), or computed by the caller with the reference's own code.  3 x 3 and 9 x 9 matrices are row-major.  With pInt = pFrame->mpImuPreintegrated, pKF =
  * pFrame->mpLastKeyFrame and b1 = pKF's bias: dR / dV / dP = pInt->GetDeltaRotation / GetDeltaVelocity / GetDeltaPosition(b1),
  * dt = pInt->dT, info9 = EdgeInertial(pInt).information() (the inverse of C.block<9,9>(0,0), symmetrised, eigenvalues below 1e-12
  * clamped to 0: src/G2oTypes.cc:500-508), infoG / infoA = C.block<3,3>(9,9) / (12,12) .cast<double>().inverse() (:3645,:3652). */
@@ -1158,7 +1158,8 @@ typedef struct orbfe_pose_inertial_prev_params {
  * With pInt = pFrame->mpImuPreintegratedFrame and pFp = pFrame->mpPrevFrame: Rwb1 .. ba1 = pFp's GetImuRotation / GetImuPosition /
  * GetVelocity / mImuBias; dR0 / dV0 / dP0 = pInt->dR / dV / dP; bg0 / ba0 = pInt->b (bwx bwy bwz / bax bay baz); JRg .. JPa and dt =
  * pInt's; info9 = EdgeInertial(pInt).information() (src/G2oTypes.cc:500-508); infoG / infoA = pFrame->mpImuPreintegrated->C
- * .block<3,3>(9,9) / (12,12) .cast<double>().inverse() (:4046, :4053). */
+ * .block<3,3>(9,9) / (12,12) .cast<double>().inverse() (:4046, :4053).  orbfe_imu_predict / orbfe_imu_frame_batch_device with
+ * ORBFE_IMU_FROM_FRAME write the block whole (SPEC DECISION S22). */
 typedef struct orbfe_imu_link_free {
     int struct_size;          /* sizeof(orbfe_imu_link_free) at the caller's compile time */
     int reserved;             /* 0 */
@@ -1239,6 +1240,114 @@ int orbfe_pose_inertial_optimization_last_frame_batch_device(orbfe_handle *h, co
 /* Optimizer::Marginalize(H, 0, 14).block<15,15>(15,15) of a 30 x 30 row-major H on the HOST (no handle, no device): the same text
  * as the kernel's epilogue (csrc/marginalize.h), byte-equal to Hprior_out for the call's H30_out.  ORBFE_ERR_INVALID_ARG: a NULL. */
 int orbfe_marginalize_pose_imu(const double *H, double *Hp);
+
+/* -------------------------------------------------------------------------------------------
+ * IMU preintegration, state prediction and the inertial links: what stands in front of orbfe_track_frame and the two inertial pose
+ * optimisations once the IMU is initialised (src/Tracking.cc:163-350)
+ * ---------------------------------------------------------------------------------------- */
+/* IMU::Point (include/ImuTypes.h): 32 bytes */
+typedef struct orbfe_imu_sample {
+    double t;
+    float a[3];
+    float w[3];
+} orbfe_imu_sample;
+
+/* Preintegrated::integrable: one entry of mvMeasurements */
+typedef struct orbfe_imu_step {
+    float a[3];
+    float w[3];
+    float dt;
+    float reserved;           /* 0 */
+} orbfe_imu_step;
+
+/* the diagonals of Calib::Cov (ng^2 x 3, na^2 x 3) and Calib::CovWalk (ngw^2 x 3, naw^2 x 3), scaled as src/Tracking.cc:116-123
+ * does; versioned by struct_size */
+typedef struct orbfe_imu_noise {
+    int struct_size;          /* sizeof(orbfe_imu_noise) at the caller's compile time */
+    int reserved;             /* 0 */
+    float cov[6];
+    float cov_walk[6];
+} orbfe_imu_noise;
+
+/* the whole state of IMU::Preintegrated except mvMeasurements (the caller keeps that list: the steps the calls hand out).  3 x 3
+ * matrices and the 15 x 15 C are row-major; the floats from dT to C are one contiguous block.  Versioned by struct_size. */
+typedef struct orbfe_imu_preint {
+    int struct_size;          /* sizeof(orbfe_imu_preint) at the caller's compile time */
+    int n_steps;              /* measurements integrated so far */
+    float dT;
+    float bg[3], ba[3];       /* b: bwx bwy bwz / bax bay baz */
+    float dR[9], dV[3], dP[3];
+    float JRg[9], JVg[9], JVa[9], JPg[9], JPa[9];
+    float avgA[3], avgW[3];
+    float C[225];
+} orbfe_imu_preint;
+
+#define ORBFE_IMU_FROM_KEYFRAME 0   /* the mbMapUpdated branch of PredictStateIMU (:301-325): the key-frame record, orbfe_imu_link */
+#define ORBFE_IMU_FROM_FRAME    1   /* the other branch (:326-347): the frame record, orbfe_imu_link_free */
+
+typedef struct orbfe_imu_predict_params {
+    int struct_size;          /* sizeof(orbfe_imu_predict_params) at the caller's compile time */
+    int which;                /* ORBFE_IMU_FROM_KEYFRAME or ORBFE_IMU_FROM_FRAME */
+    float gravity;            /* IMU::GRAVITY_VALUE: g = (0, 0, -gravity) */
+    float Rcb[9], tcb[3];     /* mImuCalib.mTcb */
+    float tbc[3];             /* mImuCalib.mTbc.translation() */
+} orbfe_imu_predict_params;
+
+/* Tracking::PreintegrateIMU (src/Tracking.cc:234-290) for an already selected mvImuFromLastFrame of n_samples samples (the queue
+ * pops of :201-232 stay with the caller), t_prev = mpPrevFrame->mTimeStamp, t_cur = mCurrentFrame->mTimeStamp.  The n_samples - 1
+ * steps of :242-277 are integrated into *kf (mpImuPreintegratedFromLastKF) in place at that record's own bias, and into *frame, which
+ * is first initialised at frame_bias (bwx bwy bwz bax bay baz of mLastFrame->mImuBias); steps_out (n_samples - 1 entries, may be
+ * NULL) receives them for mvMeasurements; *n_steps = their number.  n_samples < 2: both records stay untouched and *n_steps = 0
+ * (:235-238).  Numerics: SPEC DECISION S22; tests/imu_preint_ref.py is the normative restatement and the call
+ * equals it byte for byte.  One kernel launch.  HOST pointers.
+ * ORBFE_ERR_INVALID_ARG: a wrong struct_size (noise, either record), a NULL, n_samples < 0; decided before the device is touched.
+ * NOT the reference's function in these stated respects: NormalizeRotation is the polar factor through a pinned
+ * Jacobi eigen-decomposition, not Eigen's JacobiSVD; sin / cos of IntegratedRotation are the pinned binary64 sequences, rounded. */
+int orbfe_imu_preintegrate_frame(orbfe_handle *h, const orbfe_imu_noise *noise, int n_samples, const orbfe_imu_sample *samples,
+                                 double t_prev, double t_cur, const float *frame_bias, orbfe_imu_preint *kf, orbfe_imu_preint *frame,
+                                 orbfe_imu_step *steps_out, int *n_steps);
+
+/* Preintegrated::Initialize(bias) followed by IntegrateNewMeasurement over `steps` (src/ImuTypes.cc:149-237): Reintegrate() with the
+ * record's own list, MergePrevious() with the two lists concatenated by the caller.  bias = bwx bwy bwz bax bay baz.  *out is written
+ * whole (out->struct_size is set).  One kernel launch.  HOST pointers.  ORBFE_ERR_INVALID_ARG: a wrong struct_size, a NULL,
+ * n_steps < 0. */
+int orbfe_imu_reintegrate(orbfe_handle *h, const orbfe_imu_noise *noise, const float *bias, int n_steps, const orbfe_imu_step *steps,
+                          orbfe_imu_preint *out);
+
+/* Tracking::PredictStateIMU (src/Tracking.cc:293-350) with Frame::SetImuPoseVelocity (src/Frame.cc:221-238), and the inertial link the
+ * pose optimisation behind it takes.  state1 (21 floats) = Rwb1 (9, row-major) twb1 v1 bg1 ba1 of the last key frame
+ * (ORBFE_IMU_FROM_KEYFRAME) or of the last frame (ORBFE_IMU_FROM_FRAME).  state_out (33 floats) = Rcw tcw Rwb twb v bg ba, the
+ * d_state_in of the batched pose optimisations, bg / ba being the start's (:323, :345).  link_out: an orbfe_imu_link with dR / dV / dP
+ * = GetDelta*(b1) of *kf (ORBFE_IMU_FROM_KEYFRAME; `frame` may be NULL), or an orbfe_imu_link_free with the raw deltas, bias and
+ * Jacobians of *frame and infoG / infoA of *kf's C (ORBFE_IMU_FROM_FRAME, src/Optimizer.cc:4046).  *info_ok = 1 when every pivot of
+ * the covariance's factorisation was > 0; the link is written either way.  One kernel launch.  HOST pointers.
+ * NOT the reference's function in these stated respects, besides those of orbfe_imu_preintegrate_frame: the
+ * rotation at a new bias is S20's dR ExpSO3(JRg dbg) in binary64, then rounded and normalised; the covariance is inverted by L D L^T
+ * without pivoting of its upper triangle, not Eigen's LU; the eigen-decomposition is S12's Jacobi sequence. */
+int orbfe_imu_predict(orbfe_handle *h, const orbfe_imu_predict_params *p, const float *state1, const orbfe_imu_preint *kf,
+                      const orbfe_imu_preint *frame, float *state_out, void *link_out, int *info_ok);
+
+/* The three calls above for a batch of independent frames in ONE launch.  sample_off (batch + 1 ints, HOST: ascending, checked
+ * here, passed on by one asynchronous copy): frame b owns d_samples[sample_off[b] .. sample_off[b + 1]).  DEVICE pointers otherwise:
+ * d_t_prev / d_t_cur (one double per frame), d_frame_bias (6 floats per frame), d_state1 (21 floats per frame), d_kf (one record per
+ * frame, in / out), d_frame (one record per frame, out; a frame with fewer than 2 samples leaves both records as they are and its
+ * prediction reads them as they stand), d_steps_out (may be NULL; frame b's steps at d_steps_out[sample_off[b] ..]), d_state_in (33
+ * floats per frame), d_links (orbfe_imu_link or orbfe_imu_link_free per frame, by p->which), d_info_ok (one int per frame).
+ * d_state_in and d_links are what orbfe_pose_inertial_optimization_batch_device (ORBFE_IMU_FROM_KEYFRAME) and
+ * orbfe_pose_inertial_optimization_last_frame_batch_device (ORBFE_IMU_FROM_FRAME) read.  Asynchronous on `stream` (NULL == the
+ * handle's stream), no host synchronisation.  Frame b's bytes equal the three host-pointer calls on the same data.  The records'
+ * struct_size cannot be checked by a device call.  ORBFE_ERR_INVALID_ARG: a wrong struct_size, a NULL, batch < 1, sample_off[0] < 0
+ * or descending offsets. */
+int orbfe_imu_frame_batch_device(orbfe_handle *h, const orbfe_imu_noise *noise, const orbfe_imu_predict_params *p, int batch,
+                                 const orbfe_imu_sample *d_samples, const int *sample_off, const double *d_t_prev,
+                                 const double *d_t_cur, const float *d_frame_bias, const float *d_state1, orbfe_imu_preint *d_kf,
+                                 orbfe_imu_preint *d_frame, orbfe_imu_step *d_steps_out, float *d_state_in, void *d_links,
+                                 int *d_info_ok, void *stream);
+
+/* orbfe_imu_reintegrate for a batch of records in ONE launch: step_off (batch + 1 ints, HOST, as sample_off above), d_steps, d_bias (6
+ * floats per record), d_out (one record per entry, written whole).  Asynchronous on `stream`. */
+int orbfe_imu_reintegrate_batch_device(orbfe_handle *h, const orbfe_imu_noise *noise, int batch, const orbfe_imu_step *d_steps,
+                                       const int *step_off, const float *d_bias, orbfe_imu_preint *d_out, void *stream);
 
 /* -------------------------------------------------------------------------------------------
  * Bundle adjustment of the initial map: the line behind orbfe_two_view_reconstruct (src/Tracking.cc:698)

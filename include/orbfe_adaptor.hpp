@@ -1730,6 +1730,113 @@ struct PoseOptimizer {
     }
 };
 
+// Tracking::PreintegrateIMU (src/Tracking.cc:234-290), Tracking::PredictStateIMU (:293-350) and the builders of the two inertial links
+// (SPEC DECISION S22): what stands in front of FrameTracker and of PoseOptimizer's two inertial wrappers once the IMU is initialised.
+// The caller keeps the reference's queue handling (:201-232) and hands the selected mvImuFromLastFrame over; the records are
+// orbfe_imu_preint blocks (IMU::Preintegrated without mvMeasurements), the steps go back for mvMeasurements.  Passing the link to
+// PoseOptimizer::PoseInertialOptimizationLastKeyFrame / LastFrame is the caller's one line.
+// The stated departures are those of include/orbfe.h (the polar-factor NormalizeRotation, pinned sin / cos, ExpSO3 in binary64, L D L^T
+// for the covariance's inverse, Jacobi for its eigen-decomposition).
+class ImuPreintegrator {
+public:
+    // calib.Cov / calib.CovWalk diagonals (ng^2 x 3, na^2 x 3 / ngw^2 x 3, naw^2 x 3), IMU::GRAVITY_VALUE, mImuCalib.mTcb / mTbc
+    ImuPreintegrator(ORBextractor& extractor, const std::array<float, 6>& cov, const std::array<float, 6>& covWalk, float gravity,
+                     const float* Rcb, const float* tcb, const float* tbc)
+        : mExtractor(extractor)
+    {
+        mNoise.struct_size = (int)sizeof mNoise;
+        mNoise.reserved = 0;
+        for (int i = 0; i < 6; i++) {
+            mNoise.cov[i] = cov[(size_t)i];
+            mNoise.cov_walk[i] = covWalk[(size_t)i];
+        }
+        mParams.struct_size = (int)sizeof mParams;
+        mParams.which = ORBFE_IMU_FROM_KEYFRAME;
+        mParams.gravity = gravity;
+        std::memcpy(mParams.Rcb, Rcb, sizeof mParams.Rcb);
+        std::memcpy(mParams.tcb, tcb, sizeof mParams.tcb);
+        std::memcpy(mParams.tbc, tbc, sizeof mParams.tbc);
+    }
+
+    // new IMU::Preintegrated(bias, calib): Initialize(b) (src/ImuTypes.cc:149-168); bias = bwx bwy bwz bax bay baz
+    orbfe_imu_preint Fresh(const float* bias) const { return Reintegrate(bias, std::vector<orbfe_imu_step>()); }
+
+    // The loop of PreintegrateIMU over mvImuFromLastFrame: `fromLastKF` (mpImuPreintegratedFromLastKF) is integrated in place,
+    // `fromLastFrame` (pImuPreintegratedFromLastFrame) is made at lastFrameBias (mLastFrame->mImuBias), `steps` receives the n - 1
+    // integrable entries.  false = the reference's early return (:235-238): fewer than two samples, nothing touched.
+    bool PreintegrateIMU(const std::vector<orbfe_imu_sample>& imuFromLastFrame, double prevStamp, double curStamp, const float* lastFrameBias,
+                         orbfe_imu_preint& fromLastKF, orbfe_imu_preint& fromLastFrame, std::vector<orbfe_imu_step>* steps = nullptr) const
+    {
+        const int n = (int)imuFromLastFrame.size();
+        if (steps) steps->assign((size_t)(n > 1 ? n - 1 : 0), orbfe_imu_step{});
+        int nSteps = 0;
+        orbfe_handle* h = mExtractor.handle();
+        fromLastFrame.struct_size = (int)sizeof fromLastFrame;
+        orbfe_detail::check(orbfe_imu_preintegrate_frame(h, &mNoise, n, imuFromLastFrame.data(), prevStamp, curStamp, lastFrameBias, &fromLastKF,
+                                                         &fromLastFrame, steps && n > 1 ? steps->data() : nullptr, &nSteps),
+                            h, "orbfe_imu_preintegrate_frame");
+        return nSteps > 0;
+    }
+
+    // Preintegrated::Reintegrate() with the record's own list; MergePrevious(pPrev) with pPrev's list followed by the record's
+    orbfe_imu_preint Reintegrate(const float* bias, const std::vector<orbfe_imu_step>& measurements) const
+    {
+        orbfe_imu_preint out;
+        orbfe_handle* h = mExtractor.handle();
+        orbfe_detail::check(orbfe_imu_reintegrate(h, &mNoise, bias, (int)measurements.size(), measurements.empty() ? nullptr : measurements.data(),
+                                                  &out),
+                            h, "orbfe_imu_reintegrate");
+        return out;
+    }
+
+    // PredictStateIMU's mbMapUpdated branch (:301-325) and the link of PoseInertialOptimizationLastKeyFrame.  lastKeyFrameState (21) =
+    // GetImuRotation (9, row-major), GetImuPosition, GetVelocity, GetGyroBias, GetAccBias of mpLastKeyFrame; state (33) = Rcw tcw Rwb
+    // twb v bg ba: what SetImuPoseVelocity and mImuBias receive, and getState of the pose optimisation.  Returns info_ok.
+    bool PredictStateIMU(const float* lastKeyFrameState, const orbfe_imu_preint& fromLastKF, float* state, orbfe_imu_link& link) const
+    {
+        return Predict(ORBFE_IMU_FROM_KEYFRAME, lastKeyFrameState, fromLastKF, nullptr, state, &link);
+    }
+
+    // PredictStateIMU's other branch (:326-347) and the link of PoseInertialOptimizationLastFrame: the last frame's state, the frame
+    // record; infoG / infoA come from the key-frame record (src/Optimizer.cc:4046)
+    bool PredictStateIMU(const float* lastFrameState, const orbfe_imu_preint& fromLastKF, const orbfe_imu_preint& fromLastFrame, float* state,
+                         orbfe_imu_link_free& link) const
+    {
+        return Predict(ORBFE_IMU_FROM_FRAME, lastFrameState, fromLastKF, &fromLastFrame, state, &link);
+    }
+
+    // the links alone (the prediction is computed and dropped)
+    bool LinkLastKeyFrame(const float* lastKeyFrameState, const orbfe_imu_preint& fromLastKF, orbfe_imu_link& link) const
+    {
+        float state[33];
+        return PredictStateIMU(lastKeyFrameState, fromLastKF, state, link);
+    }
+    bool LinkLastFrame(const float* lastFrameState, const orbfe_imu_preint& fromLastKF, const orbfe_imu_preint& fromLastFrame,
+                       orbfe_imu_link_free& link) const
+    {
+        float state[33];
+        return PredictStateIMU(lastFrameState, fromLastKF, fromLastFrame, state, link);
+    }
+
+    const orbfe_imu_noise& noise() const { return mNoise; }
+    const orbfe_imu_predict_params& params() const { return mParams; }
+
+private:
+    bool Predict(int which, const float* state1, const orbfe_imu_preint& kf, const orbfe_imu_preint* frame, float* state, void* link) const
+    {
+        orbfe_imu_predict_params p = mParams;
+        p.which = which;
+        int ok = 0;
+        orbfe_handle* h = mExtractor.handle();
+        orbfe_detail::check(orbfe_imu_predict(h, &p, state1, &kf, frame, state, link, &ok), h, "orbfe_imu_predict");
+        return ok != 0;
+    }
+
+    ORBextractor& mExtractor;
+    orbfe_imu_noise mNoise;
+    orbfe_imu_predict_params mParams;
+};
+
 // The numerical core of Tracking::CreateInitialMapMonocular (src/Tracking.cc:698-729) as ONE device call and a host step:
 // Optimizer::GlobalBundleAdjustemnt(map, 20) -- two key frames of which the first is fixed, every initial map point seen once in
 // either -- is orbfe_initial_bundle_adjustment (SPEC DECISION S17); KeyFrame::ComputeSceneMedianDepth(2) (src/KeyFrame.cc:859-892)

@@ -119,6 +119,24 @@ int pose_prev_batch_device(MatchScratch& m, hipStream_t s, const orbfe_pose_iner
                            float* dStateOut, double* dH30, double* dHprior, uint8_t* dOutlier, int* dNInliers, int* dAccepted,
                            std::string& err);
 
+// kernels_imu_preint.hip (IMU preintegration, state prediction and the inertial links, SPEC DECISION S22)
+int imu_check(const orbfe_imu_noise* noise, const orbfe_imu_predict_params* P, const orbfe_imu_preint* a, const orbfe_imu_preint* b,
+              std::string& err);
+int imu_check_offsets(int batch, const int* off);
+int imu_preintegrate_run(MatchScratch& m, hipStream_t s, const orbfe_imu_noise* noise, int n, const orbfe_imu_sample* samples, double tPrev,
+                         double tCur, const float* frameBias, orbfe_imu_preint* kf, orbfe_imu_preint* frame, orbfe_imu_step* stepsOut,
+                         int* nSteps, std::string& err);
+int imu_reintegrate_run(MatchScratch& m, hipStream_t s, const orbfe_imu_noise* noise, const float* bias, int n, const orbfe_imu_step* steps,
+                        orbfe_imu_preint* out, std::string& err);
+int imu_predict_run(MatchScratch& m, hipStream_t s, const orbfe_imu_predict_params* P, const float* state1, const orbfe_imu_preint* kf,
+                    const orbfe_imu_preint* frame, float* stateOut, void* linkOut, int* infoOk, std::string& err);
+int imu_frame_batch_device(MatchScratch& m, hipStream_t s, const orbfe_imu_noise* noise, const orbfe_imu_predict_params* P, int batch,
+                           const orbfe_imu_sample* dSamples, const int* sampleOff, const double* dTPrev, const double* dTCur,
+                           const float* dFrameBias, const float* dState1, orbfe_imu_preint* dKf, orbfe_imu_preint* dFrame,
+                           orbfe_imu_step* dStepsOut, float* dStateIn, void* dLinks, int* dInfoOk, std::string& err);
+int imu_reintegrate_batch_device(MatchScratch& m, hipStream_t s, const orbfe_imu_noise* noise, int batch, const orbfe_imu_step* dSteps,
+                                 const int* stepOff, const float* dBias, orbfe_imu_preint* dOut, std::string& err);
+
 // kernels_initial_ba.hip (the bundle adjustment of the initial map, SPEC DECISION S17)
 int initial_ba_check(const orbfe_initial_ba_params* P, const orbfe_initial_ba_info* info, std::string& err);
 int initial_ba_begin(const orbfe_initial_ba_params* P, int nLevels, int n1, const orbfe_keypoint* kp1, int n2, const orbfe_keypoint* kp2,

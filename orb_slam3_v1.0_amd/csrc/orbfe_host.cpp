@@ -2760,6 +2760,105 @@ int orbfe_marginalize_pose_imu(const double* H, double* Hp)
     return ORBFE_OK;
 }
 
+// what every S22 call does once its arguments stand: the handle's lock, device and scratch, then `run`
+extern "C++" {
+template <class Run>
+static int imu_call(orbfe_handle* h, hipStream_t s, Run run)
+{
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!s) s = h->stream;
+    MatchScope scope_(h, s);
+    if (scope_.rc != ORBFE_OK) return scope_.rc;
+    std::string err;
+    const int rc = run(s, err);
+    if (rc != ORBFE_OK) h->err = err;
+    return rc;
+}
+}  // extern "C++"
+
+static int imu_refuse(orbfe_handle* h, int rc, const std::string& err)
+{
+    if (h && !err.empty()) {
+        std::lock_guard<std::mutex> lk(h->mu);
+        h->err = err;
+    }
+    return rc;
+}
+
+int orbfe_imu_preintegrate_frame(orbfe_handle* h, const orbfe_imu_noise* noise, int n_samples, const orbfe_imu_sample* samples,
+                                 double t_prev, double t_cur, const float* frame_bias, orbfe_imu_preint* kf, orbfe_imu_preint* frame,
+                                 orbfe_imu_step* steps_out, int* n_steps)
+{
+    if (!noise || !kf || !frame || !n_steps || !frame_bias || n_samples < 0 || (n_samples > 0 && !samples)) return ORBFE_ERR_INVALID_ARG;
+    std::string err;
+    // *frame is written whole when there is a step; its size field is checked all the same: it says what the caller compiled against
+    const int crc = imu_check(noise, nullptr, kf, frame, err);
+    if (crc != ORBFE_OK) return imu_refuse(h, crc, err);
+    if (!h) return ORBFE_ERR_INVALID_ARG;
+    if (n_samples < 2) {   // (:235-238)
+        *n_steps = 0;
+        return ORBFE_OK;
+    }
+    return imu_call(h, nullptr, [&](hipStream_t s, std::string& e) {
+        return imu_preintegrate_run(h->match, s, noise, n_samples, samples, t_prev, t_cur, frame_bias, kf, frame, steps_out, n_steps, e);
+    });
+}
+
+int orbfe_imu_reintegrate(orbfe_handle* h, const orbfe_imu_noise* noise, const float* bias, int n_steps, const orbfe_imu_step* steps,
+                          orbfe_imu_preint* out)
+{
+    if (!noise || !bias || !out || n_steps < 0 || (n_steps > 0 && !steps)) return ORBFE_ERR_INVALID_ARG;
+    std::string err;
+    const int crc = imu_check(noise, nullptr, nullptr, nullptr, err);
+    if (crc != ORBFE_OK) return imu_refuse(h, crc, err);
+    if (!h) return ORBFE_ERR_INVALID_ARG;
+    return imu_call(h, nullptr, [&](hipStream_t s, std::string& e) { return imu_reintegrate_run(h->match, s, noise, bias, n_steps, steps, out, e); });
+}
+
+int orbfe_imu_predict(orbfe_handle* h, const orbfe_imu_predict_params* p, const float* state1, const orbfe_imu_preint* kf,
+                      const orbfe_imu_preint* frame, float* state_out, void* link_out, int* info_ok)
+{
+    if (!p || !state1 || !kf || !state_out || !link_out || !info_ok) return ORBFE_ERR_INVALID_ARG;
+    std::string err;
+    const int crc = imu_check(nullptr, p, kf, frame, err);
+    if (crc != ORBFE_OK) return imu_refuse(h, crc, err);
+    if (!h || (p->which == ORBFE_IMU_FROM_FRAME && !frame)) return ORBFE_ERR_INVALID_ARG;
+    return imu_call(h, nullptr, [&](hipStream_t s, std::string& e) { return imu_predict_run(h->match, s, p, state1, kf, frame, state_out, link_out, info_ok, e); });
+}
+
+int orbfe_imu_frame_batch_device(orbfe_handle* h, const orbfe_imu_noise* noise, const orbfe_imu_predict_params* p, int batch,
+                                 const orbfe_imu_sample* d_samples, const int* sample_off, const double* d_t_prev, const double* d_t_cur,
+                                 const float* d_frame_bias, const float* d_state1, orbfe_imu_preint* d_kf, orbfe_imu_preint* d_frame,
+                                 orbfe_imu_step* d_steps_out, float* d_state_in, void* d_links, int* d_info_ok, void* stream_)
+{
+    if (!noise || !p) return ORBFE_ERR_INVALID_ARG;
+    std::string err;
+    const int crc = imu_check(noise, p, nullptr, nullptr, err);
+    if (crc != ORBFE_OK) return imu_refuse(h, crc, err);
+    if (imu_check_offsets(batch, sample_off) != ORBFE_OK) return ORBFE_ERR_INVALID_ARG;
+    if (!h || !d_samples || !d_t_prev || !d_t_cur || !d_frame_bias || !d_state1 || !d_kf || !d_frame || !d_state_in || !d_links || !d_info_ok)
+        return ORBFE_ERR_INVALID_ARG;
+    return imu_call(h, (hipStream_t)stream_, [&](hipStream_t s, std::string& e) {
+        return imu_frame_batch_device(h->match, s, noise, p, batch, d_samples, sample_off, d_t_prev, d_t_cur, d_frame_bias, d_state1, d_kf, d_frame,
+                                      d_steps_out, d_state_in, d_links, d_info_ok, e);
+    });
+}
+
+int orbfe_imu_reintegrate_batch_device(orbfe_handle* h, const orbfe_imu_noise* noise, int batch, const orbfe_imu_step* d_steps,
+                                       const int* step_off, const float* d_bias, orbfe_imu_preint* d_out, void* stream_)
+{
+    if (!noise) return ORBFE_ERR_INVALID_ARG;
+    std::string err;
+    const int crc = imu_check(noise, nullptr, nullptr, nullptr, err);
+    if (crc != ORBFE_OK) return imu_refuse(h, crc, err);
+    if (imu_check_offsets(batch, step_off) != ORBFE_OK) return ORBFE_ERR_INVALID_ARG;
+    if (!h || !d_steps || !d_bias || !d_out) return ORBFE_ERR_INVALID_ARG;
+    return imu_call(h, (hipStream_t)stream_, [&](hipStream_t s, std::string& e) {
+        return imu_reintegrate_batch_device(h->match, s, noise, batch, d_steps, step_off, d_bias, d_out, e);
+    });
+}
+
 int orbfe_initial_bundle_adjustment(orbfe_handle* h, const orbfe_initial_ba_params* p, int n1, const orbfe_keypoint* kp1, int n2,
                                     const orbfe_keypoint* kp2, const int* matches12, const float* points, const float* Rcw1,
                                     const float* tcw1, const float* Rcw2, const float* tcw2, float* Tcw2_out, float* points_out,

@@ -316,6 +316,52 @@ class PoseInertialPrevInfo(C.Structure):
         self.struct_size = C.sizeof(PoseInertialPrevInfo)
 
 
+class ImuNoise(C.Structure):
+    """orbfe_imu_noise: the diagonals of Calib::Cov and Calib::CovWalk (gyro x 3, accelerometer x 3 each)."""
+    _fields_ = [("struct_size", C.c_int), ("reserved", C.c_int), ("cov", C.c_float * 6), ("cov_walk", C.c_float * 6)]
+
+    def __init__(self, cov=(0.0,) * 6, cov_walk=(0.0,) * 6):
+        super().__init__(C.sizeof(ImuNoise), 0, (C.c_float * 6)(*[float(x) for x in cov]), (C.c_float * 6)(*[float(x) for x in cov_walk]))
+
+
+IMU_SAMPLE_DTYPE = np.dtype([("t", "<f8"), ("a", "<f4", 3), ("w", "<f4", 3)])            # orbfe_imu_sample
+IMU_STEP_DTYPE = np.dtype([("a", "<f4", 3), ("w", "<f4", 3), ("dt", "<f4"), ("reserved", "<f4")])  # orbfe_imu_step
+IMU_FROM_KEYFRAME, IMU_FROM_FRAME = 0, 1
+
+
+class ImuPreint(C.Structure):
+    """orbfe_imu_preint: IMU::Preintegrated without its measurement list.  floats() / set_floats() move the 298 floats dT .. C."""
+    _fields_ = [("struct_size", C.c_int), ("n_steps", C.c_int), ("dT", C.c_float), ("bg", C.c_float * 3), ("ba", C.c_float * 3),
+                ("dR", C.c_float * 9), ("dV", C.c_float * 3), ("dP", C.c_float * 3), ("JRg", C.c_float * 9), ("JVg", C.c_float * 9),
+                ("JVa", C.c_float * 9), ("JPg", C.c_float * 9), ("JPa", C.c_float * 9), ("avgA", C.c_float * 3), ("avgW", C.c_float * 3),
+                ("C", C.c_float * 225)]
+
+    def __init__(self, floats=None, n_steps=0):
+        super().__init__()
+        self.struct_size = C.sizeof(ImuPreint)
+        self.n_steps = int(n_steps)
+        if floats is not None:
+            self.set_floats(floats)
+
+    def floats(self):
+        return np.frombuffer(bytes(self), np.float32, 298, 8).copy()
+
+    def set_floats(self, v):
+        v = np.ascontiguousarray(v, np.float32).reshape(298)
+        C.memmove(C.addressof(self) + 8, v.ctypes.data, v.nbytes)
+
+
+class ImuPredictParams(C.Structure):
+    """orbfe_imu_predict_params: which record the prediction and the link come from, gravity, the camera-body extrinsics."""
+    _fields_ = [("struct_size", C.c_int), ("which", C.c_int), ("gravity", C.c_float), ("Rcb", C.c_float * 9), ("tcb", C.c_float * 3),
+                ("tbc", C.c_float * 3)]
+
+    def __init__(self, which=0, gravity=9.81, Rcb=(1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0), tcb=(0.0,) * 3, tbc=(0.0,) * 3):
+        super().__init__(C.sizeof(ImuPredictParams), int(which), float(gravity),
+                         (C.c_float * 9)(*[float(x) for x in np.asarray(Rcb).reshape(-1)]), (C.c_float * 3)(*[float(x) for x in tcb]),
+                         (C.c_float * 3)(*[float(x) for x in tbc]))
+
+
 class InitialBAParams(C.Structure):
     """orbfe_initial_ba_params: the camera and the constants of Optimizer::GlobalBundleAdjustemnt(map, 20) (src/Optimizer.cc:60-369)."""
     _fields_ = [("struct_size", C.c_int), ("camera_model", C.c_int), ("cam", C.c_float * 8), ("huber_delta2", C.c_double),
@@ -376,6 +422,8 @@ SYMBOLS = [
     "orbfe_pose_inertial_optimization_last_keyframe", "orbfe_pose_inertial_optimization_batch_device",
     "orbfe_pose_inertial_optimization_last_frame", "orbfe_pose_inertial_optimization_last_frame_batch_device",
     "orbfe_marginalize_pose_imu",
+    "orbfe_imu_preintegrate_frame", "orbfe_imu_reintegrate", "orbfe_imu_predict", "orbfe_imu_frame_batch_device",
+    "orbfe_imu_reintegrate_batch_device",
     "orbfe_shard_range", "orbfe_pool_create", "orbfe_pool_destroy", "orbfe_pool_size", "orbfe_pool_member",
     "orbfe_pool_member_frames", "orbfe_pool_last_error", "orbfe_pool_extract", "orbfe_pool_enable_track",
     "orbfe_pool_map_update", "orbfe_pool_track",
@@ -517,6 +565,13 @@ def lib():
         L.orbfe_pose_inertial_optimization_last_frame_batch_device.argtypes = [vp, C.POINTER(PoseInertialPrevParams), ci, vp, vp, vp, vp, ci,
                                                                                vp, ci, vp, ci] + [vp] * 9
         L.orbfe_marginalize_pose_imu.argtypes = [vp, vp]
+    if hasattr(L, "orbfe_imu_preintegrate_frame"):  # (as above)
+        L.orbfe_imu_preintegrate_frame.argtypes = [vp, C.POINTER(ImuNoise), ci, vp, C.c_double, C.c_double, vp, C.POINTER(ImuPreint),
+                                                   C.POINTER(ImuPreint), vp, C.POINTER(ci)]
+        L.orbfe_imu_reintegrate.argtypes = [vp, C.POINTER(ImuNoise), vp, ci, vp, C.POINTER(ImuPreint)]
+        L.orbfe_imu_predict.argtypes = [vp, C.POINTER(ImuPredictParams), vp, C.POINTER(ImuPreint), C.POINTER(ImuPreint), vp, vp, C.POINTER(ci)]
+        L.orbfe_imu_frame_batch_device.argtypes = [vp, C.POINTER(ImuNoise), C.POINTER(ImuPredictParams), ci] + [vp] * 13
+        L.orbfe_imu_reintegrate_batch_device.argtypes = [vp, C.POINTER(ImuNoise), ci, vp, vp, vp, vp, vp]
     if hasattr(L, "orbfe_initial_bundle_adjustment"):  # (as above)
         L.orbfe_initial_bundle_adjustment.argtypes = [vp, C.POINTER(InitialBAParams), ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                                       C.POINTER(InitialBAInfo)]
@@ -1569,6 +1624,76 @@ def marginalize_pose_imu(H):
     if rc != 0:
         raise OrbfeError(rc, "orbfe_marginalize_pose_imu", "")
     return Hp
+
+
+def _imu_fail(h, rc, where):
+    raise OrbfeError(rc, where, lib().orbfe_last_error(h).decode() if h else "")
+
+
+def imu_preintegrate_frame(extractor, noise, samples, t_prev, t_cur, frame_bias, kf, want_steps=True):
+    """orbfe_imu_preintegrate_frame: Tracking::PreintegrateIMU (src/Tracking.cc:234-290) for a selected sample list, SPEC DECISION S22.
+    samples: IMU_SAMPLE_DTYPE records; frame_bias: bwx bwy bwz bax bay baz; kf: the ImuPreint of the last key frame, integrated in
+    place -> (frame ImuPreint, steps IMU_STEP_DTYPE records or None, n_steps).  Fewer than 2 samples: nothing changes, n_steps = 0."""
+    smp = np.ascontiguousarray(samples, IMU_SAMPLE_DTYPE)
+    fb = np.ascontiguousarray(frame_bias, np.float32).reshape(6)
+    frame = ImuPreint()
+    steps = np.zeros(max(len(smp) - 1, 1), IMU_STEP_DTYPE) if want_steps else None
+    n = C.c_int(0)
+    h = extractor.h if extractor is not None else None
+    rc = lib().orbfe_imu_preintegrate_frame(h, C.byref(noise), len(smp), _p(smp), float(t_prev), float(t_cur), _p(fb), C.byref(kf),
+                                            C.byref(frame), _p(steps), C.byref(n))
+    if rc != 0:
+        _imu_fail(h, rc, "orbfe_imu_preintegrate_frame")
+    return frame, (steps[:n.value] if want_steps else None), n.value
+
+
+def imu_reintegrate(extractor, noise, bias, steps):
+    """orbfe_imu_reintegrate: Initialize(bias) and IntegrateNewMeasurement over `steps` (IMU_STEP_DTYPE records): Reintegrate(), and
+    MergePrevious() with the two lists concatenated -> ImuPreint"""
+    st = np.ascontiguousarray(steps, IMU_STEP_DTYPE)
+    b = np.ascontiguousarray(bias, np.float32).reshape(6)
+    out = ImuPreint()
+    h = extractor.h if extractor is not None else None
+    rc = lib().orbfe_imu_reintegrate(h, C.byref(noise), _p(b), len(st), _p(st) if len(st) else None, C.byref(out))
+    if rc != 0:
+        _imu_fail(h, rc, "orbfe_imu_reintegrate")
+    return out
+
+
+def imu_predict(extractor, params, state1, kf, frame=None):
+    """orbfe_imu_predict: Tracking::PredictStateIMU with Frame::SetImuPoseVelocity and the inertial link.  state1: Rwb1 (9) twb1 v1 bg1
+    ba1 -> (state [33] float32 = Rcw tcw Rwb twb v bg ba, link: an ImuLink (IMU_FROM_KEYFRAME) or an ImuLinkFree (IMU_FROM_FRAME),
+    info_ok)"""
+    s1 = np.ascontiguousarray(state1, np.float32).reshape(21)
+    state = np.zeros(33, np.float32)
+    link = ImuLinkFree() if params.which == IMU_FROM_FRAME else ImuLink()
+    ok = C.c_int(0)
+    h = extractor.h if extractor is not None else None
+    rc = lib().orbfe_imu_predict(h, C.byref(params), _p(s1), C.byref(kf), C.byref(frame) if frame is not None else None, _p(state),
+                                 C.addressof(link), C.byref(ok))
+    if rc != 0:
+        _imu_fail(h, rc, "orbfe_imu_predict")
+    return state, link, ok.value
+
+
+def imu_frame_batch_device(extractor, noise, params, batch, d_samples_ptr, sample_off, d_t_prev_ptr, d_t_cur_ptr, d_frame_bias_ptr,
+                           d_state1_ptr, d_kf_ptr, d_frame_ptr, d_steps_out_ptr, d_state_in_ptr, d_links_ptr, d_info_ok_ptr, stream=None):
+    """orbfe_imu_frame_batch_device: preintegration, prediction and link of a batch of frames in one launch; sample_off is a HOST array of
+    batch + 1 ints, everything else resident in HBM (raw device pointers as ints); asynchronous on `stream`."""
+    off = np.ascontiguousarray(sample_off, np.int32)
+    assert len(off) == batch + 1
+    extractor._chk(extractor.L.orbfe_imu_frame_batch_device(
+        extractor.h, C.byref(noise), C.byref(params), int(batch), d_samples_ptr, _p(off), d_t_prev_ptr, d_t_cur_ptr, d_frame_bias_ptr,
+        d_state1_ptr, d_kf_ptr, d_frame_ptr, d_steps_out_ptr, d_state_in_ptr, d_links_ptr, d_info_ok_ptr, stream),
+        "orbfe_imu_frame_batch_device")
+
+
+def imu_reintegrate_batch_device(extractor, noise, batch, d_steps_ptr, step_off, d_bias_ptr, d_out_ptr, stream=None):
+    """orbfe_imu_reintegrate_batch_device: one record per step list (step_off: HOST array of batch + 1 ints) in one launch."""
+    off = np.ascontiguousarray(step_off, np.int32)
+    assert len(off) == batch + 1
+    extractor._chk(extractor.L.orbfe_imu_reintegrate_batch_device(extractor.h, C.byref(noise), int(batch), d_steps_ptr, _p(off), d_bias_ptr,
+                                                                  d_out_ptr, stream), "orbfe_imu_reintegrate_batch_device")
 
 
 def initial_bundle_adjustment(extractor, params, kp1, kp2, matches12, points, Rcw1, tcw1, Rcw2, tcw2, want_info=True):
