@@ -1350,6 +1350,120 @@ int orbfe_imu_reintegrate_batch_device(orbfe_handle *h, const orbfe_imu_noise *n
                                        const int *step_off, const float *d_bias, orbfe_imu_preint *d_out, void *stream);
 
 /* -------------------------------------------------------------------------------------------
+ * Tracking::TrackLocalMap once the IMU is initialised, for a batch of frames, resident in HBM (SPEC DECISION S23):
+ *   PreintegrateIMU + PredictStateIMU                       (src/Tracking.cc:163-350)   orbfe_imu_frame_batch_device
+ *   SearchLocalPoints: isInFrustum + SearchByProjection     (:1037-1117)                frustum from the predicted state, on the device
+ *   PoseInertialOptimizationLastKeyFrame / ...LastFrame     (:952 / :946)               the S19 / S20 batch launch
+ *   mnMatchesInliers, the tracked verdict, IncreaseFound    (:958-982)
+ * as launches back to back on one stream: no host synchronisation and no copy in between.
+ * ---------------------------------------------------------------------------------------- */
+/* One block for the whole chain, versioned by struct_size; the nested blocks carry their own struct_size and are checked too.
+ * predict.which chooses the link kind and with it the optimisation: ORBFE_IMU_FROM_KEYFRAME reads pose_keyframe, ORBFE_IMU_FROM_FRAME
+ * reads pose_frame (the other one is not looked at). */
+typedef struct orbfe_track_inertial_params {
+    int struct_size;                            /* sizeof(orbfe_track_inertial_params) at the caller's compile time */
+    int inlier_threshold;                       /* tracked = matches_inliers >= inlier_threshold; Tracking passes 8 */
+    orbfe_track_params track;                   /* the frame grid and the parameters of SearchByProjection */
+    orbfe_imu_noise noise;                      /* as orbfe_imu_frame_batch_device */
+    orbfe_imu_predict_params predict;           /* as orbfe_imu_frame_batch_device */
+    orbfe_frustum frustum;                      /* TEMPLATE: bounds, camera, mbf, log_scale_factor, n_levels, camera_model; its rcw /
+                                                 * tcw / twc are ignored -- the pose is the predicted one, per frame, on the device */
+    orbfe_pose_inertial_params pose_keyframe;   /* S19's block */
+    orbfe_pose_inertial_prev_params pose_frame; /* S20's block */
+} orbfe_track_inertial_params;
+
+/* The pointers of orbfe_track_inertial_batch_device: DEVICE pointers except sample_off.  Versioned by struct_size.  With B = batch,
+ * M = n_points and kp_stride as given to the call: */
+typedef struct orbfe_track_inertial_io {
+    int struct_size;                  /* sizeof(orbfe_track_inertial_io) at the caller's compile time */
+    int reserved;                     /* 0 */
+    /* ---- in: orbfe_imu_frame_batch_device's ---- */
+    const orbfe_imu_sample *d_samples;
+    const int *sample_off;            /* HOST, B + 1 ascending offsets into d_samples */
+    const double *d_t_prev, *d_t_cur; /* one per frame */
+    const float *d_frame_bias;        /* 6 per frame */
+    const float *d_state1;            /* 21 per frame */
+    orbfe_imu_preint *d_kf;           /* in / out, one per frame */
+    orbfe_imu_preint *d_frame;        /* out (read as it stands by a frame with fewer than 2 samples), one per frame */
+    orbfe_imu_step *d_steps_out;      /* may be NULL */
+    /* ---- in: the frames as orbfe_extract_batch_device wrote them ---- */
+    const orbfe_keypoint *d_kp;       /* B x kp_stride */
+    const uint8_t *d_desc;            /* B x kp_stride x 32 */
+    const int *d_n;                   /* B */
+    /* ---- in: the local maps ---- */
+    const int *d_ids;                 /* B x M: id >= 0, ~id = skipped for this frame, outside the map = no point; NULL only when M == 0 */
+    const orbfe_pose_imu_prior *d_priors; /* one per frame with ORBFE_IMU_FROM_FRAME; NULL otherwise */
+    /* ---- out ---- */
+    float *d_state_in;                /* 33 per frame: the predicted Rcw tcw Rwb twb v bg ba */
+    int *d_info_ok;                   /* one per frame */
+    orbfe_map_point *d_mp_out;        /* B x M records; in_view is IncreaseVisible (:1073); NULL only when M == 0 */
+    int *d_match_out;                 /* B x kp_stride: position in the frame's id list, or -1 */
+    int *d_n_matches;                 /* B */
+    float *d_state_out;               /* 21 per frame: the optimised Rwb twb v bg ba */
+    double *d_H_out;                  /* 225 per frame (ORBFE_IMU_FROM_KEYFRAME) or 900 per frame (ORBFE_IMU_FROM_FRAME) */
+    double *d_Hprior_out;             /* ORBFE_IMU_FROM_FRAME: 225 per frame, may be NULL; ignored otherwise */
+    uint8_t *d_outlier;               /* B x kp_stride bytes, d_n[b] are written */
+    int *d_n_inliers;                 /* B: the optimisation's return value */
+    int *d_accepted;                  /* B: S20's verdict; written as 1 with ORBFE_IMU_FROM_KEYFRAME */
+    uint8_t *d_found;                 /* B x M bytes: 1 where IncreaseFound() runs (:967), 0 elsewhere; NULL only when M == 0 */
+    int *d_matches_inliers;           /* B: mnMatchesInliers (:969-976) */
+    int *d_tracked;                   /* B: matches_inliers >= inlier_threshold */
+    float *d_Tcw_out;                 /* 12 per frame, Rcw then tcw: SetImuPoseVelocity on the optimised Rwb / twb; the predicted pose
+                                       * where ORBFE_IMU_FROM_FRAME did not accept (src/Optimizer.cc:4208) */
+} orbfe_track_inertial_io;
+
+/* The chain above for `batch` independent frames.  The frames' keypoints, descriptors and counts are orbfe_extract_batch_device's
+ * outputs (kp_stride == orbfe_max_keypoints(), <= 65536); frame b's local map points are the entries d_ids[b * n_points ..] of the
+ * resident `map`.  Numerics: SPEC DECISION S23 for the glue -- the frustum from the predicted state, the
+ * hand-over of point rows and depths, the statistics, Tcw_out; S22, S8, the matcher's, S19 / S20 for the stages, whose bytes are those
+ * of their own entry points: frame b's outputs equal orbfe_imu_preintegrate_frame + orbfe_imu_predict, orbfe_project_map_points with
+ * the frustum of S23, orbfe_match_projection (init_obs == NULL: mvpMapPoints is empty when SearchLocalPoints starts, :908-923) and
+ * orbfe_pose_inertial_optimization_last_keyframe / _last_frame (mp_index = the matches, the resident rows, track_depth of the
+ * records), byte for byte.  Statistics (mono, mbOnlyTracking == false): for keypoint i < d_n[b] with m = match[i] >= 0,
+ * found[m] = !outlier[i] and matches_inliers += (!outlier[i] && record[m].observations > 0).
+ * Asynchronous on `stream` (NULL == the handle's stream): the S22 launch, the projection launch, the three matcher launches, the S19
+ * or S20 launch and the statistics launch, back to back; no host synchronisation.  Gathered descriptors, point rows, depths and the
+ * links live in the handle's matcher arena (grown on first use, ordered against its other users by the event hand-over).
+ * n_points == 0 is valid: the inertial edges alone give a full-rank system.
+ * ORBFE_ERR_INVALID_ARG: a wrong struct_size (outer or nested), a required NULL, batch < 1, n_points < 0, kp_stride outside [1, 65536],
+ * descending sample_off, d_priors missing with ORBFE_IMU_FROM_FRAME, frustum.n_levels above the handle's, a map of another handle.
+ * ORBFE_ERR_UNSUPPORTED: KannalaBrandt8 (frustum or pose block), stereo != 0.  All decided before the device is touched. */
+int orbfe_track_inertial_batch_device(orbfe_handle *h, const orbfe_track_inertial_params *p, int batch, int kp_stride,
+                                      const orbfe_map *map, int n_points, const orbfe_track_inertial_io *io, void *stream);
+
+/* What orbfe_track_frame_inertial hands back besides the frame's features.  HOST pointers; versioned by struct_size.  Every pointer
+ * is required except steps_out, link_out and Hprior_out; mp_out and found are required when n_points > 0. */
+typedef struct orbfe_track_inertial_result {
+    int struct_size;          /* sizeof(orbfe_track_inertial_result) at the caller's compile time */
+    int n_steps;              /* out: steps integrated (n_samples - 1, or 0) */
+    orbfe_imu_step *steps_out;/* n_samples - 1 entries, may be NULL */
+    float *state_in;          /* 33 */
+    void *link_out;           /* an orbfe_imu_link or orbfe_imu_link_free by predict.which, may be NULL */
+    int info_ok;              /* out */
+    int n_matches;            /* out */
+    orbfe_map_point *mp_out;  /* n_points */
+    int *match_out;           /* orbfe_max_keypoints() ints; the first *n_out are meaningful */
+    float *state_out;         /* 21 */
+    double *H_out;            /* 225 or 900 */
+    double *Hprior_out;       /* 225, ORBFE_IMU_FROM_FRAME only, may be NULL */
+    uint8_t *outlier;         /* orbfe_max_keypoints() bytes; the first *n_out are meaningful */
+    uint8_t *found;           /* n_points */
+    int n_inliers, accepted, matches_inliers, tracked;  /* out */
+    float Tcw[12];            /* out */
+} orbfe_track_inertial_result;
+
+/* The same chain for ONE frame from host pointers, image in, results out: one upload (the frame, then samples, records, ids and prior
+ * as one block), orbfe_extract's device path, the chain above with batch == 1, ONE result download and ONE synchronisation.  gray /
+ * pitch, kp_out / desc_out / n_out / per_level_counts as orbfe_track_frame_map.  kf: in / out; frame: out (in, when n_samples < 2).
+ * prior: required with ORBFE_IMU_FROM_FRAME.  Results equal orbfe_extract followed by orbfe_track_inertial_batch_device on that frame.
+ * Refusals as the batch call's, plus the records' struct_size.  No graph capture. */
+int orbfe_track_frame_inertial(orbfe_handle *h, const orbfe_track_inertial_params *p, const uint8_t *gray, int pitch, int n_samples,
+                               const orbfe_imu_sample *samples, double t_prev, double t_cur, const float *frame_bias, const float *state1,
+                               orbfe_imu_preint *kf, orbfe_imu_preint *frame, const orbfe_map *map, int n_points, const int *ids,
+                               const orbfe_pose_imu_prior *prior, orbfe_keypoint *kp_out, uint8_t *desc_out, int *n_out,
+                               int *per_level_counts, orbfe_track_inertial_result *res);
+
+/* -------------------------------------------------------------------------------------------
  * Bundle adjustment of the initial map: the line behind orbfe_two_view_reconstruct (src/Tracking.cc:698)
  * ---------------------------------------------------------------------------------------- */
 /* the camera and the constants of Optimizer::GlobalBundleAdjustemnt(map, 20) (src/Optimizer.cc:60-369); versioned by struct_size */

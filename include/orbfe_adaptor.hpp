@@ -1837,6 +1837,123 @@ private:
     orbfe_imu_predict_params mParams;
 };
 
+// Tracking::Track for one frame once the IMU is initialised, as ONE call (orbfe_track_frame_inertial, SPEC DECISION S23): Frame::Frame
+// -> ExtractORB, PreintegrateIMU, PredictStateIMU, TrackLocalMap -- SearchLocalPoints against the predicted pose, the inertial pose
+// optimisation (src/Tracking.cc:946 / :952) and the loop of :958-982.  It owns what the reference keeps between frames for this: the
+// two preintegration records (mpImuPreintegratedFromLastKF, and the frame's own) and the prior the last-frame optimisation leaves
+// for the next frame (pFrame->mpcpi).  The local map points are named by id out of a ResidentMap (id >= 0, ~id = mnLastFrameSeen ==
+// this frame, src/Tracking.cc:1066).  The caller keeps the queue handling (:201-232), the map-point bookkeeping from `found` /
+// `match` (IncreaseVisible for in_view records, IncreaseFound for found ones, mvpMapPoints, mvbOutlier) and the key-frame decision
+// (NeedNewKeyFrame reads matchesInliers).
+class InertialFrameTracker {
+public:
+    struct Result {
+        int n = 0;                          // keypoints; 0: the reference returns before Track() (:158-159)
+        std::vector<KeyPoint> keys;
+        std::vector<uint8_t> descriptors;   // n x 32
+        std::vector<orbfe_imu_step> steps;  // for mvMeasurements
+        float predicted[33];                // Rcw tcw Rwb twb v bg ba
+        float state[21];                    // the optimised Rwb twb v bg ba
+        float Tcw[12];                      // Rcw then tcw: what SetImuPoseVelocity leaves in the frame
+        std::vector<orbfe_map_point> points;// per id slot: the mTrack* fields; in_view = IncreaseVisible
+        std::vector<int> match;             // per keypoint: the id slot in mvpMapPoints, or -1
+        std::vector<uint8_t> outlier;       // mvbOutlier
+        std::vector<uint8_t> found;         // per id slot: IncreaseFound
+        int nMatches = 0, nInliers = 0, matchesInliers = 0;
+        bool accepted = true, tracked = false, infoOk = false;
+    };
+
+    // `params`: grid, matcher, noise, extrinsics, the frustum template and both pose blocks; predict.which is set per call
+    InertialFrameTracker(ORBextractor& extractor, const orbfe_track_inertial_params& params) : mExtractor(extractor), mParams(params)
+    {
+        mFromLastKF.struct_size = mFromLastFrame.struct_size = (int)sizeof(orbfe_imu_preint);
+        mPrior.struct_size = (int)sizeof mPrior;
+    }
+
+    // a new key frame: mpImuPreintegratedFromLastKF = new IMU::Preintegrated(bias, calib) (src/Tracking.cc:1339), or a record the
+    // caller carries over
+    void ResetFromLastKF(const orbfe_imu_preint& fresh) { mFromLastKF = fresh; }
+    const orbfe_imu_preint& FromLastKF() const { return mFromLastKF; }
+    const orbfe_imu_preint& FromLastFrame() const { return mFromLastFrame; }
+    bool HasPrior() const { return mHasPrior; }
+    void DropPrior() { mHasPrior = false; }
+
+    // mapUpdated (mbMapUpdated, :946-952) or no prior yet: against the last key frame, `startState` = its Rwb twb v bg ba; else against
+    // the last frame, `startState` = that frame's.  lastFrameBias = mLastFrame->mImuBias.
+    Result Track(const GrayImageView& im, const std::vector<orbfe_imu_sample>& imuFromLastFrame, double prevStamp, double curStamp,
+                 const float* lastFrameBias, const float* startState, bool mapUpdated, const ResidentMap& map, const std::vector<int>& ids)
+    {
+        orbfe_handle* h = mExtractor.handle();
+        const int cap = mExtractor.maxKeypoints(), M = (int)ids.size(), nS = (int)imuFromLastFrame.size();
+        const bool fromFrame = !mapUpdated && mHasPrior;
+        mParams.predict.which = fromFrame ? ORBFE_IMU_FROM_FRAME : ORBFE_IMU_FROM_KEYFRAME;
+        Result R;
+        R.keys.resize((size_t)cap);
+        R.descriptors.resize((size_t)cap * ORBFE_DESC_BYTES);
+        R.steps.resize((size_t)(nS > 1 ? nS - 1 : 1));
+        R.points.resize((size_t)(M > 0 ? M : 1));
+        R.match.assign((size_t)cap, -1);
+        R.outlier.assign((size_t)cap, 0);
+        R.found.assign((size_t)(M > 0 ? M : 1), 0);
+        std::vector<double> H(fromFrame ? 900 : 225), Hp(225);
+        orbfe_track_inertial_result res{};
+        res.struct_size = (int)sizeof res;
+        res.steps_out = R.steps.data();
+        res.state_in = R.predicted;
+        res.mp_out = R.points.data();
+        res.match_out = R.match.data();
+        res.state_out = R.state;
+        res.H_out = H.data();
+        res.Hprior_out = fromFrame ? Hp.data() : nullptr;
+        res.outlier = R.outlier.data();
+        res.found = R.found.data();
+        orbfe_detail::check(orbfe_track_frame_inertial(h, &mParams, im.data, im.pitch, nS, imuFromLastFrame.data(), prevStamp, curStamp,
+                                                       lastFrameBias, startState, &mFromLastKF, &mFromLastFrame, map.get(), M, ids.data(),
+                                                       fromFrame ? &mPrior : nullptr, reinterpret_cast<orbfe_keypoint*>(R.keys.data()),
+                                                       R.descriptors.data(), &R.n, nullptr, &res),
+                            h, "orbfe_track_frame_inertial");
+        R.keys.resize((size_t)R.n);
+        R.descriptors.resize((size_t)R.n * ORBFE_DESC_BYTES);
+        R.steps.resize((size_t)res.n_steps);
+        R.points.resize((size_t)M);
+        R.found.resize((size_t)M);
+        R.match.resize((size_t)R.n);
+        R.outlier.resize((size_t)R.n);
+        std::memcpy(R.Tcw, res.Tcw, sizeof R.Tcw);
+        R.nMatches = res.n_matches;
+        R.nInliers = res.n_inliers;
+        R.matchesInliers = res.matches_inliers;
+        R.accepted = res.accepted != 0;
+        R.tracked = res.tracked != 0;
+        R.infoOk = res.info_ok != 0;
+        // pFrame->mpcpi = new ConstraintPoseImu(Rwb, twb, v, bg, ba, H) (src/Optimizer.cc:3841, :4271): the optimised state and the raw
+        // Hessian block; the constructor's eigenvalue clamp (include/G2oTypes.h) stays with the caller, through Prior()
+        if (R.accepted) {
+            const double* src = fromFrame ? Hp.data() : H.data();
+            for (int i = 0; i < 9; i++) mPrior.Rwb[i] = (double)R.state[i];
+            for (int i = 0; i < 3; i++) {
+                mPrior.twb[i] = (double)R.state[9 + i];
+                mPrior.vwb[i] = (double)R.state[12 + i];
+                mPrior.bg[i] = (double)R.state[15 + i];
+                mPrior.ba[i] = (double)R.state[18 + i];
+            }
+            std::memcpy(mPrior.H, src, sizeof mPrior.H);
+            mHasPrior = true;
+        }
+        return R;
+    }
+
+    // the prior as the caller wants the next frame to see it (after the constructor's clamp of negative eigenvalues)
+    orbfe_pose_imu_prior& Prior() { return mPrior; }
+
+private:
+    ORBextractor& mExtractor;
+    orbfe_track_inertial_params mParams;
+    orbfe_imu_preint mFromLastKF{}, mFromLastFrame{};
+    orbfe_pose_imu_prior mPrior{};
+    bool mHasPrior = false;
+};
+
 // The numerical core of Tracking::CreateInitialMapMonocular (src/Tracking.cc:698-729) as ONE device call and a host step:
 // Optimizer::GlobalBundleAdjustemnt(map, 20) -- two key frames of which the first is fixed, every initial map point seen once in
 // either -- is orbfe_initial_bundle_adjustment (SPEC DECISION S17); KeyFrame::ComputeSceneMedianDepth(2) (src/KeyFrame.cc:859-892)

@@ -350,12 +350,28 @@ ORBFE_HD inline void preint_deltas(const PreintRec& R, const float* bg, const fl
     normalize_rotation(Pf, dRb);
 }
 
+// SetImuPoseVelocity (Frame.cc:221-238): Rcw = Rcb Rwb^T, tcw = Rcb (-(Rwb^T twb)) + tcb.  One text for the prediction below and for
+// the pose TrackLocalMap hands on after the inertial optimisation (kernels_track_inertial.hip, SPEC DECISION S23).
+ORBFE_HD inline void set_imu_pose(const float (&Rwb)[9], const float (&twb)[3], const float (&Rcb)[9], const float* tcb, float (&Rcw)[9],
+                                  float (&tcw)[3])
+{
+    float Rbw[9], t[3], nt[3], ct[3];
+    transpose3(Rwb, Rbw);
+    mul3(Rcb, Rbw, Rcw);
+    matvec3f(Rbw, twb, t);
+    ORBFE_UNROLL
+    for (int i = 0; i < 3; i++) nt[i] = -t[i];
+    matvec3f(Rcb, nt, ct);
+    ORBFE_UNROLL
+    for (int i = 0; i < 3; i++) tcw[i] = ct[i] + tcb[i];
+}
+
 // PredictStateIMU (Tracking.cc:293-350) and SetImuPoseVelocity (Frame.cc:221-238).  s1 = Rwb1 (9) twb1 v1 bg1 ba1; out = Rcw (9) tcw
 // Rwb twb v bg ba, the biases being the start's (:323, :345).
 ORBFE_HD inline void preint_predict(const float* s1, const float (&dRb)[9], const float (&dVb)[3], const float (&dPb)[3], float t12,
                                     float gravity, const float* Rcb_, const float* tcb, float* out)
 {
-    float Rwb1[9], Rcb[9], prod[9], Rwb2[9], Rbw2[9], Rcw[9], rp[3], rv[3], twb2[3], v2[3], t[3], nt[3], ct[3];
+    float Rwb1[9], Rcb[9], prod[9], Rwb2[9], Rcw[9], rp[3], rv[3], twb2[3], v2[3], tcw[3];
     ORBFE_UNROLL
     for (int i = 0; i < 9; i++) {
         Rwb1[i] = s1[i];
@@ -371,12 +387,7 @@ ORBFE_HD inline void preint_predict(const float* s1, const float (&dRb)[9], cons
         twb2[i] = ((s1[9 + i] + s1[12 + i] * t12) + 0.5f * t12 * t12 * g[i]) + rp[i];
         v2[i] = (s1[12 + i] + t12 * g[i]) + rv[i];
     }
-    transpose3(Rwb2, Rbw2);
-    mul3(Rcb, Rbw2, Rcw);
-    matvec3f(Rbw2, twb2, t);
-    ORBFE_UNROLL
-    for (int i = 0; i < 3; i++) nt[i] = -t[i];
-    matvec3f(Rcb, nt, ct);
+    set_imu_pose(Rwb2, twb2, Rcb, tcb, Rcw, tcw);
     ORBFE_UNROLL
     for (int i = 0; i < 9; i++) {
         out[i] = Rcw[i];
@@ -384,7 +395,7 @@ ORBFE_HD inline void preint_predict(const float* s1, const float (&dRb)[9], cons
     }
     ORBFE_UNROLL
     for (int i = 0; i < 3; i++) {
-        out[9 + i] = ct[i] + tcb[i];
+        out[9 + i] = tcw[i];
         out[21 + i] = twb2[i];
         out[24 + i] = v2[i];
         out[27 + i] = s1[15 + i];

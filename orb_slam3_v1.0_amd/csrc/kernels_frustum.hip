@@ -114,6 +114,66 @@ __global__ __launch_bounds__(256) void frustum_gather_kernel(const orbfe_frustum
     dd[1] = d1;
 }
 
+// The inertial chain's form (orbfe_track_inertial_batch_device, SPEC DECISION S23): frame b's pose is what the prediction left in
+// stateIn[33 b ..) -- Rcw (9), tcw (3) -- so the frustum is built HERE from it and the template T (bounds, camera, mbf, scale): nothing
+// goes through the host between PredictStateIMU and isInFrustum.  twc_k = -((R_0k t_0 + R_1k t_1) + R_2k t_2): mTcw.inverse()
+// (src/Frame.cc:234) with R^T taken by index.  Ids resolve as in frustum_gather_kernel.  Besides the record and the descriptor, what
+// the pose optimisation reads is written next to them: the point row as it stands in the map (zeros for an id outside it) and the
+// record's track_depth, one float per slot.  rowOut / descOut are 16-byte aligned (the matcher arena).
+__global__ __launch_bounds__(256) void track_frustum_gather_kernel(orbfe_frustum T, const float* __restrict__ stateIn,
+                                                                   const int* __restrict__ ids, int M, int mapCap,
+                                                                   const orbfe_world_point* __restrict__ mapPts,
+                                                                   const uint8_t* __restrict__ mapDesc, orbfe_map_point* __restrict__ out,
+                                                                   uint8_t* __restrict__ descOut, orbfe_world_point* __restrict__ rowOut,
+                                                                   float* __restrict__ depthOut)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= M) return;
+    const int b = blockIdx.y;
+    const float* __restrict__ st = stateIn + (size_t)b * 33;  // block-uniform: scalar loads
+    orbfe_frustum F = T;
+#pragma unroll
+    for (int k = 0; k < 9; k++) F.rcw[k] = st[k];
+#pragma unroll
+    for (int k = 0; k < 3; k++) F.tcw[k] = st[9 + k];
+#pragma unroll
+    for (int k = 0; k < 3; k++) F.twc[k] = -((F.rcw[k] * F.tcw[0] + F.rcw[3 + k] * F.tcw[1]) + F.rcw[6 + k] * F.tcw[2]);
+    const size_t slot = (size_t)b * M + i;
+    const int raw = ids[slot];
+    const int id = raw < 0 ? ~raw : raw;
+    orbfe_world_point p{};
+    uint4 r0 = make_uint4(0, 0, 0, 0), r1 = r0, d0 = r0, d1 = r0;
+    if (id < mapCap) {
+        const uint4* rp = reinterpret_cast<const uint4*>(mapPts + id);
+        r0 = rp[0];
+        r1 = rp[1];
+        const uint4* dp = reinterpret_cast<const uint4*>(mapDesc + (size_t)id * 32);
+        d0 = dp[0];
+        d1 = dp[1];
+        p.x = __uint_as_float(r0.x);
+        p.y = __uint_as_float(r0.y);
+        p.z = __uint_as_float(r0.z);
+        p.min_distance = __uint_as_float(r0.w);
+        p.max_distance = __uint_as_float(r1.x);
+        p.bad = (int)r1.y;
+        p.observations = (int)r1.z;
+        p.skip = raw < 0 ? 1 : 0;
+    } else {
+        p.bad = 1;
+        p.skip = 1;
+    }
+    orbfe_map_point o;
+    frustum_point(F, 0, &p, &o, nullptr);
+    out[slot] = o;
+    uint4* dd = reinterpret_cast<uint4*>(descOut + slot * 32);
+    dd[0] = d0;
+    dd[1] = d1;
+    uint4* rr = reinterpret_cast<uint4*>(rowOut + slot);
+    rr[0] = r0;
+    rr[1] = r1;
+    depthOut[slot] = o.track_depth;
+}
+
 __global__ __launch_bounds__(256) void map_scatter_kernel(int n, const int* __restrict__ ids, const orbfe_world_point* __restrict__ pts,
                                                           const uint8_t* __restrict__ desc, int mapCap,
                                                           orbfe_world_point* __restrict__ mapPts, uint8_t* __restrict__ mapDesc)
@@ -175,6 +235,23 @@ int frustum_gather_launch(hipStream_t s, int B, const orbfe_frustum* dF, const i
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         err = std::string("frustum_gather_kernel: ") + hipGetErrorString(e);
+        return ORBFE_ERR_HIP;
+    }
+    return ORBFE_OK;
+}
+
+static_assert(sizeof(orbfe_world_point) == 32 && sizeof(orbfe_map_point) == 32, "two 16-byte halves per record");
+
+int track_frustum_gather_launch(hipStream_t s, int B, const orbfe_frustum* T, const float* dStateIn, const int* dIds, int M, int mapCap,
+                                const orbfe_world_point* mapPts, const uint8_t* mapDesc, orbfe_map_point* dOut, uint8_t* dDescOut,
+                                orbfe_world_point* dRowOut, float* dDepthOut, std::string& err)
+{
+    if (B == 0 || M == 0) return ORBFE_OK;
+    hipLaunchKernelGGL(track_frustum_gather_kernel, dim3((M + 255) / 256, B), dim3(256), 0, s, *T, dStateIn, dIds, M, mapCap, mapPts, mapDesc,
+                       dOut, dDescOut, dRowOut, dDepthOut);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        err = std::string("track_frustum_gather_kernel: ") + hipGetErrorString(e);
         return ORBFE_ERR_HIP;
     }
     return ORBFE_OK;

@@ -161,6 +161,17 @@ int frustum_launch_dev(hipStream_t s, const orbfe_frustum* dF, int n, const orbf
 int frustum_gather_launch(hipStream_t s, int B, const orbfe_frustum* dF, const int* dIds, int M, int mapCap,
                           const orbfe_world_point* mapPts, const uint8_t* mapDesc, orbfe_map_point* dOut, uint8_t* dDescOut,
                           float* dProjXR, std::string& err);
+// the same with the frustum of frame b built on the device from dStateIn[33 b ..) and the template *T, plus the point rows and depths
+// the inertial pose optimisations read (SPEC DECISION S23); dDescOut / dRowOut 16-byte aligned
+int track_frustum_gather_launch(hipStream_t s, int B, const orbfe_frustum* T, const float* dStateIn, const int* dIds, int M, int mapCap,
+                                const orbfe_world_point* mapPts, const uint8_t* mapDesc, orbfe_map_point* dOut, uint8_t* dDescOut,
+                                orbfe_world_point* dRowOut, float* dDepthOut, std::string& err);
+// kernels_track_inertial.hip (Tracking::TrackLocalMap with the IMU for a batch of frames, SPEC DECISION S23)
+int track_inertial_check(const orbfe_track_inertial_params* P, std::string& err);
+int track_inertial_batch_device(MatchScratch& m, hipStream_t s, const orbfe_track_inertial_params* P, const float* dScaleFactors,
+                                const float* invLevelSigma2, int nLevels, int batch, int kpStride, int mapCap,
+                                const orbfe_world_point* mapPts, const uint8_t* mapDesc, int M, const orbfe_track_inertial_io* io,
+                                void** dLinksOut, std::string& err);
 int map_scatter_launch(hipStream_t s, int n, const int* dIds, const orbfe_world_point* dPts, const uint8_t* dDesc, int mapCap,
                        orbfe_world_point* mapPts, uint8_t* mapDesc, std::string& err);
 

@@ -182,6 +182,11 @@ struct orbfe_handle {
     int iniCapN1 = -1;
     size_t iniScratchBytes = 0;
     GraphCache<IniKey> iniGraphs;
+    // orbfe_track_frame_inertial: extract -> the inertial TrackLocalMap chain with batch == 1 (plain launches, no graph)
+    // in:  [image | times | bias | state1 | key-frame record | frame record | prior | samples | ids]
+    // out: [n, status | per-level | keypoints | descriptors | the chain's outputs]
+    ChainBlocks tin;
+    size_t tinInBytes = 0, tinOutBytes = 0;
     std::mutex mu;
     std::string err;
     // objects that keep a pointer to this handle: orbfe_destroy releases their device memory and orphans them (h = null), so
@@ -310,7 +315,7 @@ void destroy_impl(orbfe_handle* h)
     match_scratch_free(h->trackMatch);
     h->refGraphs.drop();
     h->iniGraphs.drop();
-    for (ChainBlocks* b : {&h->ini, &h->ref, &h->trk}) chain_blocks_free(h, *b);
+    for (ChainBlocks* b : {&h->ini, &h->ref, &h->trk, &h->tin}) chain_blocks_free(h, *b);
     for (auto& g : h->graphs)
         if (g.second) (void)hipGraphExecDestroy(g.second);
     void* dptrs[] = {h->dP, h->ws, h->dCand, h->dNodeOf, h->dCounters, h->dLvlKp, h->dTileRows, h->dQtScratch, h->dTabs,
@@ -2857,6 +2862,220 @@ int orbfe_imu_reintegrate_batch_device(orbfe_handle* h, const orbfe_imu_noise* n
     return imu_call(h, (hipStream_t)stream_, [&](hipStream_t s, std::string& e) {
         return imu_reintegrate_batch_device(h->match, s, noise, batch, d_steps, step_off, d_bias, d_out, e);
     });
+}
+
+// ---- Tracking::TrackLocalMap with the IMU, batched and resident (SPEC DECISION S23) ----
+
+// what the arguments alone decide, for both entry points: nothing is dereferenced but the two blocks, no handle is looked at
+static int track_inertial_refuse(const orbfe_track_inertial_params* p, int batch, int kp_stride, const orbfe_map* map, int M,
+                                 const orbfe_track_inertial_io* io, std::string& err)
+{
+    if (!p || !io) return ORBFE_ERR_INVALID_ARG;
+    const int crc = track_inertial_check(p, err);
+    if (crc != ORBFE_OK) return crc;
+    if (io->struct_size != (int)sizeof(orbfe_track_inertial_io)) {
+        err = "orbfe_track_inertial_io.struct_size does not match this library (rebuild the caller against include/orbfe.h)";
+        return ORBFE_ERR_INVALID_ARG;
+    }
+    if (imu_check_offsets(batch, io->sample_off) != ORBFE_OK) return ORBFE_ERR_INVALID_ARG;
+    if (M < 0 || kp_stride < 1 || kp_stride > 65536 || !map) return ORBFE_ERR_INVALID_ARG;
+    const bool fromFrame = p->predict.which == ORBFE_IMU_FROM_FRAME;
+    if (!io->d_samples || !io->d_t_prev || !io->d_t_cur || !io->d_frame_bias || !io->d_state1 || !io->d_kf || !io->d_frame || !io->d_kp ||
+        !io->d_desc || !io->d_n || !io->d_state_in || !io->d_info_ok || !io->d_match_out || !io->d_n_matches || !io->d_state_out ||
+        !io->d_H_out || !io->d_outlier || !io->d_n_inliers || !io->d_accepted || !io->d_matches_inliers || !io->d_tracked ||
+        !io->d_Tcw_out || (fromFrame && !io->d_priors) || (M > 0 && (!io->d_ids || !io->d_mp_out || !io->d_found)))
+        return ORBFE_ERR_INVALID_ARG;
+    return ORBFE_OK;
+}
+
+int orbfe_track_inertial_batch_device(orbfe_handle* h, const orbfe_track_inertial_params* p, int batch, int kp_stride, const orbfe_map* map,
+                                      int n_points, const orbfe_track_inertial_io* io, void* stream_)
+{
+    std::string err;
+    const int crc = track_inertial_refuse(p, batch, kp_stride, map, n_points, io, err);
+    if (crc != ORBFE_OK) return imu_refuse(h, crc, err);
+    if (!h) return ORBFE_ERR_INVALID_ARG;
+    if (map->h != h || p->frustum.n_levels > h->nLevels || n_points > (1 << 24)) return ORBFE_ERR_INVALID_ARG;
+    return imu_call(h, (hipStream_t)stream_, [&](hipStream_t s, std::string& e) {
+        return track_inertial_batch_device(h->match, s, p, h->dSf, h->invSig2, h->nLevels, batch, kp_stride, map->cap, map->dPts, map->dDesc,
+                                           n_points, io, nullptr, e);
+    });
+}
+
+int orbfe_track_frame_inertial(orbfe_handle* h, const orbfe_track_inertial_params* p, const uint8_t* gray, int pitch, int n_samples,
+                               const orbfe_imu_sample* samples, double t_prev, double t_cur, const float* frame_bias, const float* state1,
+                               orbfe_imu_preint* kf, orbfe_imu_preint* frame, const orbfe_map* map, int M, const int* ids,
+                               const orbfe_pose_imu_prior* prior, orbfe_keypoint* kp_out, uint8_t* desc_out, int* n_out, int* per_level,
+                               orbfe_track_inertial_result* res)
+{
+    if (!p || !res) return ORBFE_ERR_INVALID_ARG;
+    std::string err;
+    int crc = track_inertial_check(p, err);
+    if (crc == ORBFE_OK) crc = imu_check(nullptr, nullptr, kf, frame, err);
+    if (crc == ORBFE_OK && res->struct_size != (int)sizeof(orbfe_track_inertial_result)) {
+        err = "orbfe_track_inertial_result.struct_size does not match this library (rebuild the caller against include/orbfe.h)";
+        crc = ORBFE_ERR_INVALID_ARG;
+    }
+    if (crc != ORBFE_OK) return imu_refuse(h, crc, err);
+    const bool fromFrame = p->predict.which == ORBFE_IMU_FROM_FRAME;
+    if (fromFrame && prior && prior->struct_size != (int)sizeof(orbfe_pose_imu_prior)) return ORBFE_ERR_INVALID_ARG;
+    if (!gray || n_samples < 0 || (n_samples > 0 && !samples) || !frame_bias || !state1 || !kf || !frame || !map || M < 0 ||
+        (M > 0 && (!ids || !res->mp_out || !res->found)) || (fromFrame && !prior) || !kp_out || !desc_out || !n_out || !res->state_in ||
+        !res->match_out || !res->state_out || !res->H_out || !res->outlier)
+        return ORBFE_ERR_INVALID_ARG;
+    if (!h) return ORBFE_ERR_INVALID_ARG;
+    if (map->h != h || p->frustum.n_levels > h->nLevels || M > (1 << 24) || pitch < h->prm.image_width || pitch >= (1 << 24))
+        return ORBFE_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    const int cap = h->P.kpCapFrame, nL = h->nLevels;
+    if (cap > 65536) return ORBFE_ERR_UNSUPPORTED;  // the pose kernels' bound on kp_stride
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+
+    // ---- layout ----
+    const size_t linkBytes = fromFrame ? sizeof(orbfe_imu_link_free) : sizeof(orbfe_imu_link);
+    const size_t hBytes = (fromFrame ? 900 : 225) * sizeof(double);
+    const int Mp = std::max(M, 1), nS = std::max(n_samples, 1);
+    ChainPrefix L{};
+    size_t out = chain_prefix_layout(h, L);
+    size_t in = L.inFrame;
+    const size_t iTimes = take256(in, 2 * sizeof(double));
+    const size_t iBias = take256(in, 6 * sizeof(float));
+    const size_t iState1 = take256(in, 21 * sizeof(float));
+    const size_t iKf = take256(in, sizeof(orbfe_imu_preint));
+    const size_t iFrame = take256(in, sizeof(orbfe_imu_preint));
+    const size_t iPrior = take256(in, sizeof(orbfe_pose_imu_prior));
+    const size_t iSamples = take256(in, (size_t)nS * sizeof(orbfe_imu_sample));
+    const size_t iIds = take256(in, (size_t)Mp * sizeof(int));
+    // the records come back too: they sit in the input block on the device and are copied into the result block behind the chain
+    const size_t oKf = take256(out, sizeof(orbfe_imu_preint));
+    const size_t oFrame = take256(out, sizeof(orbfe_imu_preint));
+    const size_t oSteps = take256(out, (size_t)nS * sizeof(orbfe_imu_step));
+    const size_t oStateIn = take256(out, 33 * sizeof(float));
+    const size_t oLink = take256(out, linkBytes);
+    const size_t oInts = take256(out, 8 * sizeof(int));  // info_ok, n_matches, n_inliers, accepted, matches_inliers, tracked
+    const size_t oMps = take256(out, (size_t)Mp * sizeof(orbfe_map_point));
+    const size_t oMatch = take256(out, (size_t)cap * sizeof(int));
+    const size_t oStateOut = take256(out, 21 * sizeof(float));
+    const size_t oH = take256(out, hBytes);
+    const size_t oHp = take256(out, 225 * sizeof(double));
+    const size_t oOutlier = take256(out, (size_t)cap);
+    const size_t oFound = take256(out, (size_t)Mp);
+    const size_t oTcw = take256(out, 12 * sizeof(float));
+    if (in > h->tinInBytes || out > h->tinOutBytes) {
+        HIPCHK(h, hipStreamSynchronize(s));
+        h->tinInBytes = h->tinOutBytes = 0;
+        const size_t wantIn = in + in / 4, wantOut = out + out / 4;
+        const int rc = chain_blocks_alloc(h, h->tin, wantIn, wantOut, wantOut, "orbfe_track_frame_inertial");
+        if (rc != ORBFE_OK) return rc;
+        h->tinInBytes = wantIn;
+        h->tinOutBytes = wantOut;
+    }
+    uint8_t *hi = h->tin.hIn, *di = h->tin.dIn, *dout = h->tin.dOut, *ho = h->tin.hOut;
+
+    // ---- stage and upload: the frame with the small block behind it ----
+    const double times[2] = {t_prev, t_cur};
+    memcpy(hi + iTimes, times, sizeof times);
+    memcpy(hi + iBias, frame_bias, 6 * sizeof(float));
+    memcpy(hi + iState1, state1, 21 * sizeof(float));
+    memcpy(hi + iKf, kf, sizeof(orbfe_imu_preint));
+    memcpy(hi + iFrame, frame, sizeof(orbfe_imu_preint));
+    if (fromFrame) memcpy(hi + iPrior, prior, sizeof(orbfe_pose_imu_prior));
+    if (n_samples > 0) memcpy(hi + iSamples, samples, (size_t)n_samples * sizeof(orbfe_imu_sample));
+    if (M > 0) memcpy(hi + iIds, ids, (size_t)M * sizeof(int));
+    int inPitch;
+    int rc = upload_frame(h, h->tin, gray, pitch, iTimes, in, s, &inPitch);
+    if (rc != ORBFE_OK) return rc;
+
+    // ---- extraction, then the chain with batch == 1 ----
+    int* dHead = reinterpret_cast<int*>(dout);  // [n, status]
+    rc = extract_chain(h, di, L.inFrame, inPitch, 1, reinterpret_cast<orbfe_keypoint*>(dout + L.oKp), dout + L.oDesc, dHead,
+                       reinterpret_cast<int*>(dout + L.oPer), dHead + 1, s);
+    if (rc != ORBFE_OK) return rc;
+    const int off[2] = {0, n_samples};
+    int* dInts = reinterpret_cast<int*>(dout + oInts);
+    orbfe_track_inertial_io io{};
+    io.struct_size = (int)sizeof io;
+    io.d_samples = reinterpret_cast<const orbfe_imu_sample*>(di + iSamples);
+    io.sample_off = off;
+    io.d_t_prev = reinterpret_cast<const double*>(di + iTimes);
+    io.d_t_cur = io.d_t_prev + 1;
+    io.d_frame_bias = reinterpret_cast<const float*>(di + iBias);
+    io.d_state1 = reinterpret_cast<const float*>(di + iState1);
+    io.d_kf = reinterpret_cast<orbfe_imu_preint*>(di + iKf);
+    io.d_frame = reinterpret_cast<orbfe_imu_preint*>(di + iFrame);
+    io.d_steps_out = reinterpret_cast<orbfe_imu_step*>(dout + oSteps);
+    io.d_kp = reinterpret_cast<const orbfe_keypoint*>(dout + L.oKp);
+    io.d_desc = dout + L.oDesc;
+    io.d_n = dHead;
+    io.d_ids = reinterpret_cast<const int*>(di + iIds);
+    io.d_priors = fromFrame ? reinterpret_cast<const orbfe_pose_imu_prior*>(di + iPrior) : nullptr;
+    io.d_state_in = reinterpret_cast<float*>(dout + oStateIn);
+    io.d_info_ok = dInts;
+    io.d_mp_out = reinterpret_cast<orbfe_map_point*>(dout + oMps);
+    io.d_match_out = reinterpret_cast<int*>(dout + oMatch);
+    io.d_n_matches = dInts + 1;
+    io.d_state_out = reinterpret_cast<float*>(dout + oStateOut);
+    io.d_H_out = reinterpret_cast<double*>(dout + oH);
+    io.d_Hprior_out = fromFrame && res->Hprior_out ? reinterpret_cast<double*>(dout + oHp) : nullptr;
+    io.d_outlier = dout + oOutlier;
+    io.d_n_inliers = dInts + 2;
+    io.d_accepted = dInts + 3;
+    io.d_found = dout + oFound;
+    io.d_matches_inliers = dInts + 4;
+    io.d_tracked = dInts + 5;
+    io.d_Tcw_out = reinterpret_cast<float*>(dout + oTcw);
+    {
+        MatchScope scope_(h, s);
+        if (scope_.rc != ORBFE_OK) return scope_.rc;
+        void* dLinks = nullptr;
+        rc = track_inertial_batch_device(h->match, s, p, h->dSf, h->invSig2, nL, 1, cap, map->cap, map->dPts, map->dDesc, M, &io, &dLinks, err);
+        if (rc != ORBFE_OK) {
+            h->err = err;
+            return rc;
+        }
+        // the records and the link join the result block, so that ONE copy brings everything back
+        HIPCHK(h, hipMemcpyAsync(dout + oKf, di + iKf, sizeof(orbfe_imu_preint), hipMemcpyDeviceToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(dout + oFrame, di + iFrame, sizeof(orbfe_imu_preint), hipMemcpyDeviceToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(dout + oLink, dLinks, linkBytes, hipMemcpyDeviceToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(ho, dout, out, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(h, hipStreamSynchronize(s));
+    const int status = reinterpret_cast<const int*>(ho)[1];
+    if (status) {
+        char buf[112];
+        snprintf(buf, sizeof buf, "device guard flags 0x%x in orbfe_track_frame_inertial", (unsigned)status);
+        h->err = buf;
+        return ORBFE_ERR_INTERNAL;
+    }
+
+    // ---- hand over ----
+    const int n = chain_prefix_copy_out(h, ho, L, kp_out, desc_out, n_out, per_level);
+    const int nSteps = n_samples < 2 ? 0 : n_samples - 1;
+    memcpy(kf, ho + oKf, sizeof(orbfe_imu_preint));
+    memcpy(frame, ho + oFrame, sizeof(orbfe_imu_preint));
+    res->n_steps = nSteps;
+    if (res->steps_out && nSteps) memcpy(res->steps_out, ho + oSteps, (size_t)nSteps * sizeof(orbfe_imu_step));
+    memcpy(res->state_in, ho + oStateIn, 33 * sizeof(float));
+    if (res->link_out) memcpy(res->link_out, ho + oLink, linkBytes);
+    const int* ints = reinterpret_cast<const int*>(ho + oInts);
+    res->info_ok = ints[0];
+    res->n_matches = ints[1];
+    res->n_inliers = ints[2];
+    res->accepted = ints[3];
+    res->matches_inliers = ints[4];
+    res->tracked = ints[5];
+    if (M > 0) {
+        memcpy(res->mp_out, ho + oMps, (size_t)M * sizeof(orbfe_map_point));
+        memcpy(res->found, ho + oFound, (size_t)M);
+    }
+    memcpy(res->match_out, ho + oMatch, (size_t)n * sizeof(int));
+    memcpy(res->state_out, ho + oStateOut, 21 * sizeof(float));
+    memcpy(res->H_out, ho + oH, hBytes);
+    if (io.d_Hprior_out) memcpy(res->Hprior_out, ho + oHp, 225 * sizeof(double));
+    memcpy(res->outlier, ho + oOutlier, (size_t)n);
+    memcpy(res->Tcw, ho + oTcw, 12 * sizeof(float));
+    return ORBFE_OK;
 }
 
 int orbfe_initial_bundle_adjustment(orbfe_handle* h, const orbfe_initial_ba_params* p, int n1, const orbfe_keypoint* kp1, int n2,

@@ -394,6 +394,52 @@ class TrackParams(C.Structure):
         self.struct_size = C.sizeof(TrackParams)
 
 
+class TrackInertialParams(C.Structure):
+    """orbfe_track_inertial_params: the one block of the inertial TrackLocalMap chain (SPEC DECISION S23) -- the grid and matcher
+    parameters, the IMU noise, the prediction block (its `which` chooses the link kind and the optimisation), the frustum TEMPLATE
+    (its pose fields are ignored) and the S19 / S20 blocks."""
+    _fields_ = [("struct_size", C.c_int), ("inlier_threshold", C.c_int), ("track", TrackParams), ("noise", ImuNoise),
+                ("predict", ImuPredictParams), ("frustum", Frustum), ("pose_keyframe", PoseInertialParams),
+                ("pose_frame", PoseInertialPrevParams)]
+
+    def __init__(self, track=None, noise=None, predict=None, frustum=None, pose_keyframe=None, pose_frame=None, inlier_threshold=8):
+        super().__init__()
+        self.struct_size = C.sizeof(TrackInertialParams)
+        self.inlier_threshold = int(inlier_threshold)
+        for name, v, t in (("track", track, TrackParams), ("noise", noise, ImuNoise), ("predict", predict, ImuPredictParams),
+                           ("frustum", frustum, Frustum), ("pose_keyframe", pose_keyframe, PoseInertialParams),
+                           ("pose_frame", pose_frame, PoseInertialPrevParams)):
+            src = v if v is not None else t()
+            C.memmove(C.addressof(self) + getattr(TrackInertialParams, name).offset, C.addressof(src), C.sizeof(t))
+
+
+TRACK_INERTIAL_IO_FIELDS = ("d_samples", "sample_off", "d_t_prev", "d_t_cur", "d_frame_bias", "d_state1", "d_kf", "d_frame", "d_steps_out",
+                            "d_kp", "d_desc", "d_n", "d_ids", "d_priors", "d_state_in", "d_info_ok", "d_mp_out", "d_match_out",
+                            "d_n_matches", "d_state_out", "d_H_out", "d_Hprior_out", "d_outlier", "d_n_inliers", "d_accepted", "d_found",
+                            "d_matches_inliers", "d_tracked", "d_Tcw_out")
+
+
+class TrackInertialIO(C.Structure):
+    """orbfe_track_inertial_io: the pointers of orbfe_track_inertial_batch_device (device pointers as ints; sample_off is HOST)."""
+    _fields_ = [("struct_size", C.c_int), ("reserved", C.c_int)] + [(k, C.c_void_p) for k in TRACK_INERTIAL_IO_FIELDS]
+
+    def __init__(self, **k):
+        super().__init__(**k)
+        self.struct_size = C.sizeof(TrackInertialIO)
+
+
+class TrackInertialResult(C.Structure):
+    """orbfe_track_inertial_result: what orbfe_track_frame_inertial hands back besides the frame's features."""
+    _fields_ = [("struct_size", C.c_int), ("n_steps", C.c_int), ("steps_out", C.c_void_p), ("state_in", C.c_void_p), ("link_out", C.c_void_p),
+                ("info_ok", C.c_int), ("n_matches", C.c_int), ("mp_out", C.c_void_p), ("match_out", C.c_void_p), ("state_out", C.c_void_p),
+                ("H_out", C.c_void_p), ("Hprior_out", C.c_void_p), ("outlier", C.c_void_p), ("found", C.c_void_p), ("n_inliers", C.c_int),
+                ("accepted", C.c_int), ("matches_inliers", C.c_int), ("tracked", C.c_int), ("Tcw", C.c_float * 12)]
+
+    def __init__(self, **k):
+        super().__init__(**k)
+        self.struct_size = C.sizeof(TrackInertialResult)
+
+
 class FrameView(C.Structure):
     _fields_ = [("n", C.c_int), ("kp", C.c_void_p), ("desc", C.c_void_p), ("grid_cols", C.c_int),
                 ("grid_rows", C.c_int), ("min_x", C.c_float), ("min_y", C.c_float),
@@ -424,6 +470,7 @@ SYMBOLS = [
     "orbfe_marginalize_pose_imu",
     "orbfe_imu_preintegrate_frame", "orbfe_imu_reintegrate", "orbfe_imu_predict", "orbfe_imu_frame_batch_device",
     "orbfe_imu_reintegrate_batch_device",
+    "orbfe_track_inertial_batch_device", "orbfe_track_frame_inertial",
     "orbfe_shard_range", "orbfe_pool_create", "orbfe_pool_destroy", "orbfe_pool_size", "orbfe_pool_member",
     "orbfe_pool_member_frames", "orbfe_pool_last_error", "orbfe_pool_extract", "orbfe_pool_enable_track",
     "orbfe_pool_map_update", "orbfe_pool_track",
@@ -572,6 +619,11 @@ def lib():
         L.orbfe_imu_predict.argtypes = [vp, C.POINTER(ImuPredictParams), vp, C.POINTER(ImuPreint), C.POINTER(ImuPreint), vp, vp, C.POINTER(ci)]
         L.orbfe_imu_frame_batch_device.argtypes = [vp, C.POINTER(ImuNoise), C.POINTER(ImuPredictParams), ci] + [vp] * 13
         L.orbfe_imu_reintegrate_batch_device.argtypes = [vp, C.POINTER(ImuNoise), ci, vp, vp, vp, vp, vp]
+    if hasattr(L, "orbfe_track_inertial_batch_device"):  # (as above)
+        L.orbfe_track_inertial_batch_device.argtypes = [vp, C.POINTER(TrackInertialParams), ci, ci, vp, ci, C.POINTER(TrackInertialIO), vp]
+        L.orbfe_track_frame_inertial.argtypes = [vp, C.POINTER(TrackInertialParams), vp, ci, ci, vp, C.c_double, C.c_double, vp, vp,
+                                                 C.POINTER(ImuPreint), C.POINTER(ImuPreint), vp, ci, vp, C.POINTER(PoseImuPrior), vp, vp,
+                                                 C.POINTER(ci), vp, C.POINTER(TrackInertialResult)]
     if hasattr(L, "orbfe_initial_bundle_adjustment"):  # (as above)
         L.orbfe_initial_bundle_adjustment.argtypes = [vp, C.POINTER(InitialBAParams), ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                                       C.POINTER(InitialBAInfo)]
@@ -1694,6 +1746,66 @@ def imu_reintegrate_batch_device(extractor, noise, batch, d_steps_ptr, step_off,
     assert len(off) == batch + 1
     extractor._chk(extractor.L.orbfe_imu_reintegrate_batch_device(extractor.h, C.byref(noise), int(batch), d_steps_ptr, _p(off), d_bias_ptr,
                                                                   d_out_ptr, stream), "orbfe_imu_reintegrate_batch_device")
+
+
+def track_inertial_batch_device(extractor, params, batch, kp_stride, map_points, n_points, io, stream=None):
+    """orbfe_track_inertial_batch_device: Tracking::TrackLocalMap with the IMU for `batch` independent frames, resident in HBM (SPEC
+    DECISION S23): preintegration + prediction, isInFrustum against the predicted pose, SearchByProjection, the inertial pose
+    optimisation chosen by params.predict.which and the statistics of src/Tracking.cc:958-982, launched back to back on `stream`.
+    io: a TrackInertialIO of raw device pointers (track_inertial_io() builds it and keeps the HOST offsets alive)."""
+    extractor._chk(extractor.L.orbfe_track_inertial_batch_device(extractor.h, C.byref(params), int(batch), int(kp_stride),
+                                                                 map_points.h if map_points is not None else None, int(n_points),
+                                                                 C.byref(io), stream), "orbfe_track_inertial_batch_device")
+
+
+def track_inertial_io(sample_off, **ptrs):
+    """-> (TrackInertialIO, the int32 offsets array that has to stay alive until the call has returned)"""
+    off = np.ascontiguousarray(sample_off, np.int32)
+    io = TrackInertialIO(sample_off=off.ctypes.data, **ptrs)
+    return io, off
+
+
+def track_frame_inertial(extractor, params, im, samples, t_prev, t_cur, frame_bias, state1, kf, frame, map_points, ids, prior=None,
+                         want_hprior=True):
+    """orbfe_track_frame_inertial: the chain of track_inertial_batch_device for ONE frame from host memory, image in, results out: one
+    upload, extraction, the chain with batch == 1, one download, one synchronisation.  kf / frame: ImuPreint, updated in place.
+    -> dict(kp, desc, per_level, steps, state_in, link, info_ok, mps, match, nmatches, state_out, H, Hprior, outlier, n_inliers,
+    accepted, found, matches_inliers, tracked, Tcw)"""
+    e = extractor
+    im = np.asarray(im)
+    assert im.dtype == np.uint8 and im.shape == (e.H, e.W) and im.strides[1] == 1
+    smp = np.ascontiguousarray(samples, IMU_SAMPLE_DTYPE)
+    fb = np.ascontiguousarray(frame_bias, np.float32).reshape(6)
+    s1 = np.ascontiguousarray(state1, np.float32).reshape(21)
+    ids = np.ascontiguousarray(ids, np.int32)
+    M = len(ids)
+    from_frame = params.predict.which == IMU_FROM_FRAME
+    kp = np.zeros(e.cap, KP_DTYPE)
+    desc = np.zeros((e.cap, 32), np.uint8)
+    per = np.zeros(e.nlevels, np.int32)
+    steps = np.zeros(max(len(smp) - 1, 1), IMU_STEP_DTYPE)
+    state_in, state_out = np.zeros(33, np.float32), np.zeros(21, np.float32)
+    link = ImuLinkFree() if from_frame else ImuLink()
+    mps = np.zeros(max(M, 1), MP_DTYPE)
+    match = np.full(e.cap, -1, np.int32)
+    H = np.zeros(900 if from_frame else 225, np.float64)
+    Hp = np.zeros(225, np.float64) if from_frame and want_hprior else None
+    outlier = np.zeros(e.cap, np.uint8)
+    found = np.zeros(max(M, 1), np.uint8)
+    n = C.c_int()
+    res = TrackInertialResult(steps_out=steps.ctypes.data, state_in=state_in.ctypes.data, link_out=C.addressof(link),
+                              mp_out=mps.ctypes.data, match_out=match.ctypes.data, state_out=state_out.ctypes.data, H_out=H.ctypes.data,
+                              Hprior_out=Hp.ctypes.data if Hp is not None else None, outlier=outlier.ctypes.data, found=found.ctypes.data)
+    e._chk(e.L.orbfe_track_frame_inertial(e.h, C.byref(params), _p(im), im.strides[0], len(smp), _p(smp) if len(smp) else None, float(t_prev),
+                                          float(t_cur), _p(fb), _p(s1), C.byref(kf), C.byref(frame), map_points.h, M, _p(ids) if M else None,
+                                          C.byref(prior) if prior is not None else None, _p(kp), _p(desc), C.byref(n), _p(per), C.byref(res)),
+           "orbfe_track_frame_inertial")
+    k = n.value
+    side = 30 if from_frame else 15
+    return dict(kp=kp[:k], desc=desc[:k], per_level=per, steps=steps[:res.n_steps], state_in=state_in, link=link, info_ok=res.info_ok,
+                mps=mps[:M], match=match[:k], nmatches=res.n_matches, state_out=state_out, H=H.reshape(side, side),
+                Hprior=Hp.reshape(15, 15) if Hp is not None else None, outlier=outlier[:k], n_inliers=res.n_inliers, accepted=res.accepted,
+                found=found[:M], matches_inliers=res.matches_inliers, tracked=res.tracked, Tcw=np.array(res.Tcw, np.float32))
 
 
 def initial_bundle_adjustment(extractor, params, kp1, kp2, matches12, points, Rcw1, tcw1, Rcw2, tcw2, want_info=True):
