@@ -1879,7 +1879,9 @@ public:
     void DropPrior() { mHasPrior = false; }
 
     // mapUpdated (mbMapUpdated, :946-952) or no prior yet: against the last key frame, `startState` = its Rwb twb v bg ba; else against
-    // the last frame, `startState` = that frame's.  lastFrameBias = mLastFrame->mImuBias.
+    // the last frame, `startState` = that frame's: the caller picks it by `mapUpdated || !HasPrior()`.  lastFrameBias =
+    // mLastFrame->mImuBias.  The last frame's state afterwards is Result::state -- unless this call ran against the last frame and
+    // the result is not accepted (src/Optimizer.cc:4208-4213 did not run): then it is Result::predicted + 12, and no prior is left.
     Result Track(const GrayImageView& im, const std::vector<orbfe_imu_sample>& imuFromLastFrame, double prevStamp, double curStamp,
                  const float* lastFrameBias, const float* startState, bool mapUpdated, const ResidentMap& map, const std::vector<int>& ids)
     {
@@ -1927,7 +1929,12 @@ public:
         R.tracked = res.tracked != 0;
         R.infoOk = res.info_ok != 0;
         // pFrame->mpcpi = new ConstraintPoseImu(Rwb, twb, v, bg, ba, H) (src/Optimizer.cc:3841, :4271): the optimised state and the raw
-        // Hessian block; the constructor's eigenvalue clamp (include/G2oTypes.h) stays with the caller, through Prior()
+        // Hessian block; the constructor's eigenvalue clamp (include/G2oTypes.h) stays with the caller, through Prior().
+        // A prior exists afterwards if and only if THIS frame left one: the last-frame kind leaves none when it is rejected
+        // (:4268 stands inside `if(validPoints >= inlierThreshold)`, :4208) and the frame's own mpcpi starts as nullptr
+        // (src/Frame.cc:59), so the next frame falls back to the last key frame (src/Tracking.cc:940-953) instead of running
+        // against this one with the prior of the frame before it.  The key-frame kind always accepts.
+        mHasPrior = R.accepted;
         if (R.accepted) {
             const double* src = fromFrame ? Hp.data() : H.data();
             for (int i = 0; i < 9; i++) mPrior.Rwb[i] = (double)R.state[i];
@@ -1938,7 +1945,6 @@ public:
                 mPrior.ba[i] = (double)R.state[18 + i];
             }
             std::memcpy(mPrior.H, src, sizeof mPrior.H);
-            mHasPrior = true;
         }
         return R;
     }

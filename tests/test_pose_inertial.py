@@ -1,7 +1,7 @@
 """The restatement of SPEC DECISION S19 (pose_inertial_ref.py) on the CPU: which branches the scenes of pose_inertial_scenarios reach,
 the stated departure 1 (no NormalizeRotation) as a figure, and the restatement against an independent solver --
-scipy.optimize.least_squares on the same 15 unknowns, written here with scipy's Rotation and plain numpy, nothing shared with the
-restatement.  Residuals are whitened by the Cholesky factors of info9 / infoG / infoA and by sqrt(w).  Round 0 is compared with
+scipy.optimize.least_squares on the same 15 unknowns, written (in tests/pose_inertial_scipy.py) with scipy's Rotation and plain
+numpy, nothing shared with the restatement.  Residuals are whitened by the Cholesky factors of info9 / infoG / infoA and by sqrt(w).  Round 0 is compared with
 loss='huber' (f_scale = delta) from the same start, round 3 with loss='linear' on round 2's inlier set from round 2's state.
 scipy's Huber acts per residual component and on the inertial residuals too, g2o's per mono edge only; the two agree where no residual
 is beyond delta at the optimum, which the small-noise scenes are built for.
@@ -12,11 +12,10 @@ import collections
 
 import numpy as np
 import pytest
-from scipy.optimize import least_squares
-from scipy.spatial.transform import Rotation
 
 import pose_inertial_ref as R
 import pose_inertial_scenarios as PS
+from pose_inertial_scipy import measure15
 
 SCIPY_KINDS = ("general", "far", "weak_imu", "strong_imu")
 METRICS = ("rot", "twb", "v", "bg", "ba")
@@ -95,74 +94,13 @@ def test_rotation_stays_orthonormal_without_normalize_rotation():
     assert worst < ORTHONORMALITY_BOUND
 
 
-# ---- the independent solver ----
-def _unpack(x0, x):
-    Rwb = x0["Rwb"] @ Rotation.from_rotvec(x[0:3]).as_matrix()
-    return Rwb, x0["twb"] + x[3:6], x0["v"] + x[6:9], x0["bg"] + x[9:12], x0["ba"] + x[12:15]
-
-
-def _residuals(x, x0, sc, K, obs, w, Xw, keep, gravity):
-    Rwb, twb, v, bg, ba = _unpack(x0, x)
-    Rcb, tcb = K["Rcb"], K["tcb"]
-    Rcw = Rcb @ Rwb.T
-    tcw = Rcb @ (-Rwb.T @ twb) + tcb
-    Xc = Xw[keep] @ Rcw.T + tcw
-    fx, fy, cx, cy = (float(c) for c in sc["cam"][:4])
-    proj = np.stack([fx * Xc[:, 0] / Xc[:, 2] + cx, fy * Xc[:, 1] / Xc[:, 2] + cy], 1)
-    r_mono = ((obs[keep] - proj) * np.sqrt(w[keep])[:, None]).reshape(-1)
-    g = np.array([0.0, 0.0, -gravity])
-    dt = K["dt"]
-    Rbw1 = K["Rwb1"].T
-    er = Rotation.from_matrix(K["dR"].T @ Rbw1 @ Rwb).as_rotvec()
-    ev = Rbw1 @ (v - K["v1"] - g * dt) - K["dV"]
-    ep = Rbw1 @ (twb - K["twb1"] - K["v1"] * dt - g * dt * dt / 2.0) - K["dP"]
-    r_imu = K["L9"].T @ np.concatenate([er, ev, ep])
-    return np.concatenate([r_mono, r_imu, K["LG"].T @ (bg - K["bg1"]), K["LA"].T @ (ba - K["ba1"])])
-
-
-def _link64(link):
-    K = {k: np.asarray(link[k], np.float32).astype(np.float64) for k in ("twb1", "v1", "bg1", "ba1", "dV", "dP", "tcb")}
-    for k in ("Rwb1", "dR", "Rcb"):
-        K[k] = np.asarray(link[k], np.float32).astype(np.float64).reshape(3, 3)
-    K["dt"] = float(np.float32(link["dt"]))
-    # dR as the caller's floats is not exactly a rotation; the independent solver takes the nearest one
-    U, _, Vt = np.linalg.svd(K["dR"])
-    K["dR"] = U @ Vt
-    K["L9"] = np.linalg.cholesky(np.asarray(link["info9"], np.float64).reshape(9, 9))
-    K["LG"] = np.linalg.cholesky(np.asarray(link["infoG"], np.float64).reshape(3, 3))
-    K["LA"] = np.linalg.cholesky(np.asarray(link["infoA"], np.float64).reshape(3, 3))
-    return K
-
-
-def _state(vec):
-    return dict(Rwb=vec[:9].reshape(3, 3), twb=vec[9:12], v=vec[12:15], bg=vec[15:18], ba=vec[18:21])
-
-
-def _distance(vec, x0, x):
-    Rwb, twb, v, bg, ba = _unpack(x0, x)
-    s = _state(vec)
-    rot = float(np.linalg.norm(Rotation.from_matrix(Rwb.T @ s["Rwb"]).as_rotvec()))
-    return (rot,) + tuple(float(np.linalg.norm(a - b)) for a, b in ((twb, s["twb"]), (v, s["v"]), (bg, s["bg"]), (ba, s["ba"])))
-
-
+# ---- the independent solver: tests/pose_inertial_scipy.py (shared with tests/test_track_inertial_sequence.py) ----
 def measure(kind, seed):
     """-> {0: distances after round 0, 3: distances after round 3} between the restatement and scipy"""
     sc = PS.make(kind, 300, seed)
     ref = PS.ref(sc)
     assert ref["rounds_run"] == 4 and ref["round_ok"].all()
-    first, obs, w, Xw = R.edges_of(sc["level_sigma2"], sc["kp_xy"], sc["kp_octave"], sc["mp_index"], sc["points"])
-    K = _link64(sc["link"])
-    gravity = float(np.float32(9.81))
-    delta = R.delta_of(5.991)
-    out = {}
-    start = np.concatenate([sc[k].astype(np.float64).reshape(-1) for k in ("Rwb", "twb", "v", "bg", "ba")])
-    for rnd, x0vec, keep, loss in ((0, start, np.ones(len(first), bool), "huber"),
-                                   (3, ref["round_state"][2], ref["round_outlier"][2] == 0, "linear")):
-        x0 = _state(x0vec)
-        sol = least_squares(_residuals, np.zeros(15), args=(x0, sc, K, obs, w, Xw, keep, gravity), loss=loss, f_scale=delta, method="trf",
-                            x_scale="jac", xtol=1e-15, ftol=1e-15, gtol=1e-15, max_nfev=400)
-        out[rnd] = _distance(ref["round_state"][rnd], x0, sol.x)
-    return out
+    return measure15(R, sc, ref)
 
 
 @pytest.mark.parametrize("kind", SCIPY_KINDS)

@@ -1,8 +1,8 @@
 """The restatement of SPEC DECISION S20 (pose_inertial_prev_ref.py) on the CPU against independent forms: which branches the scenes of
 pose_inertial_prev_scenarios reach; the marginalisation against marginalize_svd, the literal numpy rendering of Optimizer::Marginalize
 with numpy.linalg.svd; the stated departure in the preintegrated rotation against a plain binary32 rendering of the reference's line;
-the orthonormality of both frames' rotations; and the solver against scipy.optimize.least_squares on the same 30 unknowns, written here
-with scipy's Rotation and plain numpy in binary64, nothing shared with the restatement.  Residuals are whitened by the Cholesky factors
+the orthonormality of both frames' rotations; and the solver against scipy.optimize.least_squares on the same 30 unknowns, written (in
+tests/pose_inertial_scipy.py) with scipy's Rotation and plain numpy in binary64, nothing shared with the restatement.  Residuals are whitened by the Cholesky factors
 of info9 / infoG / infoA / the prior's H and by sqrt(w).  Round 0 is compared with loss='huber' (f_scale = delta) from the same start,
 round 3 with loss='linear' on round 2's inlier set from round 2's state.  scipy's Huber acts per residual component and on every
 residual, g2o's per mono edge and on the prior edge; the two agree where no residual is beyond delta at the optimum, which the
@@ -12,11 +12,10 @@ Protocol (S14's, S17's, S19's): the figures of seeds 0 and 1 were measured, each
 must hold them too (the tables are here and in DESIGN.md S20)."""
 import numpy as np
 import pytest
-from scipy.optimize import least_squares
-from scipy.spatial.transform import Rotation
 
 import pose_inertial_prev_ref as R
 import pose_inertial_prev_scenarios as PS
+from pose_inertial_scipy import measure30
 
 SCIPY_KINDS = ("general", "far", "bias_step", "weak_imu")
 METRICS = ("rot", "twb", "v", "bg", "ba", "rot1", "twb1", "v1", "bg1", "ba1")
@@ -140,94 +139,14 @@ def test_marginalisation_against_the_svd_form(kind):
         assert v <= MARG_GATE, "%s seed %d: %.3e above the gate %.3e" % (kind, seed, v, MARG_GATE)
 
 
-# ---- the independent solver ----
-def _unpack(x0, x):
-    out = []
-    for h in (0, 1):
-        s, d = x0[h], x[15 * h:15 * h + 15]
-        out.append((s["Rwb"] @ Rotation.from_rotvec(d[0:3]).as_matrix(), s["twb"] + d[3:6], s["v"] + d[6:9], s["bg"] + d[9:12], s["ba"] + d[12:15]))
-    return out
-
-
-def _residuals(x, x0, sc, K, Pr, obs, w, Xw, keep, gravity):
-    (Rwb, twb, v, bg, ba), (Rwb1, twb1, v1, bg1, ba1) = _unpack(x0, x)
-    Rcb, tcb = K["Rcb"], K["tcb"]
-    Rcw = Rcb @ Rwb.T
-    tcw = Rcb @ (-Rwb.T @ twb) + tcb
-    Xc = Xw[keep] @ Rcw.T + tcw
-    fx, fy, cx, cy = (float(c) for c in sc["cam"][:4])
-    proj = np.stack([fx * Xc[:, 0] / Xc[:, 2] + cx, fy * Xc[:, 1] / Xc[:, 2] + cy], 1)
-    r_mono = ((obs[keep] - proj) * np.sqrt(w[keep])[:, None]).reshape(-1)
-    g = np.array([0.0, 0.0, -gravity])
-    dt = K["dt"]
-    dbg, dba = bg1 - K["bg0"], ba1 - K["ba0"]
-    dR = K["dR0"] @ Rotation.from_rotvec(K["JRg"] @ dbg).as_matrix()
-    dV = K["dV0"] + K["JVg"] @ dbg + K["JVa"] @ dba
-    dP = K["dP0"] + K["JPg"] @ dbg + K["JPa"] @ dba
-    Rbw1 = Rwb1.T
-    er = Rotation.from_matrix(dR.T @ Rbw1 @ Rwb).as_rotvec()
-    ev = Rbw1 @ (v - v1 - g * dt) - dV
-    ep = Rbw1 @ (twb - twb1 - v1 * dt - g * dt * dt / 2.0) - dP
-    r_imu = K["L9"].T @ np.concatenate([er, ev, ep])
-    e_pr = np.concatenate([Rotation.from_matrix(Pr["Rwb"].T @ Rwb1).as_rotvec(), Pr["Rwb"].T @ (twb1 - Pr["twb"]), v1 - Pr["vwb"],
-                           bg1 - Pr["bg"], ba1 - Pr["ba"]])
-    return np.concatenate([r_mono, r_imu, K["LG"].T @ (bg - bg1), K["LA"].T @ (ba - ba1), Pr["L"].T @ e_pr])
-
-
-def _link64(link):
-    K = {k: np.asarray(link[k], np.float32).astype(np.float64) for k in ("dV0", "dP0", "bg0", "ba0", "tcb")}
-    for k in ("dR0", "Rcb", "JRg", "JVg", "JVa", "JPg", "JPa"):
-        K[k] = np.asarray(link[k], np.float32).astype(np.float64).reshape(3, 3)
-    K["dt"] = float(np.float32(link["dt"]))
-    U, _, Vt = np.linalg.svd(K["dR0"])   # dR0 as the caller's floats is not exactly a rotation; the independent solver takes the nearest one
-    K["dR0"] = U @ Vt
-    K["L9"] = np.linalg.cholesky(np.asarray(link["info9"], np.float64).reshape(9, 9))
-    K["LG"] = np.linalg.cholesky(np.asarray(link["infoG"], np.float64).reshape(3, 3))
-    K["LA"] = np.linalg.cholesky(np.asarray(link["infoA"], np.float64).reshape(3, 3))
-    return K
-
-
-def _prior64(prior):
-    Pr = {k: np.asarray(prior[k], np.float64) for k in ("twb", "vwb", "bg", "ba")}
-    Pr["Rwb"] = np.asarray(prior["Rwb"], np.float64).reshape(3, 3)
-    Hm = np.asarray(prior["H"], np.float64).reshape(15, 15)
-    Pr["L"] = np.linalg.cholesky((Hm + Hm.T) / 2.0 + 1e-9 * np.eye(15))   # (a rank-deficient H would be regularised here, and only here)
-    return Pr
-
-
-def _states(vec):
-    return [dict(Rwb=vec[o:o + 9].reshape(3, 3), twb=vec[o + 9:o + 12], v=vec[o + 12:o + 15], bg=vec[o + 15:o + 18], ba=vec[o + 18:o + 21])
-            for o in (0, 21)]
-
-
-def _distance(vec, x0, x):
-    out = []
-    for (Rwb, twb, v, bg, ba), s in zip(_unpack(x0, x), _states(vec)):
-        out.append(float(np.linalg.norm(Rotation.from_matrix(Rwb.T @ s["Rwb"]).as_rotvec())))
-        out += [float(np.linalg.norm(a - b)) for a, b in ((twb, s["twb"]), (v, s["v"]), (bg, s["bg"]), (ba, s["ba"]))]
-    return tuple(out)
-
-
+# ---- the independent solver: tests/pose_inertial_scipy.py (shared with tests/test_track_inertial_sequence.py) ----
 def measure(kind, seed):
     """-> {0: distances after round 0, 3: distances after round 3} between the restatement and scipy"""
     sc = PS.make(kind, 257, seed)
     ref = PS.ref(sc)
     assert ref["rounds_run"] == 4 and ref["round_ok"].all()
     assert (ref["round_prior_weight"] == 1.0).all()   # the prior's Huber kernel is inactive: scipy's per-component Huber is comparable
-    first, obs, w, Xw = R.edges_of(sc["level_sigma2"], sc["kp_xy"], sc["kp_octave"], sc["mp_index"], sc["points"])
-    K, Pr = _link64(sc["link"]), _prior64(sc["prior"])
-    gravity = float(np.float32(9.81))
-    delta = R.delta_of(5.991)
-    out = {}
-    start = np.concatenate([np.asarray(sc[k], np.float32).astype(np.float64).reshape(-1) for k in ("Rwb", "twb", "v", "bg", "ba")] +
-                           [np.asarray(sc["link"][k], np.float32).astype(np.float64).reshape(-1) for k in ("Rwb1", "twb1", "v1", "bg1", "ba1")])
-    for rnd, x0vec, keep, loss in ((0, start, np.ones(len(first), bool), "huber"),
-                                   (3, ref["round_state"][2], ref["round_outlier"][2] == 0, "linear")):
-        x0 = _states(x0vec)
-        sol = least_squares(_residuals, np.zeros(30), args=(x0, sc, K, Pr, obs, w, Xw, keep, gravity), loss=loss, f_scale=delta, method="trf",
-                            x_scale="jac", xtol=1e-15, ftol=1e-15, gtol=1e-15, max_nfev=400)
-        out[rnd] = _distance(ref["round_state"][rnd], x0, sol.x)
-    return out
+    return measure30(R, sc, ref)
 
 
 @pytest.mark.parametrize("kind", SCIPY_KINDS)

@@ -39,11 +39,12 @@ def _camera_pose(sc):
     return Rcb @ Rwb.T, Rcb @ (-Rwb.T @ twb) + tcb
 
 
-def make_frame(kind, M, seed, id_base, capacity, wp_dtype, kp_dtype, n_kp=150, case=None):
-    """-> dict(sc, which-independent IMU inputs, ids [M], points / desc: the map entries id_base .. id_base + M - 1, kp, kp_desc, n)"""
+def make_frame(kind, M, seed, id_base, capacity, wp_dtype, kp_dtype, n_kp=150, case=None, sc=None):
+    """-> dict(sc, which-independent IMU inputs, ids [M], points / desc: the map entries id_base .. id_base + M - 1, kp, kp_desc, n).
+    `sc`: a window of the caller's own (track_inertial_sequence) instead of the archetype's"""
     assert M == 0 or M >= N_PLANTED + 8
     case = case or ARCHETYPES[kind]
-    sc = PS.make(*case)
+    sc = sc if sc is not None else PS.make(*case)
     rng = np.random.RandomState(2300 + 31 * seed + M)
     Rt, tt = _camera_pose(sc)
     fx, fy, cx, cy = (float(v) for v in PINHOLE[:4])
@@ -100,7 +101,10 @@ def make_frame(kind, M, seed, id_base, capacity, wp_dtype, kp_dtype, n_kp=150, c
 
 def records_in(fr, which):
     """the two records as the call finds them -> (kf Record, frame Record or None): the standing frame has the records the window's
-    integration left (the restatement's), every other frame the scene's key-frame record and no frame record yet"""
+    integration left (the restatement's), every other frame the scene's key-frame record and no frame record yet.  A frame of a
+    sequence (track_inertial_sequence) carries the records the frame before left, as fr["records"]"""
+    if "records" in fr:
+        return fr["records"]
     if fr["kind"] == "standing":
         r = PS.ref_cached(fr["case"], which)
         return r["kf"], r["frame"]
@@ -172,7 +176,10 @@ class CpuStages:
         sc = fr["sc"]
         kf, frame = records_in(fr, which)
         if fr["kind"] != "standing":
-            kf, frame, _ = R22.preintegrate_frame(sc["noise"], sc["t"], sc["a"], sc["w"], sc["t_prev"], sc["t_cur"], sc["frame_bias"], kf)
+            kf, frame, steps = R22.preintegrate_frame(sc["noise"], sc["t"], sc["a"], sc["w"], sc["t_prev"], sc["t_cur"], sc["frame_bias"], kf)
+        else:
+            steps = np.zeros((0, 8), f32)
+        self.last = dict(kf=kf, frame=frame, steps=steps)    # what the IMU stage left in the records, as HostStages keeps it
         return R22.predict(which, start_state(fr, which), kf, frame, sc["gravity"], sc["Rcb"], sc["tcb"], sc["tbc"])
 
     def project(self, state_in, seen):
@@ -193,10 +200,12 @@ class CpuStages:
         a = (np.array(PINHOLE, f32), level_sigma2(), np.stack([kp["x"], kp["y"]], 1).astype(f32).reshape(-1, 2), kp["octave"].astype(np.int32),
              match, rows_xyz, depth, link)
         tail = (s[0:9], s[9:12], s[12:21], s[21:24], s[24:27], s[27:30], s[30:33])
+        r = R20.pose_inertial_optimization_last_frame(*a, prior, *tail) if which == R22.FROM_FRAME else R19.pose_inertial_optimization(*a, *tail)
+        # the problem and the restatement's whole result, for the tests that solve it again independently
+        self.last_pose = dict(zip(("cam", "level_sigma2", "kp_xy", "kp_octave", "mp_index", "points", "track_depth", "link"), a), prior=prior,
+                              Rwb=s[12:21], twb=s[21:24], v=s[24:27], bg=s[27:30], ba=s[30:33], ref=r)
         if which == R22.FROM_FRAME:
-            r = R20.pose_inertial_optimization_last_frame(*a, prior, *tail)
             return r, r["H30"], r["accepted"]
-        r = R19.pose_inertial_optimization(*a, *tail)
         return r, r["H"], 1
 
 
