@@ -32,7 +32,7 @@ static_assert(offsetof(orbfe_imu_preint, C) - offsetof(orbfe_imu_preint, dT) == 
 namespace {
 
 constexpr int kImuThreads = 64;
-constexpr int kImuStateIn = 33, kImuState1 = 21;
+constexpr int kImuState1 = 21;
 
 struct ImuArgs {
     const orbfe_imu_sample* samples;

@@ -34,9 +34,6 @@ namespace orbfe {
 
 namespace {
 
-constexpr int kImuMaxKp = 65536;
-constexpr int kImuStateIn = 33;            // Rcw, tcw, Rwb, twb, v, bg, ba
-
 struct PoseImuRounds {   // what the kernel reports per call (host call only)
     int Ne, roundsRun, recovered, pad;
     int iterations[4], ok[4], nBad[4];
@@ -463,21 +460,7 @@ constexpr char kPoseImuSizeErr[] =
 
 void fill_args(PoseImuArgs& G, const orbfe_pose_inertial_params* P, const float* invLevelSigma2, int nLevels)
 {
-    memset(&G, 0, sizeof G);
-    fill_pose_cam(G.cam, P->cam, P->huber_delta2);
-    G.gravity = (double)P->gravity;
-    for (int i = 0; i < 4; i++) {
-        G.chi2[i] = P->chi2[i];
-        G.chi2Close[i] = (float)(P->close_factor * (double)P->chi2[i]);   // float chi2close = 1.5 * chi2Mono[it] (:3686)
-    }
-    G.closeDepth = P->close_depth;
-    G.recoverChi2 = P->recover_chi2;
-    G.recoverBelow = P->recover_below;
-    G.recInit = P->rec_init != 0;
-    G.iterations = P->iterations;
-    G.nRounds = P->rounds;
-    G.nLevels = nLevels;
-    for (int i = 0; i < kMaxLevels; i++) G.invSigma2[i] = i < nLevels ? invLevelSigma2[i] : 0.0f;
+    fill_inertial_args(G, G, P, invLevelSigma2, nLevels);
 }
 
 }  // namespace
@@ -504,9 +487,7 @@ int pose_imu_begin(const orbfe_pose_inertial_params* P, const orbfe_imu_link* li
 {
     const int crc = pose_imu_check(P, link, info, err);
     if (crc != ORBFE_OK) return crc;
-    if (n > kImuMaxKp) return ORBFE_ERR_INVALID_ARG;
-    if (!matched_keypoints(n, kp, mpIndex, nPoints, nLevels, first)) return ORBFE_ERR_INVALID_ARG;
-    return ORBFE_OK;
+    return pose_edge_list(nLevels, n, kp, mpIndex, nPoints, first);
 }
 
 // the device part of the host call, for the edge list `first` of pose_imu_begin (it may be empty)
@@ -515,83 +496,37 @@ int pose_imu_run(MatchScratch& m, hipStream_t s, const orbfe_pose_inertial_param
                  const float* trackDepth, const float* stateIn, const std::vector<int>& first, float* stateOut, double* Hout,
                  uint8_t* outlier, int* nInliers, orbfe_pose_inertial_info* info, std::string& err)
 {
-    const int Ne = (int)first.size();
-    // up: [kp | match (edge order index into pts) | pts | depth | state | link]; device only: [edgeIdx];
-    // down: [state | nInliers | rounds | H | outlier | roundOutlier]
-    Carver c;
-    const size_t oKp = c.take((size_t)n * sizeof(orbfe_keypoint));
-    const size_t oMatch = c.take((size_t)n * sizeof(int));
-    const size_t oPts = c.take((size_t)Ne * 3 * sizeof(float));
-    const size_t oDepth = c.take((size_t)Ne * sizeof(float));
-    const size_t oState = c.take(kImuStateIn * sizeof(float));
-    const size_t oLink = c.take(sizeof(orbfe_imu_link));
-    const size_t inBytes = c.off;
-    const size_t oIdx = c.take((size_t)n * sizeof(int));
-    const size_t oStateOut = c.take(kImuState * sizeof(float));
-    const size_t oNInl = c.take(sizeof(int));
-    const size_t oRounds = c.take(sizeof(PoseImuRounds));
-    const size_t oH = c.take(kImuN * kImuN * sizeof(double));
-    const size_t oOutlier = c.take((size_t)n);
-    const size_t oRoundOut = c.take((size_t)4 * Ne);
-    const size_t resBytes = c.off - oStateOut;
-    int rc = ensure(m, c.off + 256, inBytes + resBytes + 256, err);
+    // the unit's blocks (EdgeStaging, match_common.h): up [state | link]; down [state | nInliers | rounds | H]
+    EdgeStaging st(n, first, trackDepth);
+    const size_t oState = st.c.take(kImuStateIn * sizeof(float));
+    const size_t oLink = st.c.take(sizeof(orbfe_imu_link));
+    st.inputs_done();
+    const size_t oStateOut = st.c.take(kImuState * sizeof(float));
+    const size_t oNInl = st.c.take(sizeof(int));
+    const size_t oRounds = st.c.take(sizeof(PoseImuRounds));
+    const size_t oH = st.c.take(kImuN * kImuN * sizeof(double));
+    int rc = st.stage(m, kp, first, mpIndex, points, trackDepth, err);
     if (rc != ORBFE_OK) return rc;
-    uint8_t* hp = static_cast<uint8_t*>(m.hpin);
-    uint8_t* dp = static_cast<uint8_t*>(m.d);
-    if (n > 0) memcpy(hp + oKp, kp, (size_t)n * sizeof(orbfe_keypoint));
-    stage_edge_list(n, first, mpIndex, points, reinterpret_cast<int*>(hp + oMatch), reinterpret_cast<float*>(hp + oPts), trackDepth,
-                    reinterpret_cast<float*>(hp + oDepth));
-    memcpy(hp + oState, stateIn, kImuStateIn * sizeof(float));
-    memcpy(hp + oLink, link, sizeof(orbfe_imu_link));
-    MCHK(hipMemcpyAsync(dp, hp, inBytes, hipMemcpyHostToDevice, s));
-    MCHK(hipMemsetAsync(dp + oRounds, 0, sizeof(PoseImuRounds), s));
+    memcpy(st.host<float>(oState), stateIn, kImuStateIn * sizeof(float));
+    memcpy(st.host<orbfe_imu_link>(oLink), link, sizeof(orbfe_imu_link));
+    rc = st.upload(s, oRounds, sizeof(PoseImuRounds), err);
+    if (rc != ORBFE_OK) return rc;
 
     PoseImuArgs G;
     fill_args(G, P, invLevelSigma2, nLevels);
-    G.nSingle = n;
-    G.kpStride = n;
-    G.kp = reinterpret_cast<const orbfe_keypoint*>(dp + oKp);
-    G.match = reinterpret_cast<const int*>(dp + oMatch);
-    G.nPoints = Ne;
-    G.pts = reinterpret_cast<const float*>(dp + oPts);
-    G.depth = reinterpret_cast<const float*>(dp + oDepth);
-    G.ptRec = 3;
-    G.link = reinterpret_cast<const orbfe_imu_link*>(dp + oLink);
-    G.stateIn = reinterpret_cast<const float*>(dp + oState);
-    G.stateOut = reinterpret_cast<float*>(dp + oStateOut);
-    G.Hout = reinterpret_cast<double*>(dp + oH);
-    G.outlier = dp + oOutlier;
-    G.nInliers = reinterpret_cast<int*>(dp + oNInl);
-    G.edgeIdx = reinterpret_cast<int*>(dp + oIdx);
-    G.rounds = reinterpret_cast<PoseImuRounds*>(dp + oRounds);
-    G.roundOutlier = dp + oRoundOut;
+    st.set_args(G, oNInl, oRounds);
+    G.depth = st.dev<const float>(st.oDepth);
+    G.link = st.dev<const orbfe_imu_link>(oLink);
+    G.stateIn = st.dev<const float>(oState);
+    G.stateOut = st.dev<float>(oStateOut);
+    G.Hout = st.dev<double>(oH);
     hipLaunchKernelGGL(pose_imu_kernel, dim3(1), dim3(kTreeThreads), 0, s, G);
-    MCHK(hipGetLastError());
-    MCHK(hipMemcpyAsync(hp + inBytes, dp + oStateOut, resBytes, hipMemcpyDeviceToHost, s));
-    MCHK(hipStreamSynchronize(s));
-    const uint8_t* r = hp + inBytes;
-    memcpy(stateOut, r, kImuState * sizeof(float));
-    const PoseImuRounds* I = reinterpret_cast<const PoseImuRounds*>(r + (oRounds - oStateOut));
-    *nInliers = *reinterpret_cast<const int*>(r + (oNInl - oStateOut));
-    memcpy(Hout, r + (oH - oStateOut), kImuN * kImuN * sizeof(double));
-    if (n > 0) memcpy(outlier, r + (oOutlier - oStateOut), (size_t)n);
-    if (info) {
-        uint8_t* infoOutlier = info->outlier;
-        memset(info, 0, sizeof *info);
-        info->struct_size = (int)sizeof(orbfe_pose_inertial_info);
-        info->outlier = infoOutlier;
-        info->N_e = I->Ne;
-        info->rounds_run = I->roundsRun;
-        info->recovered = I->recovered;
-        memcpy(info->iterations, I->iterations, sizeof I->iterations);
-        memcpy(info->ok, I->ok, sizeof I->ok);
-        memcpy(info->n_bad, I->nBad, sizeof I->nBad);
-        memcpy(info->state, I->state, sizeof I->state);
-        if (info->outlier && Ne > 0) {
-            memset(info->outlier, 0, (size_t)4 * Ne);
-            memcpy(info->outlier, r + (oRoundOut - oStateOut), (size_t)I->roundsRun * Ne);
-        }
-    }
+    rc = st.download(s, outlier, err);
+    if (rc != ORBFE_OK) return rc;
+    memcpy(stateOut, st.res<float>(oStateOut), kImuState * sizeof(float));
+    *nInliers = *st.res<int>(oNInl);
+    memcpy(Hout, st.res<double>(oH), kImuN * kImuN * sizeof(double));
+    if (info) fill_inertial_info(info, st.res<PoseImuRounds>(oRounds), st);
     return ORBFE_OK;
 }
 
@@ -603,7 +538,7 @@ int pose_imu_batch_device(MatchScratch& m, hipStream_t s, const orbfe_pose_inert
 {
     const int crc = pose_imu_check(P, nullptr, nullptr, err);
     if (crc != ORBFE_OK) return crc;
-    if (kpStride > kImuMaxKp) return ORBFE_ERR_INVALID_ARG;
+    if (kpStride > kPoseMaxKp) return ORBFE_ERR_INVALID_ARG;
     int rc = ensure(m, (size_t)batch * kpStride * sizeof(int), 0, err);
     if (rc != ORBFE_OK) return rc;
     PoseImuArgs G;

@@ -28,9 +28,6 @@ namespace orbfe {
 
 namespace {
 
-constexpr int kPrevMaxKp = 65536;
-constexpr int kPrevStateIn = 33;           // Rcw, tcw, Rwb, twb, v, bg, ba
-
 struct PosePrevArgs {
     int nSingle;                 // the keypoint count when dN == nullptr
     const int* dN;               // [batch]
@@ -359,7 +356,7 @@ __global__ __launch_bounds__(kTreeThreads) void pose_prev_kernel(PosePrevArgs G)
     const orbfe_pose_imu_prior& Pr = G.prior[frame];
     PrevState& St = S.state;
     if (tid == 0) {
-        const float* in = G.stateIn + (size_t)frame * kPrevStateIn;
+        const float* in = G.stateIn + (size_t)frame * kImuStateIn;
 #pragma unroll
         for (int i = 0; i < 9; i++) {
             St.cur.Rcw[i] = (double)in[i];
@@ -399,23 +396,9 @@ constexpr char kPosePrevSizeErr[] =
 
 void fill_args(PosePrevArgs& G, const orbfe_pose_inertial_prev_params* P, const float* invLevelSigma2, int nLevels)
 {
-    memset(&G, 0, sizeof G);
-    fill_pose_cam(G.cam, P->cam, P->huber_delta2);
-    G.par.gravity = (double)P->gravity;
+    fill_inertial_args(G, G.par, P, invLevelSigma2, nLevels);
     G.par.priorDelta = P->prior_huber_delta;
-    for (int i = 0; i < 4; i++) {
-        G.par.chi2[i] = P->chi2[i];
-        G.par.chi2Close[i] = (float)(P->close_factor * (double)P->chi2[i]);   // float chi2close = 1.5 * chi2Mono[it] (:4100)
-    }
-    G.closeDepth = P->close_depth;
-    G.par.recoverChi2 = P->recover_chi2;
-    G.par.recoverBelow = P->recover_below;
-    G.par.recInit = P->rec_init != 0;
-    G.par.iterations = P->iterations;
-    G.par.nRounds = P->rounds;
     G.par.inlierThreshold = P->inlier_threshold;
-    G.nLevels = nLevels;
-    for (int i = 0; i < kMaxLevels; i++) G.invSigma2[i] = i < nLevels ? invLevelSigma2[i] : 0.0f;
 }
 
 }  // namespace
@@ -447,9 +430,7 @@ int pose_prev_begin(const orbfe_pose_inertial_prev_params* P, const orbfe_imu_li
 {
     const int crc = pose_prev_check(P, link, prior, info, err);
     if (crc != ORBFE_OK) return crc;
-    if (n > kPrevMaxKp) return ORBFE_ERR_INVALID_ARG;
-    if (!matched_keypoints(n, kp, mpIndex, nPoints, nLevels, first)) return ORBFE_ERR_INVALID_ARG;
-    return ORBFE_OK;
+    return pose_edge_list(nLevels, n, kp, mpIndex, nPoints, first);
 }
 
 // the device part of the host call, for the edge list `first` of pose_prev_begin (it may be empty)
@@ -459,92 +440,49 @@ int pose_prev_run(MatchScratch& m, hipStream_t s, const orbfe_pose_inertial_prev
                   float* stateOut, double* H30out, double* HpriorOut, uint8_t* outlier, int* nInliers, int* accepted,
                   orbfe_pose_inertial_prev_info* info, std::string& err)
 {
-    const int Ne = (int)first.size();
-    // up: [kp | match (edge order index into pts) | pts | depth | state | link | prior]; device only: [edgeIdx];
-    // down: [state | nInliers, accepted | rounds | H30 | Hprior | outlier | roundOutlier]
-    Carver c;
-    const size_t oKp = c.take((size_t)n * sizeof(orbfe_keypoint));
-    const size_t oMatch = c.take((size_t)n * sizeof(int));
-    const size_t oPts = c.take((size_t)Ne * 3 * sizeof(float));
-    const size_t oDepth = c.take((size_t)Ne * sizeof(float));
-    const size_t oState = c.take(kPrevStateIn * sizeof(float));
-    const size_t oLink = c.take(sizeof(orbfe_imu_link_free));
-    const size_t oPrior = c.take(sizeof(orbfe_pose_imu_prior));
-    const size_t inBytes = c.off;
-    const size_t oIdx = c.take((size_t)n * sizeof(int));
-    const size_t oStateOut = c.take(kImuState * sizeof(float));
-    const size_t oNInl = c.take(2 * sizeof(int));
-    const size_t oRounds = c.take(sizeof(PrevRoundsOut));
-    const size_t oH = c.take(kPrevH * sizeof(double));
-    const size_t oHp = c.take(kMargN * kMargN * sizeof(double));
-    const size_t oOutlier = c.take((size_t)n);
-    const size_t oRoundOut = c.take((size_t)4 * Ne);
-    const size_t resBytes = c.off - oStateOut;
-    int rc = ensure(m, c.off + 256, inBytes + resBytes + 256, err);
+    // the unit's blocks (EdgeStaging, match_common.h): up [state | link | prior]; down [state | nInliers, accepted | rounds | H30 | Hprior]
+    EdgeStaging st(n, first, trackDepth);
+    const size_t oState = st.c.take(kImuStateIn * sizeof(float));
+    const size_t oLink = st.c.take(sizeof(orbfe_imu_link_free));
+    const size_t oPrior = st.c.take(sizeof(orbfe_pose_imu_prior));
+    st.inputs_done();
+    const size_t oStateOut = st.c.take(kImuState * sizeof(float));
+    const size_t oNInl = st.c.take(2 * sizeof(int));
+    const size_t oRounds = st.c.take(sizeof(PrevRoundsOut));
+    const size_t oH = st.c.take(kPrevH * sizeof(double));
+    const size_t oHp = st.c.take(kMargN * kMargN * sizeof(double));
+    int rc = st.stage(m, kp, first, mpIndex, points, trackDepth, err);
     if (rc != ORBFE_OK) return rc;
-    uint8_t* hp = static_cast<uint8_t*>(m.hpin);
-    uint8_t* dp = static_cast<uint8_t*>(m.d);
-    if (n > 0) memcpy(hp + oKp, kp, (size_t)n * sizeof(orbfe_keypoint));
-    stage_edge_list(n, first, mpIndex, points, reinterpret_cast<int*>(hp + oMatch), reinterpret_cast<float*>(hp + oPts), trackDepth,
-                    reinterpret_cast<float*>(hp + oDepth));
-    memcpy(hp + oState, stateIn, kPrevStateIn * sizeof(float));
-    memcpy(hp + oLink, link, sizeof(orbfe_imu_link_free));
-    memcpy(hp + oPrior, prior, sizeof(orbfe_pose_imu_prior));
-    MCHK(hipMemcpyAsync(dp, hp, inBytes, hipMemcpyHostToDevice, s));
-    MCHK(hipMemsetAsync(dp + oRounds, 0, sizeof(PrevRoundsOut), s));
+    memcpy(st.host<float>(oState), stateIn, kImuStateIn * sizeof(float));
+    memcpy(st.host<orbfe_imu_link_free>(oLink), link, sizeof(orbfe_imu_link_free));
+    memcpy(st.host<orbfe_pose_imu_prior>(oPrior), prior, sizeof(orbfe_pose_imu_prior));
+    rc = st.upload(s, oRounds, sizeof(PrevRoundsOut), err);
+    if (rc != ORBFE_OK) return rc;
 
     PosePrevArgs G;
     fill_args(G, P, invLevelSigma2, nLevels);
-    G.nSingle = n;
-    G.kpStride = n;
-    G.kp = reinterpret_cast<const orbfe_keypoint*>(dp + oKp);
-    G.match = reinterpret_cast<const int*>(dp + oMatch);
-    G.nPoints = Ne;
-    G.pts = reinterpret_cast<const float*>(dp + oPts);
-    G.depth = reinterpret_cast<const float*>(dp + oDepth);
-    G.ptRec = 3;
-    G.link = reinterpret_cast<const orbfe_imu_link_free*>(dp + oLink);
-    G.prior = reinterpret_cast<const orbfe_pose_imu_prior*>(dp + oPrior);
-    G.stateIn = reinterpret_cast<const float*>(dp + oState);
-    G.stateOut = reinterpret_cast<float*>(dp + oStateOut);
-    G.H30 = reinterpret_cast<double*>(dp + oH);
-    G.Hprior = HpriorOut ? reinterpret_cast<double*>(dp + oHp) : nullptr;
-    G.outlier = dp + oOutlier;
-    G.nInliers = reinterpret_cast<int*>(dp + oNInl);
+    st.set_args(G, oNInl, oRounds);
+    G.depth = st.dev<const float>(st.oDepth);
+    G.link = st.dev<const orbfe_imu_link_free>(oLink);
+    G.prior = st.dev<const orbfe_pose_imu_prior>(oPrior);
+    G.stateIn = st.dev<const float>(oState);
+    G.stateOut = st.dev<float>(oStateOut);
+    G.H30 = st.dev<double>(oH);
+    G.Hprior = HpriorOut ? st.dev<double>(oHp) : nullptr;
     G.accepted = G.nInliers + 1;
-    G.edgeIdx = reinterpret_cast<int*>(dp + oIdx);
-    G.rounds = reinterpret_cast<PrevRoundsOut*>(dp + oRounds);
-    G.roundOutlier = dp + oRoundOut;
     hipLaunchKernelGGL(pose_prev_kernel, dim3(1), dim3(kTreeThreads), 0, s, G);
-    MCHK(hipGetLastError());
-    MCHK(hipMemcpyAsync(hp + inBytes, dp + oStateOut, resBytes, hipMemcpyDeviceToHost, s));
-    MCHK(hipStreamSynchronize(s));
-    const uint8_t* r = hp + inBytes;
-    memcpy(stateOut, r, kImuState * sizeof(float));
-    const PrevRoundsOut* I = reinterpret_cast<const PrevRoundsOut*>(r + (oRounds - oStateOut));
-    *nInliers = *reinterpret_cast<const int*>(r + (oNInl - oStateOut));
-    *accepted = *(reinterpret_cast<const int*>(r + (oNInl - oStateOut)) + 1);
-    memcpy(H30out, r + (oH - oStateOut), kPrevH * sizeof(double));
-    if (HpriorOut) memcpy(HpriorOut, r + (oHp - oStateOut), kMargN * kMargN * sizeof(double));
-    if (n > 0) memcpy(outlier, r + (oOutlier - oStateOut), (size_t)n);
+    rc = st.download(s, outlier, err);
+    if (rc != ORBFE_OK) return rc;
+    memcpy(stateOut, st.res<float>(oStateOut), kImuState * sizeof(float));
+    *nInliers = st.res<int>(oNInl)[0];
+    *accepted = st.res<int>(oNInl)[1];
+    memcpy(H30out, st.res<double>(oH), kPrevH * sizeof(double));
+    if (HpriorOut) memcpy(HpriorOut, st.res<double>(oHp), kMargN * kMargN * sizeof(double));
     if (info) {
-        uint8_t* infoOutlier = info->outlier;
-        memset(info, 0, sizeof *info);
-        info->struct_size = (int)sizeof(orbfe_pose_inertial_prev_info);
-        info->outlier = infoOutlier;
-        info->N_e = I->Ne;
-        info->rounds_run = I->roundsRun;
-        info->recovered = I->recovered;
-        memcpy(info->iterations, I->iterations, sizeof I->iterations);
-        memcpy(info->ok, I->ok, sizeof I->ok);
-        memcpy(info->n_bad, I->nBad, sizeof I->nBad);
-        memcpy(info->state, I->state, sizeof I->state);
+        const PrevRoundsOut* I = st.res<PrevRoundsOut>(oRounds);
+        fill_inertial_info(info, I, st);
         memcpy(info->prior_chi2, I->priorChi2, sizeof I->priorChi2);
         memcpy(info->prior_weight, I->priorWeight, sizeof I->priorWeight);
-        if (info->outlier && Ne > 0) {
-            memset(info->outlier, 0, (size_t)4 * Ne);
-            memcpy(info->outlier, r + (oRoundOut - oStateOut), (size_t)I->roundsRun * Ne);
-        }
     }
     return ORBFE_OK;
 }
@@ -558,7 +496,7 @@ int pose_prev_batch_device(MatchScratch& m, hipStream_t s, const orbfe_pose_iner
 {
     const int crc = pose_prev_check(P, nullptr, nullptr, nullptr, err);
     if (crc != ORBFE_OK) return crc;
-    if (kpStride > kPrevMaxKp) return ORBFE_ERR_INVALID_ARG;
+    if (kpStride > kPoseMaxKp) return ORBFE_ERR_INVALID_ARG;
     int rc = ensure(m, (size_t)batch * kpStride * sizeof(int), 0, err);
     if (rc != ORBFE_OK) return rc;
     PosePrevArgs G;

@@ -37,7 +37,6 @@ namespace orbfe {
 namespace {
 
 constexpr int kPoseOptThreads = kTreeThreads;
-constexpr int kPoseOptMaxKp = 65536;
 constexpr int kPoseOptMaxWaves = kTreeMaxWaves;
 constexpr int kPoseOptTrials = 10;
 
@@ -402,8 +401,8 @@ int pose_opt_begin(const orbfe_pose_opt_params* P, int nLevels, int n, const orb
 {
     const int crc = pose_opt_check(P, info, err);
     if (crc != ORBFE_OK) return crc;
-    if (n > kPoseOptMaxKp) return ORBFE_ERR_INVALID_ARG;
-    if (!matched_keypoints(n, kp, mpIndex, nPoints, nLevels, first)) return ORBFE_ERR_INVALID_ARG;
+    const int rc = pose_edge_list(nLevels, n, kp, mpIndex, nPoints, first);
+    if (rc != ORBFE_OK) return rc;
     const int Ne = (int)first.size();
     *nInliers = 0;
     fill_tcw(Rcw, tcw, TcwOut);
@@ -426,58 +425,33 @@ int pose_opt_run(MatchScratch& m, hipStream_t s, const orbfe_pose_opt_params* P,
     const int Ne = (int)first.size();
     if (Ne < 3) return ORBFE_ERR_INVALID_ARG;
 
-    // up: [kp | match (edge order index into pts) | pts | pose]; device only: [edgeIdx]; down: [pose | nInliers | rounds | outlier | roundOutlier]
-    Carver c;
-    const size_t oKp = c.take((size_t)n * sizeof(orbfe_keypoint));
-    const size_t oMatch = c.take((size_t)n * sizeof(int));
-    const size_t oPts = c.take((size_t)Ne * 3 * sizeof(float));
-    const size_t oPose = c.take(12 * sizeof(float));
-    const size_t inBytes = c.off;
-    const size_t oIdx = c.take((size_t)n * sizeof(int));
-    const size_t oPoseOut = c.take(12 * sizeof(float));
-    const size_t oNInl = c.take(sizeof(int));
-    const size_t oRounds = c.take(sizeof(PoseOptRounds));
-    const size_t oOutlier = c.take((size_t)n);
-    const size_t oRoundOut = c.take((size_t)4 * Ne);
-    const size_t resBytes = c.off - oPoseOut;
-    int rc = ensure(m, c.off, inBytes + resBytes + 256, err);
+    // the unit's blocks (EdgeStaging, match_common.h): up [pose]; down [pose | nInliers | rounds]
+    EdgeStaging st(n, first, nullptr);
+    const size_t oPose = st.c.take(12 * sizeof(float));
+    st.inputs_done();
+    const size_t oPoseOut = st.c.take(12 * sizeof(float));
+    const size_t oNInl = st.c.take(sizeof(int));
+    const size_t oRounds = st.c.take(sizeof(PoseOptRounds));
+    int rc = st.stage(m, kp, first, mpIndex, points, nullptr, err);
     if (rc != ORBFE_OK) return rc;
-    uint8_t* hp = static_cast<uint8_t*>(m.hpin);
-    uint8_t* dp = static_cast<uint8_t*>(m.d);
-    memcpy(hp + oKp, kp, (size_t)n * sizeof(orbfe_keypoint));
-    stage_edge_list(n, first, mpIndex, points, reinterpret_cast<int*>(hp + oMatch), reinterpret_cast<float*>(hp + oPts));
-    float* hPose = reinterpret_cast<float*>(hp + oPose);
+    float* hPose = st.host<float>(oPose);
     for (int i = 0; i < 9; i++) hPose[i] = Rcw[i];
     for (int i = 0; i < 3; i++) hPose[9 + i] = tcw[i];
-    MCHK(hipMemcpyAsync(dp, hp, inBytes, hipMemcpyHostToDevice, s));
-    MCHK(hipMemsetAsync(dp + oRounds, 0, sizeof(PoseOptRounds), s));
+    rc = st.upload(s, oRounds, sizeof(PoseOptRounds), err);
+    if (rc != ORBFE_OK) return rc;
 
     PoseOptArgs G;
     fill_args(G, P, invLevelSigma2, nLevels);
-    G.nSingle = n;
-    G.kpStride = n;
-    G.kp = reinterpret_cast<const orbfe_keypoint*>(dp + oKp);
-    G.match = reinterpret_cast<const int*>(dp + oMatch);
-    G.nPoints = Ne;
-    G.pts = reinterpret_cast<const float*>(dp + oPts);
-    G.ptRec = 3;
-    G.poseIn = reinterpret_cast<const float*>(dp + oPose);
-    G.poseOut = reinterpret_cast<float*>(dp + oPoseOut);
-    G.outlier = dp + oOutlier;
-    G.nInliers = reinterpret_cast<int*>(dp + oNInl);
-    G.edgeIdx = reinterpret_cast<int*>(dp + oIdx);
-    G.rounds = reinterpret_cast<PoseOptRounds*>(dp + oRounds);
-    G.roundOutlier = dp + oRoundOut;
+    st.set_args(G, oNInl, oRounds);
+    G.poseIn = st.dev<const float>(oPose);
+    G.poseOut = st.dev<float>(oPoseOut);
     hipLaunchKernelGGL(pose_opt_kernel, dim3(1), dim3(Ne <= 64 ? 64 : kPoseOptThreads), 0, s, G);
-    MCHK(hipGetLastError());
-    MCHK(hipMemcpyAsync(hp + inBytes, dp + oPoseOut, resBytes, hipMemcpyDeviceToHost, s));
-    MCHK(hipStreamSynchronize(s));
-    const uint8_t* r = hp + inBytes;
-    const float* pose = reinterpret_cast<const float*>(r);
-    const PoseOptRounds* I = reinterpret_cast<const PoseOptRounds*>(r + (oRounds - oPoseOut));
+    rc = st.download(s, outlier, err);
+    if (rc != ORBFE_OK) return rc;
+    const float* pose = st.res<float>(oPoseOut);
+    const PoseOptRounds* I = st.res<PoseOptRounds>(oRounds);
     fill_tcw(pose, pose + 9, TcwOut);
-    *nInliers = *reinterpret_cast<const int*>(r + (oNInl - oPoseOut));
-    memcpy(outlier, r + (oOutlier - oPoseOut), (size_t)n);
+    *nInliers = *st.res<int>(oNInl);
     if (info) {
         info->rounds_run = I->roundsRun;
         memcpy(info->iterations, I->iterations, sizeof I->iterations);
@@ -487,10 +461,7 @@ int pose_opt_run(MatchScratch& m, hipStream_t s, const orbfe_pose_opt_params* P,
         memcpy(info->pose, I->pose, sizeof I->pose);
         memcpy(info->lambda, I->lambda, sizeof I->lambda);
         memcpy(info->chi2, I->chi2, sizeof I->chi2);
-        if (info->outlier) {
-            memset(info->outlier, 0, (size_t)4 * Ne);
-            memcpy(info->outlier, r + (oRoundOut - oPoseOut), (size_t)I->roundsRun * Ne);
-        }
+        st.round_rows(info->outlier, I->roundsRun);
     }
     return ORBFE_OK;
 }
@@ -502,7 +473,7 @@ int pose_opt_batch_device(MatchScratch& m, hipStream_t s, const orbfe_pose_opt_p
 {
     const int crc = pose_opt_check(P, nullptr, err);
     if (crc != ORBFE_OK) return crc;
-    if (kpStride > kPoseOptMaxKp) return ORBFE_ERR_INVALID_ARG;
+    if (kpStride > kPoseMaxKp) return ORBFE_ERR_INVALID_ARG;
     int rc = ensure(m, (size_t)batch * kpStride * sizeof(int), 0, err);
     if (rc != ORBFE_OK) return rc;
     PoseOptArgs G;

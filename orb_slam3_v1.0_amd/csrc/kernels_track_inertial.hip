@@ -20,7 +20,6 @@ namespace orbfe {
 namespace {
 
 constexpr int kStatsThreads = 256;
-constexpr int kTrackMaxKp = 65536;   // the pose kernels' bound on kp_stride (kernels_poseimu.hip)
 
 struct TrackStatsArgs {
     const int* nKp;              // [B]
@@ -140,7 +139,7 @@ int track_inertial_batch_device(MatchScratch& m, hipStream_t s, const orbfe_trac
                                 const orbfe_world_point* mapPts, const uint8_t* mapDesc, int M, const orbfe_track_inertial_io* io,
                                 void** dLinksOut, std::string& err)
 {
-    if (kpStride > kTrackMaxKp) return ORBFE_ERR_INVALID_ARG;
+    if (kpStride > kPoseMaxKp) return ORBFE_ERR_INVALID_ARG;
     const bool fromFrame = P->predict.which == ORBFE_IMU_FROM_FRAME;
     const size_t linkBytes = fromFrame ? sizeof(orbfe_imu_link_free) : sizeof(orbfe_imu_link);
     const size_t slots = (size_t)batch * std::max(M, 1);

@@ -18,6 +18,9 @@ struct MatchScratch {
 
 void match_scratch_free(MatchScratch& m);
 
+constexpr int kPoseMaxKp = 65536;   // the pose kernels' bound on the keypoints (kp_stride) of one frame
+constexpr int kImuStateIn = 33;     // what an inertial solver reads per frame: Rcw, tcw, Rwb, twb, v, bg, ba (it writes the last kImuState)
+
 int match_projection_run(MatchScratch& m, hipStream_t s, const orbfe_frame_view* F, int M,
                          const orbfe_map_point* mps, const uint8_t* mpDesc, const int* initObs, float th,
                          int farPoints, float thFar, float nnRatio, int* matchOut, int* nMatches,

@@ -1,7 +1,9 @@
 // match_common.h -- pieces shared by the matcher translation units: descriptor distance, the rotation-consistency filter,
-// wave64 reductions, scratch arenas; and the host pieces the solver units share (the edge list, Tcw, the camera, the refusal ladder).
+// wave64 reductions, scratch arenas; and the host pieces the solver units share (the edge list, Tcw, the camera, the refusal ladder, the staging of a pose call).
 #pragma once
+#include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "match.h"
@@ -259,5 +261,139 @@ inline int solver_check_common(const Params* P, const char* entry, const char* b
         hipError_t e_ = (call);                                                             \
         if (e_ != hipSuccess) { err = std::string(#call) + ": " + hipGetErrorString(e_); return ORBFE_ERR_HIP; } \
     } while (0)
+
+// ---- what the pose solvers' host halves share (S14, S19, S20): host text only, the kernels and their Args stay per unit (r20) ----
+// what a *_begin does after its unit's check: the keypoint bound and the edge list
+inline int pose_edge_list(int nLevels, int n, const orbfe_keypoint* kp, const int* mpIndex, int nPoints, std::vector<int>& first)
+{
+    if (n > kPoseMaxKp) return ORBFE_ERR_INVALID_ARG;
+    if (!matched_keypoints(n, kp, mpIndex, nPoints, nLevels, first)) return ORBFE_ERR_INVALID_ARG;
+    return ORBFE_OK;
+}
+
+// The arenas of a host-pointer pose call, one upload and one download:
+//   up [kp | match (edge order index into pts) | pts | depth (with trackDepth) | the unit's input blocks]; device only [edgeIdx];
+//   down [the unit's result blocks | outlier | roundOutlier].
+// The unit takes its own blocks from `c`, and the order of a call is fixed: the constructor, the unit's input takes, inputs_done(),
+// the unit's result takes (the first of them is where the download starts), stage() -- which appends outlier and roundOutlier --,
+// the unit's copies into host(), upload(), set_args() and the unit's own fields, the launch, download(), then res().
+struct EdgeStaging {
+    Carver c;
+    const int n, Ne;
+    size_t oKp, oMatch, oPts, oDepth, inBytes = 0, oIdx = 0, oRes = 0, oOutlier = 0, oRoundOut = 0, resBytes = 0;
+    uint8_t *hp = nullptr, *dp = nullptr;
+
+    EdgeStaging(int n_, const std::vector<int>& first, const float* trackDepth) : n(n_), Ne((int)first.size())
+    {
+        oKp = c.take((size_t)n * sizeof(orbfe_keypoint));
+        oMatch = c.take((size_t)n * sizeof(int));
+        oPts = c.take((size_t)Ne * 3 * sizeof(float));
+        oDepth = c.take(trackDepth ? (size_t)Ne * sizeof(float) : 0);
+    }
+    void inputs_done()
+    {
+        inBytes = c.off;
+        oIdx = c.take((size_t)n * sizeof(int));
+        oRes = c.off;
+    }
+    // the arenas for the finished layout, the keypoints and the edge list `first` in the pinned one
+    int stage(MatchScratch& m, const orbfe_keypoint* kp, const std::vector<int>& first, const int* mpIndex, const float* points,
+              const float* trackDepth, std::string& err)
+    {
+        oOutlier = c.take((size_t)n);
+        oRoundOut = c.take((size_t)4 * Ne);
+        resBytes = c.off - oRes;
+        const int rc = ensure(m, c.off + 256, inBytes + resBytes + 256, err);
+        if (rc != ORBFE_OK) return rc;
+        hp = static_cast<uint8_t*>(m.hpin);
+        dp = static_cast<uint8_t*>(m.d);
+        if (n > 0) memcpy(hp + oKp, kp, (size_t)n * sizeof(orbfe_keypoint));
+        stage_edge_list(n, first, mpIndex, points, host<int>(oMatch), host<float>(oPts), trackDepth, host<float>(oDepth));
+        return ORBFE_OK;
+    }
+    template <class T> T* host(size_t o) const { return reinterpret_cast<T*>(hp + o); }   // an input block, before the upload
+    template <class T> T* dev(size_t o) const { return reinterpret_cast<T*>(dp + o); }
+    template <class T> const T* res(size_t o) const { return reinterpret_cast<const T*>(hp + inBytes + (o - oRes)); }   // after download()
+
+    // the inputs go up and the rounds record (roundsBytes at oRounds) is zeroed
+    int upload(hipStream_t s, size_t oRounds, size_t roundsBytes, std::string& err)
+    {
+        MCHK(hipMemcpyAsync(dp, hp, inBytes, hipMemcpyHostToDevice, s));
+        MCHK(hipMemsetAsync(dp + oRounds, 0, roundsBytes, s));
+        return ORBFE_OK;
+    }
+    // the fields the three Args name alike (dN stays null: one frame of n keypoints)
+    template <class Args>
+    void set_args(Args& G, size_t oNInl, size_t oRounds) const
+    {
+        G.nSingle = n;
+        G.kpStride = n;
+        G.kp = dev<const orbfe_keypoint>(oKp);
+        G.match = dev<const int>(oMatch);
+        G.nPoints = Ne;
+        G.pts = dev<const float>(oPts);
+        G.ptRec = 3;
+        G.outlier = dp + oOutlier;
+        G.nInliers = dev<int>(oNInl);
+        G.edgeIdx = dev<int>(oIdx);
+        G.rounds = dev<typename std::remove_pointer<decltype(Args::rounds)>::type>(oRounds);
+        G.roundOutlier = dp + oRoundOut;
+    }
+    // behind the launch: the result span comes down in one copy; the keypoints' flags are unpacked
+    int download(hipStream_t s, uint8_t* outlier, std::string& err)
+    {
+        MCHK(hipGetLastError());
+        MCHK(hipMemcpyAsync(hp + inBytes, dp + oRes, resBytes, hipMemcpyDeviceToHost, s));
+        MCHK(hipStreamSynchronize(s));
+        if (n > 0) memcpy(outlier, res<uint8_t>(oOutlier), (size_t)n);
+        return ORBFE_OK;
+    }
+    // info->outlier [4][N_e]: the rows of the rounds that ran, zeros below
+    void round_rows(uint8_t* out, int roundsRun) const
+    {
+        if (!out || Ne <= 0) return;
+        memset(out, 0, (size_t)4 * Ne);
+        memcpy(out, res<uint8_t>(oRoundOut), (size_t)roundsRun * Ne);
+    }
+};
+
+// what the two inertial Args hold alike; R is where the unit keeps the loop's parameters (PoseImuArgs itself, PosePrevArgs::par)
+template <class Args, class Par, class Params>
+inline void fill_inertial_args(Args& G, Par& R, const Params* P, const float* invLevelSigma2, int nLevels)
+{
+    memset(&G, 0, sizeof G);
+    fill_pose_cam(G.cam, P->cam, P->huber_delta2);
+    R.gravity = (double)P->gravity;
+    for (int i = 0; i < 4; i++) {
+        R.chi2[i] = P->chi2[i];
+        R.chi2Close[i] = (float)(P->close_factor * (double)P->chi2[i]);   // float chi2close = 1.5 * chi2Mono[it] (Optimizer.cc:3686, :4100)
+    }
+    G.closeDepth = P->close_depth;
+    R.recoverChi2 = P->recover_chi2;
+    R.recoverBelow = P->recover_below;
+    R.recInit = P->rec_init != 0;
+    R.iterations = P->iterations;
+    R.nRounds = P->rounds;
+    G.nLevels = nLevels;
+    for (int i = 0; i < kMaxLevels; i++) G.invSigma2[i] = i < nLevels ? invLevelSigma2[i] : 0.0f;
+}
+
+// the fields orbfe_pose_inertial_info and orbfe_pose_inertial_prev_info share, from the unit's rounds record
+template <class Info, class Rounds>
+inline void fill_inertial_info(Info* info, const Rounds* I, const EdgeStaging& st)
+{
+    uint8_t* infoOutlier = info->outlier;
+    memset(info, 0, sizeof *info);
+    info->struct_size = (int)sizeof(Info);
+    info->outlier = infoOutlier;
+    info->N_e = I->Ne;
+    info->rounds_run = I->roundsRun;
+    info->recovered = I->recovered;
+    memcpy(info->iterations, I->iterations, sizeof I->iterations);
+    memcpy(info->ok, I->ok, sizeof I->ok);
+    memcpy(info->n_bad, I->nBad, sizeof I->nBad);
+    memcpy(info->state, I->state, sizeof I->state);
+    st.round_rows(info->outlier, I->roundsRun);
+}
 
 }  // namespace orbfe

@@ -26,6 +26,7 @@
 #include "match_proj.h"
 #include "keyframe.h"
 #include "marginalize.h"
+#include "poseimu_math.h"
 #include "prep.h"
 #include "vocab.h"
 
@@ -247,6 +248,41 @@ struct MatchScope {
         }
     }
 };
+
+// What an entry point does once its arguments stand, with h->mu held: the device, the stream (null: the handle's), the scratch
+// hand-over, then run(s, err); a failure's text, empty or not, becomes the handle's last error.
+template <class Run>
+int match_call_locked(orbfe_handle* h, hipStream_t s, Run run)
+{
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!s) s = h->stream;
+    MatchScope scope_(h, s);
+    if (scope_.rc != ORBFE_OK) return scope_.rc;
+    std::string err;
+    const int rc = run(s, err);
+    if (rc != ORBFE_OK) h->err = err;
+    return rc;
+}
+
+template <class Run>
+int match_call(orbfe_handle* h, hipStream_t s, Run run)
+{
+    std::lock_guard<std::mutex> lk(h->mu);
+    return match_call_locked(h, s, run);
+}
+
+// A refusal in front of the lock that may carry text (h may be null).  The sites do not agree on a refusal without text, and each keeps
+// its rule: the solvers' *_batch_device (S14, S19, S20) replace the last error with the empty string (kReplace), the S22 / S23 calls
+// keep the older text (kKeep); so do the matchers, which return such refusals without coming here.
+enum RefuseText { kKeep, kReplace };
+int refuse(orbfe_handle* h, int rc, const std::string& err, RefuseText empty)
+{
+    if (h && (empty == kReplace || !err.empty())) {
+        std::lock_guard<std::mutex> lk(h->mu);
+        h->err = err;
+    }
+    return rc;
+}
 
 int cv_round_f(float v) { return (int)lrintf(v); }
 
@@ -2075,15 +2111,10 @@ int orbfe_match_projection(orbfe_handle* h, const orbfe_frame_view* F, int M, co
 {
     if (!h || !F || !match_out || !n_matches || M < 0 || F->n < 0) return ORBFE_ERR_INVALID_ARG;
     if ((M > 0 && (!mps || !mp_desc)) || (F->n > 0 && (!F->kp || !F->desc)) || !F->scale_factors) return ORBFE_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    std::string err;
-    MatchScope scope_(h, h->stream);
-    if (scope_.rc != ORBFE_OK) return scope_.rc;
-    int rc = match_projection_run(h->match, h->stream, F, M, mps, mp_desc, init_obs, th, far_points, th_far, nn_ratio,
-                                  match_out, n_matches, err);
-    if (rc != ORBFE_OK) h->err = err;
-    return rc;
+    return match_call(h, nullptr, [&](hipStream_t s, std::string& err) {
+        return match_projection_run(h->match, s, F, M, mps, mp_desc, init_obs, th, far_points, th_far, nn_ratio, match_out, n_matches,
+                                    err);
+    });
 }
 
 int orbfe_match_projection_batch_device(orbfe_handle* h, int batch, const orbfe_keypoint* d_kp, const uint8_t* d_desc,
@@ -2096,17 +2127,11 @@ int orbfe_match_projection_batch_device(orbfe_handle* h, int batch, const orbfe_
         grid_cols < 1 || grid_rows < 1)
         return ORBFE_ERR_INVALID_ARG;
     if (M > 0 && (!d_mps || !d_mp_desc)) return ORBFE_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : h->stream;
-    std::string err;
-    MatchScope scope_(h, s);
-    if (scope_.rc != ORBFE_OK) return scope_.rc;
-    int rc = match_projection_batch_device(h->match, s, batch, d_kp, d_desc, d_n, kp_stride, grid_cols, grid_rows, min_x,
-                                           min_y, inv_w, inv_h, h->dSf, h->nLevels, M, d_mps, d_mp_desc, d_init_obs, th,
-                                           far_points, th_far, nn_ratio, d_match_out, d_n_matches, err);
-    if (rc != ORBFE_OK) h->err = err;
-    return rc;
+    return match_call(h, (hipStream_t)stream_, [&](hipStream_t s, std::string& err) {
+        return match_projection_batch_device(h->match, s, batch, d_kp, d_desc, d_n, kp_stride, grid_cols, grid_rows, min_x, min_y, inv_w,
+                                             inv_h, h->dSf, h->nLevels, M, d_mps, d_mp_desc, d_init_obs, th, far_points, th_far, nn_ratio,
+                                             d_match_out, d_n_matches, err);
+    });
 }
 
 int orbfe_match_initialization(orbfe_handle* h, const orbfe_frame_view* F1, const orbfe_frame_view* F2, int window_size,
@@ -2116,15 +2141,9 @@ int orbfe_match_initialization(orbfe_handle* h, const orbfe_frame_view* F1, cons
         return ORBFE_ERR_INVALID_ARG;
     if ((F1->n > 0 && (!F1->kp || !F1->desc)) || (F2->n > 0 && (!F2->kp || !F2->desc)) || F2->grid_cols < 1 || F2->grid_rows < 1)
         return ORBFE_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    std::string err;
-    MatchScope scope_(h, h->stream);
-    if (scope_.rc != ORBFE_OK) return scope_.rc;
-    int rc = match_initialization_run(h->match, h->stream, F1, F2, window_size, nn_ratio, check_orientation, matches12_out,
-                                      n_matches, err);
-    if (rc != ORBFE_OK) h->err = err;
-    return rc;
+    return match_call(h, nullptr, [&](hipStream_t s, std::string& err) {
+        return match_initialization_run(h->match, s, F1, F2, window_size, nn_ratio, check_orientation, matches12_out, n_matches, err);
+    });
 }
 
 int orbfe_project_map_points_device(orbfe_handle* h, const orbfe_frustum* frustum, int n, const orbfe_world_point* d_points,
@@ -2186,15 +2205,10 @@ int orbfe_fuse_search(orbfe_handle* h, const orbfe_frame_view* KF, const float* 
         return ORBFE_ERR_INVALID_ARG;
     const int rc0 = frustum_validate(frustum);
     if (rc0 != ORBFE_OK) return rc0;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    std::string err;
-    MatchScope scope_(h, h->stream);
-    if (scope_.rc != ORBFE_OK) return scope_.rc;
-    const int rc = fuse_search_run(h->match, h->stream, KF, inv_level_sigma2, u_right, frustum, th, M, points, mp_desc, 1, -1,
-                                   best_idx_out, best_dist_out, err);
-    if (rc != ORBFE_OK) h->err = err;
-    return rc;
+    return match_call(h, nullptr, [&](hipStream_t s, std::string& err) {
+        return fuse_search_run(h->match, s, KF, inv_level_sigma2, u_right, frustum, th, M, points, mp_desc, 1, -1, best_idx_out,
+                               best_dist_out, err);
+    });
 }
 
 int orbfe_fuse_search_right(orbfe_handle* h, const orbfe_frame_view* KF, int n_right, const float* inv_level_sigma2,
@@ -2207,15 +2221,10 @@ int orbfe_fuse_search_right(orbfe_handle* h, const orbfe_frame_view* KF, int n_r
         return ORBFE_ERR_INVALID_ARG;
     const int rc0 = frustum_validate(frustum);
     if (rc0 != ORBFE_OK) return rc0;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    std::string err;
-    MatchScope scope_(h, h->stream);
-    if (scope_.rc != ORBFE_OK) return scope_.rc;
-    const int rc = fuse_search_run(h->match, h->stream, KF, inv_level_sigma2, u_right, frustum, th, M, points, mp_desc, 1,
-                                   n_right, best_idx_out, best_dist_out, err);
-    if (rc != ORBFE_OK) h->err = err;
-    return rc;
+    return match_call(h, nullptr, [&](hipStream_t s, std::string& err) {
+        return fuse_search_run(h->match, s, KF, inv_level_sigma2, u_right, frustum, th, M, points, mp_desc, 1, n_right, best_idx_out,
+                               best_dist_out, err);
+    });
 }
 
 static bool view_args_bad(const orbfe_frame_view* V)
@@ -2230,15 +2239,10 @@ int orbfe_fuse_search_sim3(orbfe_handle* h, const orbfe_frame_view* KF, const or
         return ORBFE_ERR_INVALID_ARG;
     const int rc0 = frustum_validate(frustum);
     if (rc0 != ORBFE_OK) return rc0;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    std::string err;
-    MatchScope scope_(h, h->stream);
-    if (scope_.rc != ORBFE_OK) return scope_.rc;
-    const int rc = fuse_search_run(h->match, h->stream, KF, nullptr, nullptr, frustum, th, M, points, mp_desc, 0, -1,
-                                   best_idx_out, best_dist_out, err);
-    if (rc != ORBFE_OK) h->err = err;
-    return rc;
+    return match_call(h, nullptr, [&](hipStream_t s, std::string& err) {
+        return fuse_search_run(h->match, s, KF, nullptr, nullptr, frustum, th, M, points, mp_desc, 0, -1, best_idx_out, best_dist_out,
+                               err);
+    });
 }
 
 static bool sim3_view_bad(const orbfe_sim3_view* D)
@@ -2254,15 +2258,9 @@ int orbfe_search_by_sim3(orbfe_handle* h, const orbfe_frame_view* KF1, const orb
     if (!h || view_args_bad(KF1) || view_args_bad(KF2) || sim3_view_bad(dir12) || sim3_view_bad(dir21) || !n_found ||
         (KF1->n > 0 && (!mp1 || !mp_desc1 || !match12_out)) || (KF2->n > 0 && (!mp2 || !mp_desc2)))
         return ORBFE_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    std::string err;
-    MatchScope scope_(h, h->stream);
-    if (scope_.rc != ORBFE_OK) return scope_.rc;
-    const int rc = search_by_sim3_run(h->match, h->stream, KF1, KF2, dir12, dir21, mp1, mp_desc1, mp2, mp_desc2, th,
-                                      match12_out, n_found, err);
-    if (rc != ORBFE_OK) h->err = err;
-    return rc;
+    return match_call(h, nullptr, [&](hipStream_t s, std::string& err) {
+        return search_by_sim3_run(h->match, s, KF1, KF2, dir12, dir21, mp1, mp_desc1, mp2, mp_desc2, th, match12_out, n_found, err);
+    });
 }
 
 int orbfe_match_projection_keyframe(orbfe_handle* h, const orbfe_frame_view* frame, const orbfe_frustum* frustum,
@@ -2275,15 +2273,10 @@ int orbfe_match_projection_keyframe(orbfe_handle* h, const orbfe_frame_view* fra
         return ORBFE_ERR_INVALID_ARG;
     const int rc0 = frustum_validate(frustum);
     if (rc0 != ORBFE_OK) return rc0;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    std::string err;
-    MatchScope scope_(h, h->stream);
-    if (scope_.rc != ORBFE_OK) return scope_.rc;
-    const int rc = match_projection_kf_run(h->match, h->stream, frame, frustum, n_points, points, mp_desc, kf_angle,
-                                           frame_has_mp, th, check_orientation, match_out, n_matches, err);
-    if (rc != ORBFE_OK) h->err = err;
-    return rc;
+    return match_call(h, nullptr, [&](hipStream_t s, std::string& err) {
+        return match_projection_kf_run(h->match, s, frame, frustum, n_points, points, mp_desc, kf_angle, frame_has_mp, th,
+                                       check_orientation, match_out, n_matches, err);
+    });
 }
 
 int orbfe_match_triangulation(orbfe_handle* h, int n_groups, const int* kf1_off, const int* kf1_idx, const int* kf2_off,
@@ -2303,16 +2296,10 @@ int orbfe_match_triangulation(orbfe_handle* h, int n_groups, const int* kf1_off,
         h->err = "orbfe_tri_params.struct_size does not match this library (rebuild the caller against include/orbfe.h)";
         return ORBFE_ERR_INVALID_ARG;
     }
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    std::string err;
-    MatchScope scope_(h, h->stream);
-    if (scope_.rc != ORBFE_OK) return scope_.rc;
-    const int rc = match_triangulation_run(h->match, h->stream, n_groups, kf1_off, kf1_idx, kf2_off, kf2_idx, n1, kp1, desc1,
-                                           has_mp1, stereo1, n2, kp2, desc2, has_mp2, stereo2, scale_factors2, n_levels2,
-                                           params, matches12_out, n_matches, err);
-    if (rc != ORBFE_OK) h->err = err;
-    return rc;
+    return match_call(h, nullptr, [&](hipStream_t s, std::string& err) {
+        return match_triangulation_run(h->match, s, n_groups, kf1_off, kf1_idx, kf2_off, kf2_idx, n1, kp1, desc1, has_mp1, stereo1, n2, kp2,
+                                       desc2, has_mp2, stereo2, scale_factors2, n_levels2, params, matches12_out, n_matches, err);
+    });
 }
 
 struct orbfe_keyframe {
@@ -2369,15 +2356,11 @@ int orbfe_fuse_search_keyframe(orbfe_handle* h, const orbfe_keyframe* kf, const 
         return ORBFE_ERR_INVALID_ARG;
     const int rc0 = frustum_validate(frustum);
     if (rc0 != ORBFE_OK) return rc0;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    std::string err;
-    MatchScope scope_(h, h->stream);  // also orders the call behind an orbfe_map_update of another stream's making
-    if (scope_.rc != ORBFE_OK) return scope_.rc;
-    const int rc = fuse_search_keyframe_run(h->match, h->stream, kf->k, map->cap, map->dPts, map->dDesc, M, ids, frustum, th,
-                                            best_idx_out, best_dist_out, err);
-    if (rc != ORBFE_OK) h->err = err;
-    return rc;
+    // the scope also orders the call behind an orbfe_map_update of another stream's making
+    return match_call(h, nullptr, [&](hipStream_t s, std::string& err) {
+        return fuse_search_keyframe_run(h->match, s, kf->k, map->cap, map->dPts, map->dDesc, M, ids, frustum, th, best_idx_out,
+                                        best_dist_out, err);
+    });
 }
 
 int orbfe_fuse_search_keyframes(orbfe_handle* h, int K, const orbfe_keyframe* const* kfs, const orbfe_frustum* frusta,
@@ -2404,14 +2387,11 @@ int orbfe_fuse_search_keyframes(orbfe_handle* h, int K, const orbfe_keyframe* co
         if (kd[(size_t)k]->n > 0 && M > 0 && frusta[k].n_levels > kd[(size_t)k]->nLevels) return ORBFE_ERR_INVALID_ARG;
     }
     if (K == 0 || M == 0) return ORBFE_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    std::string err;
-    MatchScope scope_(h, h->stream);  // also orders the call behind an orbfe_map_update of another stream's making
-    if (scope_.rc != ORBFE_OK) return scope_.rc;
-    const int rc = fuse_search_keyframes_run(h->match, h->stream, K, kd.data(), frusta, map->cap, map->dPts, map->dDesc, M, ids, skip, th,
-                                             best_idx_out, best_dist_out, cand_cap, cand_idx_out, cand_count_out, err);
-    if (rc != ORBFE_OK) h->err = err;
-    return rc;
+    // the scope also orders the call behind an orbfe_map_update of another stream's making
+    return match_call_locked(h, nullptr, [&](hipStream_t s, std::string& err) {
+        return fuse_search_keyframes_run(h->match, s, K, kd.data(), frusta, map->cap, map->dPts, map->dDesc, M, ids, skip, th, best_idx_out,
+                                         best_dist_out, cand_cap, cand_idx_out, cand_count_out, err);
+    });
 }
 
 int orbfe_fuse_select(const int* cand_idx, int cand_count, int cand_cap, const uint8_t* kf_desc, int n_kf, const uint8_t* mp_desc,
@@ -2435,15 +2415,9 @@ int orbfe_match_triangulation_batch(orbfe_handle* h, const orbfe_keyframe* kf1, 
         k2[(size_t)k] = kf2[k]->k;
     }
     if (kf1->device != h->device) return ORBFE_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    std::string err;
-    MatchScope scope_(h, h->stream);
-    if (scope_.rc != ORBFE_OK) return scope_.rc;
-    const int rc = match_triangulation_batch_run(h->match, h->stream, kf1->k, has_mp1, K, k2.data(), has_mp2, params, raw_match12,
-                                                 raw_bin, err);
-    if (rc != ORBFE_OK) h->err = err;
-    return rc;
+    return match_call(h, nullptr, [&](hipStream_t s, std::string& err) {
+        return match_triangulation_batch_run(h->match, s, kf1->k, has_mp1, K, k2.data(), has_mp2, params, raw_match12, raw_bin, err);
+    });
 }
 
 int orbfe_create_new_points_batch(orbfe_handle* h, const orbfe_keyframe* kf1, const uint8_t* has_mp1, int K,
@@ -2461,15 +2435,10 @@ int orbfe_create_new_points_batch(orbfe_handle* h, const orbfe_keyframe* kf1, co
         k2[(size_t)k] = kf2[k]->k;
     }
     if (kf1->device != h->device || kf1->owner != h) return ORBFE_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    std::string err;
-    MatchScope scope_(h, h->stream);
-    if (scope_.rc != ORBFE_OK) return scope_.rc;
-    const int rc = match_triangulation_batch_run(h->match, h->stream, kf1->k, has_mp1, K, k2.data(), has_mp2, tri_params, raw_match12,
-                                                 raw_bin, err, np_params, x3d_out, verdict_out);
-    if (rc != ORBFE_OK) h->err = err;
-    return rc;
+    return match_call(h, nullptr, [&](hipStream_t s, std::string& err) {
+        return match_triangulation_batch_run(h->match, s, kf1->k, has_mp1, K, k2.data(), has_mp2, tri_params, raw_match12, raw_bin, err,
+                                             np_params, x3d_out, verdict_out);
+    });
 }
 
 int orbfe_triangulate_pairs(orbfe_handle* h, const orbfe_keyframe* kf1, const orbfe_keyframe* kf2,
@@ -2480,14 +2449,9 @@ int orbfe_triangulate_pairs(orbfe_handle* h, const orbfe_keyframe* kf1, const or
         return ORBFE_ERR_INVALID_ARG;
     if (np_params->struct_size != (int)sizeof(orbfe_newpoint_params)) return ORBFE_ERR_INVALID_ARG;
     if (kf1->device != h->device || kf2->device != h->device || kf1->owner != h || kf2->owner != h) return ORBFE_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    std::string err;
-    MatchScope scope_(h, h->stream);
-    if (scope_.rc != ORBFE_OK) return scope_.rc;
-    const int rc = triangulate_pairs_run(h->match, h->stream, kf1->k, kf2->k, np_params, n_pairs, idx1, idx2, x3d_out, verdict_out, err);
-    if (rc != ORBFE_OK) h->err = err;
-    return rc;
+    return match_call(h, nullptr, [&](hipStream_t s, std::string& err) {
+        return triangulate_pairs_run(h->match, s, kf1->k, kf2->k, np_params, n_pairs, idx1, idx2, x3d_out, verdict_out, err);
+    });
 }
 
 int orbfe_two_view_reconstruct(orbfe_handle* h, const orbfe_two_view_params* p, int n1, const orbfe_keypoint* kp1, int n2,
@@ -2497,15 +2461,9 @@ int orbfe_two_view_reconstruct(orbfe_handle* h, const orbfe_two_view_params* p, 
     if (!h || !p || n1 < 0 || n2 < 0 || !reconstructed || !R21 || !t21 || (n1 > 0 && (!kp1 || !matches12 || !p3d || !triangulated)) ||
         (n2 > 0 && !kp2))
         return ORBFE_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    std::string err;
-    MatchScope scope_(h, h->stream);
-    if (scope_.rc != ORBFE_OK) return scope_.rc;
-    const int rc = two_view_run(h->match, h->stream, p, n1, kp1, n2, kp2, matches12, sets, reconstructed, R21, t21, p3d, triangulated,
-                                info, err);
-    if (rc != ORBFE_OK) h->err = err;
-    return rc;
+    return match_call(h, nullptr, [&](hipStream_t s, std::string& err) {
+        return two_view_run(h->match, s, p, n1, kp1, n2, kp2, matches12, sets, reconstructed, R21, t21, p3d, triangulated, info, err);
+    });
 }
 
 int orbfe_mlpnp_plan(const orbfe_mlpnp_params* p, int N, int* min_inliers, int* max_its, int* total_iterations)
@@ -2521,15 +2479,10 @@ int orbfe_mlpnp_ransac(orbfe_handle* h, const orbfe_mlpnp_params* p, int n, cons
     if (!h || !p || n < 0 || n_points < 0 || n_sets < 0 || !solved || !Tcw || !n_inliers || !no_more ||
         (n > 0 && (!kp || !mp_index || !inliers)) || (n_points > 0 && !points))
         return ORBFE_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    std::string err;
-    MatchScope scope_(h, h->stream);
-    if (scope_.rc != ORBFE_OK) return scope_.rc;
-    const int rc = mlpnp_run(h->match, h->stream, p, h->sig2, h->nLevels, n, kp, mp_index, n_points, points, sets, n_sets, solved, Tcw,
-                             inliers, n_inliers, no_more, info, err);
-    if (rc != ORBFE_OK) h->err = err;
-    return rc;
+    return match_call(h, nullptr, [&](hipStream_t s, std::string& err) {
+        return mlpnp_run(h->match, s, p, h->sig2, h->nLevels, n, kp, mp_index, n_points, points, sets, n_sets, solved, Tcw, inliers,
+                         n_inliers, no_more, info, err);
+    });
 }
 
 int orbfe_pose_optimization(orbfe_handle* h, const orbfe_pose_opt_params* p, int n, const orbfe_keypoint* kp, const int* mp_index,
@@ -2552,13 +2505,10 @@ int orbfe_pose_optimization(orbfe_handle* h, const orbfe_pose_opt_params* p, int
         return rc;
     }
     if (first.size() < 3) return ORBFE_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    MatchScope scope_(h, h->stream);
-    if (scope_.rc != ORBFE_OK) return scope_.rc;
-    rc = pose_opt_run(h->match, h->stream, p, h->invSig2, h->nLevels, n, kp, mp_index, points, Rcw, tcw, first, Tcw_out, outlier_out, n_inliers,
-                      info, err);
-    if (rc != ORBFE_OK) h->err = err;
-    return rc;
+    return match_call_locked(h, nullptr, [&](hipStream_t s, std::string& e) {
+        return pose_opt_run(h->match, s, p, h->invSig2, h->nLevels, n, kp, mp_index, points, Rcw, tcw, first, Tcw_out, outlier_out, n_inliers,
+                            info, e);
+    });
 }
 
 int orbfe_pose_optimization_batch_device(orbfe_handle* h, const orbfe_pose_opt_params* p, int batch, const orbfe_keypoint* d_kp,
@@ -2569,25 +2519,36 @@ int orbfe_pose_optimization_batch_device(orbfe_handle* h, const orbfe_pose_opt_p
     if (!p) return ORBFE_ERR_INVALID_ARG;
     std::string err;
     const int crc = pose_opt_check(p, nullptr, err);
-    if (crc != ORBFE_OK) {
-        if (h) {
-            std::lock_guard<std::mutex> lk(h->mu);
-            h->err = err;
-        }
-        return crc;
-    }
+    if (crc != ORBFE_OK) return refuse(h, crc, err, kReplace);
     if (!h || batch < 1 || !d_kp || !d_n || kp_stride < 1 || !d_match || n_map_points < 0 || (n_map_points > 0 && !d_points) ||
         point_stride_frames < 0 || !d_pose_in || !d_pose_out || !d_outlier || !d_n_inliers)
         return ORBFE_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : h->stream;
-    MatchScope scope_(h, s);
-    if (scope_.rc != ORBFE_OK) return scope_.rc;
-    const int rc = pose_opt_batch_device(h->match, s, p, h->invSig2, h->nLevels, batch, d_kp, d_n, kp_stride, d_match, n_map_points,
-                                         d_points, point_stride_frames, d_pose_in, d_pose_out, d_outlier, d_n_inliers, err);
-    if (rc != ORBFE_OK) h->err = err;
-    return rc;
+    return match_call(h, (hipStream_t)stream_, [&](hipStream_t s, std::string& e) {
+        return pose_opt_batch_device(h->match, s, p, h->invSig2, h->nLevels, batch, d_kp, d_n, kp_stride, d_match, n_map_points, d_points,
+                                     point_stride_frames, d_pose_in, d_pose_out, d_outlier, d_n_inliers, e);
+    });
+}
+
+// the inertial solvers' state as they read it, in[kImuStateIn], and as they write it, out[kImuState]
+static void pack_imu_state(float* in, const float* Rcw, const float* tcw, const float* Rwb, const float* twb, const float* v, const float* bg,
+                           const float* ba)
+{
+    memcpy(in, Rcw, 9 * sizeof(float));
+    memcpy(in + 9, tcw, 3 * sizeof(float));
+    memcpy(in + 12, Rwb, 9 * sizeof(float));
+    memcpy(in + 21, twb, 3 * sizeof(float));
+    memcpy(in + 24, v, 3 * sizeof(float));
+    memcpy(in + 27, bg, 3 * sizeof(float));
+    memcpy(in + 30, ba, 3 * sizeof(float));
+}
+
+static void unpack_imu_state(const float* out, float* Rwb, float* twb, float* v, float* bg, float* ba)
+{
+    memcpy(Rwb, out, 9 * sizeof(float));
+    memcpy(twb, out + 9, 3 * sizeof(float));
+    memcpy(v, out + 12, 3 * sizeof(float));
+    memcpy(bg, out + 15, 3 * sizeof(float));
+    memcpy(ba, out + 18, 3 * sizeof(float));
 }
 
 int orbfe_pose_inertial_optimization_last_keyframe(orbfe_handle* h, const orbfe_pose_inertial_params* p, const orbfe_imu_link* link,
@@ -2613,29 +2574,14 @@ int orbfe_pose_inertial_optimization_last_keyframe(orbfe_handle* h, const orbfe_
         h->err = err;
         return rc;
     }
-    HIPCHK(h, hipSetDevice(h->device));
-    MatchScope scope_(h, h->stream);
-    if (scope_.rc != ORBFE_OK) return scope_.rc;
-    float in[33], out[21];
-    memcpy(in, Rcw, 9 * sizeof(float));
-    memcpy(in + 9, tcw, 3 * sizeof(float));
-    memcpy(in + 12, Rwb, 9 * sizeof(float));
-    memcpy(in + 21, twb, 3 * sizeof(float));
-    memcpy(in + 24, v, 3 * sizeof(float));
-    memcpy(in + 27, bg, 3 * sizeof(float));
-    memcpy(in + 30, ba, 3 * sizeof(float));
-    rc = pose_imu_run(h->match, h->stream, p, link, h->invSig2, h->nLevels, n, kp, mp_index, points, track_depth, in, first, out, H_out,
-                      outlier_out, n_inliers, info, err);
-    if (rc != ORBFE_OK) {
-        h->err = err;
-        return rc;
-    }
-    memcpy(Rwb_out, out, 9 * sizeof(float));
-    memcpy(twb_out, out + 9, 3 * sizeof(float));
-    memcpy(v_out, out + 12, 3 * sizeof(float));
-    memcpy(bg_out, out + 15, 3 * sizeof(float));
-    memcpy(ba_out, out + 18, 3 * sizeof(float));
-    return rc;
+    return match_call_locked(h, nullptr, [&](hipStream_t s, std::string& e) {
+        float in[kImuStateIn], out[kImuState];
+        pack_imu_state(in, Rcw, tcw, Rwb, twb, v, bg, ba);
+        const int r = pose_imu_run(h->match, s, p, link, h->invSig2, h->nLevels, n, kp, mp_index, points, track_depth, in, first, out, H_out,
+                                   outlier_out, n_inliers, info, e);
+        if (r == ORBFE_OK) unpack_imu_state(out, Rwb_out, twb_out, v_out, bg_out, ba_out);
+        return r;
+    });
 }
 
 int orbfe_pose_inertial_optimization_batch_device(orbfe_handle* h, const orbfe_pose_inertial_params* p, int batch,
@@ -2648,27 +2594,15 @@ int orbfe_pose_inertial_optimization_batch_device(orbfe_handle* h, const orbfe_p
     if (!p) return ORBFE_ERR_INVALID_ARG;
     std::string err;
     const int crc = pose_imu_check(p, nullptr, nullptr, err);
-    if (crc != ORBFE_OK) {
-        if (h) {
-            std::lock_guard<std::mutex> lk(h->mu);
-            h->err = err;
-        }
-        return crc;
-    }
+    if (crc != ORBFE_OK) return refuse(h, crc, err, kReplace);
     if (!h || batch < 1 || !d_links || !d_kp || !d_n || kp_stride < 1 || !d_match || n_map_points < 0 ||
         (n_map_points > 0 && (!d_points || !d_track_depth)) || point_stride_frames < 0 || !d_state_in || !d_state_out || !d_H_out ||
         !d_outlier || !d_n_inliers)
         return ORBFE_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : h->stream;
-    MatchScope scope_(h, s);
-    if (scope_.rc != ORBFE_OK) return scope_.rc;
-    const int rc = pose_imu_batch_device(h->match, s, p, h->invSig2, h->nLevels, batch, d_links, d_kp, d_n, kp_stride, d_match, n_map_points,
-                                         d_points, point_stride_frames, d_track_depth, d_state_in, d_state_out, d_H_out, d_outlier,
-                                         d_n_inliers, err);
-    if (rc != ORBFE_OK) h->err = err;
-    return rc;
+    return match_call(h, (hipStream_t)stream_, [&](hipStream_t s, std::string& e) {
+        return pose_imu_batch_device(h->match, s, p, h->invSig2, h->nLevels, batch, d_links, d_kp, d_n, kp_stride, d_match, n_map_points,
+                                     d_points, point_stride_frames, d_track_depth, d_state_in, d_state_out, d_H_out, d_outlier, d_n_inliers, e);
+    });
 }
 
 int orbfe_pose_inertial_optimization_last_frame(orbfe_handle* h, const orbfe_pose_inertial_prev_params* p,
@@ -2696,29 +2630,14 @@ int orbfe_pose_inertial_optimization_last_frame(orbfe_handle* h, const orbfe_pos
         h->err = err;
         return rc;
     }
-    HIPCHK(h, hipSetDevice(h->device));
-    MatchScope scope_(h, h->stream);
-    if (scope_.rc != ORBFE_OK) return scope_.rc;
-    float in[33], out[21];
-    memcpy(in, Rcw, 9 * sizeof(float));
-    memcpy(in + 9, tcw, 3 * sizeof(float));
-    memcpy(in + 12, Rwb, 9 * sizeof(float));
-    memcpy(in + 21, twb, 3 * sizeof(float));
-    memcpy(in + 24, v, 3 * sizeof(float));
-    memcpy(in + 27, bg, 3 * sizeof(float));
-    memcpy(in + 30, ba, 3 * sizeof(float));
-    rc = pose_prev_run(h->match, h->stream, p, link, prior, h->invSig2, h->nLevels, n, kp, mp_index, points, track_depth, in, first, out,
-                       H30_out, Hprior_out, outlier_out, n_inliers, accepted, info, err);
-    if (rc != ORBFE_OK) {
-        h->err = err;
-        return rc;
-    }
-    memcpy(Rwb_out, out, 9 * sizeof(float));
-    memcpy(twb_out, out + 9, 3 * sizeof(float));
-    memcpy(v_out, out + 12, 3 * sizeof(float));
-    memcpy(bg_out, out + 15, 3 * sizeof(float));
-    memcpy(ba_out, out + 18, 3 * sizeof(float));
-    return rc;
+    return match_call_locked(h, nullptr, [&](hipStream_t s, std::string& e) {
+        float in[kImuStateIn], out[kImuState];
+        pack_imu_state(in, Rcw, tcw, Rwb, twb, v, bg, ba);
+        const int r = pose_prev_run(h->match, s, p, link, prior, h->invSig2, h->nLevels, n, kp, mp_index, points, track_depth, in, first, out,
+                                    H30_out, Hprior_out, outlier_out, n_inliers, accepted, info, e);
+        if (r == ORBFE_OK) unpack_imu_state(out, Rwb_out, twb_out, v_out, bg_out, ba_out);
+        return r;
+    });
 }
 
 int orbfe_pose_inertial_optimization_last_frame_batch_device(orbfe_handle* h, const orbfe_pose_inertial_prev_params* p, int batch,
@@ -2733,27 +2652,16 @@ int orbfe_pose_inertial_optimization_last_frame_batch_device(orbfe_handle* h, co
     if (!p) return ORBFE_ERR_INVALID_ARG;
     std::string err;
     const int crc = pose_prev_check(p, nullptr, nullptr, nullptr, err);
-    if (crc != ORBFE_OK) {
-        if (h) {
-            std::lock_guard<std::mutex> lk(h->mu);
-            h->err = err;
-        }
-        return crc;
-    }
+    if (crc != ORBFE_OK) return refuse(h, crc, err, kReplace);
     if (!h || batch < 1 || !d_links || !d_priors || !d_kp || !d_n || kp_stride < 1 || !d_match || n_map_points < 0 ||
         (n_map_points > 0 && (!d_points || !d_track_depth)) || point_stride_frames < 0 || !d_state_in || !d_state_out || !d_H30_out ||
         !d_outlier || !d_n_inliers || !d_accepted)
         return ORBFE_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : h->stream;
-    MatchScope scope_(h, s);
-    if (scope_.rc != ORBFE_OK) return scope_.rc;
-    const int rc = pose_prev_batch_device(h->match, s, p, h->invSig2, h->nLevels, batch, d_links, d_priors, d_kp, d_n, kp_stride, d_match,
-                                          n_map_points, d_points, point_stride_frames, d_track_depth, d_state_in, d_state_out, d_H30_out,
-                                          d_Hprior_out, d_outlier, d_n_inliers, d_accepted, err);
-    if (rc != ORBFE_OK) h->err = err;
-    return rc;
+    return match_call(h, (hipStream_t)stream_, [&](hipStream_t s, std::string& e) {
+        return pose_prev_batch_device(h->match, s, p, h->invSig2, h->nLevels, batch, d_links, d_priors, d_kp, d_n, kp_stride, d_match,
+                                      n_map_points, d_points, point_stride_frames, d_track_depth, d_state_in, d_state_out, d_H30_out,
+                                      d_Hprior_out, d_outlier, d_n_inliers, d_accepted, e);
+    });
 }
 
 int orbfe_marginalize_pose_imu(const double* H, double* Hp)
@@ -2765,32 +2673,6 @@ int orbfe_marginalize_pose_imu(const double* H, double* Hp)
     return ORBFE_OK;
 }
 
-// what every S22 call does once its arguments stand: the handle's lock, device and scratch, then `run`
-extern "C++" {
-template <class Run>
-static int imu_call(orbfe_handle* h, hipStream_t s, Run run)
-{
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    if (!s) s = h->stream;
-    MatchScope scope_(h, s);
-    if (scope_.rc != ORBFE_OK) return scope_.rc;
-    std::string err;
-    const int rc = run(s, err);
-    if (rc != ORBFE_OK) h->err = err;
-    return rc;
-}
-}  // extern "C++"
-
-static int imu_refuse(orbfe_handle* h, int rc, const std::string& err)
-{
-    if (h && !err.empty()) {
-        std::lock_guard<std::mutex> lk(h->mu);
-        h->err = err;
-    }
-    return rc;
-}
-
 int orbfe_imu_preintegrate_frame(orbfe_handle* h, const orbfe_imu_noise* noise, int n_samples, const orbfe_imu_sample* samples,
                                  double t_prev, double t_cur, const float* frame_bias, orbfe_imu_preint* kf, orbfe_imu_preint* frame,
                                  orbfe_imu_step* steps_out, int* n_steps)
@@ -2799,13 +2681,13 @@ int orbfe_imu_preintegrate_frame(orbfe_handle* h, const orbfe_imu_noise* noise, 
     std::string err;
     // *frame is written whole when there is a step; its size field is checked all the same: it says what the caller compiled against
     const int crc = imu_check(noise, nullptr, kf, frame, err);
-    if (crc != ORBFE_OK) return imu_refuse(h, crc, err);
+    if (crc != ORBFE_OK) return refuse(h, crc, err, kKeep);
     if (!h) return ORBFE_ERR_INVALID_ARG;
     if (n_samples < 2) {   // (:235-238)
         *n_steps = 0;
         return ORBFE_OK;
     }
-    return imu_call(h, nullptr, [&](hipStream_t s, std::string& e) {
+    return match_call(h, nullptr, [&](hipStream_t s, std::string& e) {
         return imu_preintegrate_run(h->match, s, noise, n_samples, samples, t_prev, t_cur, frame_bias, kf, frame, steps_out, n_steps, e);
     });
 }
@@ -2816,9 +2698,9 @@ int orbfe_imu_reintegrate(orbfe_handle* h, const orbfe_imu_noise* noise, const f
     if (!noise || !bias || !out || n_steps < 0 || (n_steps > 0 && !steps)) return ORBFE_ERR_INVALID_ARG;
     std::string err;
     const int crc = imu_check(noise, nullptr, nullptr, nullptr, err);
-    if (crc != ORBFE_OK) return imu_refuse(h, crc, err);
+    if (crc != ORBFE_OK) return refuse(h, crc, err, kKeep);
     if (!h) return ORBFE_ERR_INVALID_ARG;
-    return imu_call(h, nullptr, [&](hipStream_t s, std::string& e) { return imu_reintegrate_run(h->match, s, noise, bias, n_steps, steps, out, e); });
+    return match_call(h, nullptr, [&](hipStream_t s, std::string& e) { return imu_reintegrate_run(h->match, s, noise, bias, n_steps, steps, out, e); });
 }
 
 int orbfe_imu_predict(orbfe_handle* h, const orbfe_imu_predict_params* p, const float* state1, const orbfe_imu_preint* kf,
@@ -2827,9 +2709,9 @@ int orbfe_imu_predict(orbfe_handle* h, const orbfe_imu_predict_params* p, const 
     if (!p || !state1 || !kf || !state_out || !link_out || !info_ok) return ORBFE_ERR_INVALID_ARG;
     std::string err;
     const int crc = imu_check(nullptr, p, kf, frame, err);
-    if (crc != ORBFE_OK) return imu_refuse(h, crc, err);
+    if (crc != ORBFE_OK) return refuse(h, crc, err, kKeep);
     if (!h || (p->which == ORBFE_IMU_FROM_FRAME && !frame)) return ORBFE_ERR_INVALID_ARG;
-    return imu_call(h, nullptr, [&](hipStream_t s, std::string& e) { return imu_predict_run(h->match, s, p, state1, kf, frame, state_out, link_out, info_ok, e); });
+    return match_call(h, nullptr, [&](hipStream_t s, std::string& e) { return imu_predict_run(h->match, s, p, state1, kf, frame, state_out, link_out, info_ok, e); });
 }
 
 int orbfe_imu_frame_batch_device(orbfe_handle* h, const orbfe_imu_noise* noise, const orbfe_imu_predict_params* p, int batch,
@@ -2840,11 +2722,11 @@ int orbfe_imu_frame_batch_device(orbfe_handle* h, const orbfe_imu_noise* noise, 
     if (!noise || !p) return ORBFE_ERR_INVALID_ARG;
     std::string err;
     const int crc = imu_check(noise, p, nullptr, nullptr, err);
-    if (crc != ORBFE_OK) return imu_refuse(h, crc, err);
+    if (crc != ORBFE_OK) return refuse(h, crc, err, kKeep);
     if (imu_check_offsets(batch, sample_off) != ORBFE_OK) return ORBFE_ERR_INVALID_ARG;
     if (!h || !d_samples || !d_t_prev || !d_t_cur || !d_frame_bias || !d_state1 || !d_kf || !d_frame || !d_state_in || !d_links || !d_info_ok)
         return ORBFE_ERR_INVALID_ARG;
-    return imu_call(h, (hipStream_t)stream_, [&](hipStream_t s, std::string& e) {
+    return match_call(h, (hipStream_t)stream_, [&](hipStream_t s, std::string& e) {
         return imu_frame_batch_device(h->match, s, noise, p, batch, d_samples, sample_off, d_t_prev, d_t_cur, d_frame_bias, d_state1, d_kf, d_frame,
                                       d_steps_out, d_state_in, d_links, d_info_ok, e);
     });
@@ -2856,10 +2738,10 @@ int orbfe_imu_reintegrate_batch_device(orbfe_handle* h, const orbfe_imu_noise* n
     if (!noise) return ORBFE_ERR_INVALID_ARG;
     std::string err;
     const int crc = imu_check(noise, nullptr, nullptr, nullptr, err);
-    if (crc != ORBFE_OK) return imu_refuse(h, crc, err);
+    if (crc != ORBFE_OK) return refuse(h, crc, err, kKeep);
     if (imu_check_offsets(batch, step_off) != ORBFE_OK) return ORBFE_ERR_INVALID_ARG;
     if (!h || !d_steps || !d_bias || !d_out) return ORBFE_ERR_INVALID_ARG;
-    return imu_call(h, (hipStream_t)stream_, [&](hipStream_t s, std::string& e) {
+    return match_call(h, (hipStream_t)stream_, [&](hipStream_t s, std::string& e) {
         return imu_reintegrate_batch_device(h->match, s, noise, batch, d_steps, step_off, d_bias, d_out, e);
     });
 }
@@ -2878,7 +2760,7 @@ static int track_inertial_refuse(const orbfe_track_inertial_params* p, int batch
         return ORBFE_ERR_INVALID_ARG;
     }
     if (imu_check_offsets(batch, io->sample_off) != ORBFE_OK) return ORBFE_ERR_INVALID_ARG;
-    if (M < 0 || kp_stride < 1 || kp_stride > 65536 || !map) return ORBFE_ERR_INVALID_ARG;
+    if (M < 0 || kp_stride < 1 || kp_stride > kPoseMaxKp || !map) return ORBFE_ERR_INVALID_ARG;
     const bool fromFrame = p->predict.which == ORBFE_IMU_FROM_FRAME;
     if (!io->d_samples || !io->d_t_prev || !io->d_t_cur || !io->d_frame_bias || !io->d_state1 || !io->d_kf || !io->d_frame || !io->d_kp ||
         !io->d_desc || !io->d_n || !io->d_state_in || !io->d_info_ok || !io->d_match_out || !io->d_n_matches || !io->d_state_out ||
@@ -2893,10 +2775,10 @@ int orbfe_track_inertial_batch_device(orbfe_handle* h, const orbfe_track_inertia
 {
     std::string err;
     const int crc = track_inertial_refuse(p, batch, kp_stride, map, n_points, io, err);
-    if (crc != ORBFE_OK) return imu_refuse(h, crc, err);
+    if (crc != ORBFE_OK) return refuse(h, crc, err, kKeep);
     if (!h) return ORBFE_ERR_INVALID_ARG;
     if (map->h != h || p->frustum.n_levels > h->nLevels || n_points > (1 << 24)) return ORBFE_ERR_INVALID_ARG;
-    return imu_call(h, (hipStream_t)stream_, [&](hipStream_t s, std::string& e) {
+    return match_call(h, (hipStream_t)stream_, [&](hipStream_t s, std::string& e) {
         return track_inertial_batch_device(h->match, s, p, h->dSf, h->invSig2, h->nLevels, batch, kp_stride, map->cap, map->dPts, map->dDesc,
                                            n_points, io, nullptr, e);
     });
@@ -2916,7 +2798,7 @@ int orbfe_track_frame_inertial(orbfe_handle* h, const orbfe_track_inertial_param
         err = "orbfe_track_inertial_result.struct_size does not match this library (rebuild the caller against include/orbfe.h)";
         crc = ORBFE_ERR_INVALID_ARG;
     }
-    if (crc != ORBFE_OK) return imu_refuse(h, crc, err);
+    if (crc != ORBFE_OK) return refuse(h, crc, err, kKeep);
     const bool fromFrame = p->predict.which == ORBFE_IMU_FROM_FRAME;
     if (fromFrame && prior && prior->struct_size != (int)sizeof(orbfe_pose_imu_prior)) return ORBFE_ERR_INVALID_ARG;
     if (!gray || n_samples < 0 || (n_samples > 0 && !samples) || !frame_bias || !state1 || !kf || !frame || !map || M < 0 ||
@@ -2928,7 +2810,7 @@ int orbfe_track_frame_inertial(orbfe_handle* h, const orbfe_track_inertial_param
         return ORBFE_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
     const int cap = h->P.kpCapFrame, nL = h->nLevels;
-    if (cap > 65536) return ORBFE_ERR_UNSUPPORTED;  // the pose kernels' bound on kp_stride
+    if (cap > kPoseMaxKp) return ORBFE_ERR_UNSUPPORTED;  // the pose kernels' bound on kp_stride
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
 
@@ -2941,7 +2823,7 @@ int orbfe_track_frame_inertial(orbfe_handle* h, const orbfe_track_inertial_param
     size_t in = L.inFrame;
     const size_t iTimes = take256(in, 2 * sizeof(double));
     const size_t iBias = take256(in, 6 * sizeof(float));
-    const size_t iState1 = take256(in, 21 * sizeof(float));
+    const size_t iState1 = take256(in, kImuState * sizeof(float));
     const size_t iKf = take256(in, sizeof(orbfe_imu_preint));
     const size_t iFrame = take256(in, sizeof(orbfe_imu_preint));
     const size_t iPrior = take256(in, sizeof(orbfe_pose_imu_prior));
@@ -2951,12 +2833,12 @@ int orbfe_track_frame_inertial(orbfe_handle* h, const orbfe_track_inertial_param
     const size_t oKf = take256(out, sizeof(orbfe_imu_preint));
     const size_t oFrame = take256(out, sizeof(orbfe_imu_preint));
     const size_t oSteps = take256(out, (size_t)nS * sizeof(orbfe_imu_step));
-    const size_t oStateIn = take256(out, 33 * sizeof(float));
+    const size_t oStateIn = take256(out, kImuStateIn * sizeof(float));
     const size_t oLink = take256(out, linkBytes);
     const size_t oInts = take256(out, 8 * sizeof(int));  // info_ok, n_matches, n_inliers, accepted, matches_inliers, tracked
     const size_t oMps = take256(out, (size_t)Mp * sizeof(orbfe_map_point));
     const size_t oMatch = take256(out, (size_t)cap * sizeof(int));
-    const size_t oStateOut = take256(out, 21 * sizeof(float));
+    const size_t oStateOut = take256(out, kImuState * sizeof(float));
     const size_t oH = take256(out, hBytes);
     const size_t oHp = take256(out, 225 * sizeof(double));
     const size_t oOutlier = take256(out, (size_t)cap);
@@ -2977,7 +2859,7 @@ int orbfe_track_frame_inertial(orbfe_handle* h, const orbfe_track_inertial_param
     const double times[2] = {t_prev, t_cur};
     memcpy(hi + iTimes, times, sizeof times);
     memcpy(hi + iBias, frame_bias, 6 * sizeof(float));
-    memcpy(hi + iState1, state1, 21 * sizeof(float));
+    memcpy(hi + iState1, state1, kImuState * sizeof(float));
     memcpy(hi + iKf, kf, sizeof(orbfe_imu_preint));
     memcpy(hi + iFrame, frame, sizeof(orbfe_imu_preint));
     if (fromFrame) memcpy(hi + iPrior, prior, sizeof(orbfe_pose_imu_prior));
@@ -3056,7 +2938,7 @@ int orbfe_track_frame_inertial(orbfe_handle* h, const orbfe_track_inertial_param
     memcpy(frame, ho + oFrame, sizeof(orbfe_imu_preint));
     res->n_steps = nSteps;
     if (res->steps_out && nSteps) memcpy(res->steps_out, ho + oSteps, (size_t)nSteps * sizeof(orbfe_imu_step));
-    memcpy(res->state_in, ho + oStateIn, 33 * sizeof(float));
+    memcpy(res->state_in, ho + oStateIn, kImuStateIn * sizeof(float));
     if (res->link_out) memcpy(res->link_out, ho + oLink, linkBytes);
     const int* ints = reinterpret_cast<const int*>(ho + oInts);
     res->info_ok = ints[0];
@@ -3070,7 +2952,7 @@ int orbfe_track_frame_inertial(orbfe_handle* h, const orbfe_track_inertial_param
         memcpy(res->found, ho + oFound, (size_t)M);
     }
     memcpy(res->match_out, ho + oMatch, (size_t)n * sizeof(int));
-    memcpy(res->state_out, ho + oStateOut, 21 * sizeof(float));
+    memcpy(res->state_out, ho + oStateOut, kImuState * sizeof(float));
     memcpy(res->H_out, ho + oH, hBytes);
     if (io.d_Hprior_out) memcpy(res->Hprior_out, ho + oHp, 225 * sizeof(double));
     memcpy(res->outlier, ho + oOutlier, (size_t)n);
@@ -3099,13 +2981,10 @@ int orbfe_initial_bundle_adjustment(orbfe_handle* h, const orbfe_initial_ba_para
         return rc;
     }
     if (first.empty()) return ORBFE_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    MatchScope scope_(h, h->stream);
-    if (scope_.rc != ORBFE_OK) return scope_.rc;
-    rc = initial_ba_run_host(h->match, h->stream, p, h->invSig2, kp1, kp2, matches12, points, Rcw1, tcw1, Rcw2, tcw2, first, Tcw2_out,
-                             points_out, info, err);
-    if (rc != ORBFE_OK) h->err = err;
-    return rc;
+    return match_call_locked(h, nullptr, [&](hipStream_t s, std::string& e) {
+        return initial_ba_run_host(h->match, s, p, h->invSig2, kp1, kp2, matches12, points, Rcw1, tcw1, Rcw2, tcw2, first, Tcw2_out, points_out,
+                                   info, e);
+    });
 }
 
 int orbfe_triangulation_select(int n1, const int* raw_match12, const uint8_t* raw_bin, const uint8_t* has_mp1_now,
@@ -3145,14 +3024,9 @@ int orbfe_distinctive_descriptors(orbfe_handle* h, int n_sets, const int* set_of
     if (!h || n_sets < 0 || (n_sets > 0 && (!set_off || !best_idx_out || set_off[0] != 0)) ||
         (n_sets > 0 && set_off[n_sets] > 0 && !desc))
         return ORBFE_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    std::string err;
-    MatchScope scope_(h, h->stream);
-    if (scope_.rc != ORBFE_OK) return scope_.rc;
-    const int rc = distinctive_run(h->match, h->stream, n_sets, set_off, desc, best_idx_out, best_median_out, err);
-    if (rc != ORBFE_OK) h->err = err;
-    return rc;
+    return match_call(h, nullptr, [&](hipStream_t s, std::string& err) {
+        return distinctive_run(h->match, s, n_sets, set_off, desc, best_idx_out, best_median_out, err);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3363,15 +3237,10 @@ int orbfe_match_bow_rig(orbfe_handle* h, int G, const int* kf_off, const int* kf
     if (!h || !match_out || !n_matches || G < 0 || n_kf < 0 || n_f < 0 || n_left < -1 || n_left > n_f) return ORBFE_ERR_INVALID_ARG;
     if (G > 0 && (!kf_off || !kf_idx || !f_off || !f_idx || !kf_desc || !f_desc || !kf_has_mp)) return ORBFE_ERR_INVALID_ARG;
     if (check_orientation && G > 0 && (!kf_angle || !f_angle)) return ORBFE_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    std::string err;
-    MatchScope scope_(h, h->stream);
-    if (scope_.rc != ORBFE_OK) return scope_.rc;
-    int rc = match_bow_run(h->match, h->stream, G, kf_off, kf_idx, f_off, f_idx, n_kf, kf_desc, kf_angle, kf_has_mp, n_f,
-                           f_desc, f_angle, n_left, nn_ratio, check_orientation, match_out, n_matches, err);
-    if (rc != ORBFE_OK) h->err = err;
-    return rc;
+    return match_call(h, nullptr, [&](hipStream_t s, std::string& err) {
+        return match_bow_run(h->match, s, G, kf_off, kf_idx, f_off, f_idx, n_kf, kf_desc, kf_angle, kf_has_mp, n_f, f_desc, f_angle, n_left,
+                             nn_ratio, check_orientation, match_out, n_matches, err);
+    });
 }
 
 int orbfe_match_bow(orbfe_handle* h, int G, const int* kf_off, const int* kf_idx, const int* f_off, const int* f_idx,
