@@ -1464,6 +1464,119 @@ int orbfe_track_frame_inertial(orbfe_handle *h, const orbfe_track_inertial_param
                                int *per_level_counts, orbfe_track_inertial_result *res);
 
 /* -------------------------------------------------------------------------------------------
+ * Tracking::UpdateLocalMap from a resident covisibility graph (src/Tracking.cc:1119-1324; SPEC DECISION S24, DESIGN.md section 2;
+ * tests/local_map_ref.py is the normative restatement).  UpdateLocalKeyFrames (:1157-1324) followed by UpdateLocalPoints
+ * (:1129-1154) for a batch of independent frames: the output is the id list every per-frame chain takes as `ids` / `d_ids`.
+ * ---------------------------------------------------------------------------------------- */
+#define ORBFE_COVIS_MAX_COVISIBLE 16     /* ordered covisibles kept per key frame (the nodes ask for the best 5) */
+#define ORBFE_LOCAL_KF_MAX 288           /* 4 * 64 + 32: first phase + three appended per first-phase key frame + the temporal ones */
+#define ORBFE_NO_POINT 0x7fffffff        /* pad of an id row: outside every map and unchanged by ~, so every consumer reads "no point" */
+#define ORBFE_LOCAL_MAP_BLOCK 1024       /* threads of the points kernel's block: the walk is resolved in chunks of this many slots */
+#define ORBFE_LOCAL_MAP_VOTE_TABLE 512   /* distinct voted key frames the LDS vote table holds; above it, exact counters in HBM */
+
+typedef struct orbfe_covis orbfe_covis;
+
+/* The graph UpdateLocalMap walks, resident in HBM: per key frame slot in [0, kf_capacity) mnId, isBad(), the parent, mPrevKF, the
+ * map point of every feature slot (GetMapPointMatches), the ordered covisibles (the head of mvpOrderedConnectedKeyFrames) and the
+ * children in the caller's order; per point id of `map` (same ids, same capacity; the map's `bad` field is the points' isBad()) the
+ * key frames that observe it.  The caller's key-frame slots stand for the key frames: mn_id must differ between slots.
+ * A slot that was never set is a bad key frame with mn_id == slot, no features, no parent.
+ * Device memory, all taken at create: 4 * (kf_capacity * (8 + 16 + child_stride + kf_stride) + capacity * (1 + obs_stride)) bytes
+ * (10 000 key frames x 3000 slots: 120 MB).  Per-call scratch is kept with the graph and grows to the largest batch seen:
+ * 4 * batch * (capacity + kf_capacity) bytes; batch * capacity above 2^28 is refused with ORBFE_ERR_OUT_OF_MEMORY.
+ * kf_capacity in [1, 262144], kf_stride in [1, 2^20], obs_stride in [1, 4096], child_stride in [1, 4096].
+ * Lifetime: as orbfe_map's.  orbfe_covis_destroy waits for the handle's stream; orbfe_destroy releases the device memory of the graphs
+ * created from the handle, destroying them afterwards only frees the shell; destroying `map` first detaches it and every later call on
+ * the graph returns ORBFE_ERR_INVALID_ARG. */
+int orbfe_covis_create(orbfe_handle *h, const orbfe_map *map, int kf_capacity, int kf_stride, int obs_stride, int child_stride,
+                       orbfe_covis **out);
+void orbfe_covis_destroy(orbfe_covis *g);
+
+/* one key frame as orbfe_covis_set_keyframes takes it; HOST pointers; versioned by struct_size */
+typedef struct orbfe_covis_keyframe {
+    int struct_size;          /* sizeof(orbfe_covis_keyframe) at the caller's compile time */
+    int slot;                 /* [0, kf_capacity) */
+    int mn_id;                /* KeyFrame::mnId, >= 0 */
+    int bad;                  /* isBad() */
+    int parent;               /* GetParent(): slot or -1 */
+    int prev;                 /* mPrevKF: slot or -1 */
+    int n_features;           /* <= kf_stride; ignored when point_ids == NULL */
+    int n_covisible;          /* <= ORBFE_COVIS_MAX_COVISIBLE: the head of GetBestCovisibilityKeyFrames' list, bad ones included */
+    int n_children;           /* <= child_stride; S24: their order here is the order of the expansion */
+    int reserved;             /* 0 */
+    const int *point_ids;     /* n_features ids, < 0 or outside the map = no point; NULL keeps the stored list and its length */
+    const int *covisible;     /* n_covisible slots (or -1) */
+    const int *children;      /* n_children slots (or -1) */
+} orbfe_covis_keyframe;
+
+/* Writes n key frames: one staged block, one upload, one scatter launch on the handle's stream, i.e. behind everything submitted
+ * before on that stream; returns when the tables are updated.  This is where the mapping thread's changes reach the graph (the
+ * mbMapUpdated moment).  Everything is validated on the host before the device is touched and nothing is written on a
+ * refusal: ORBFE_ERR_INVALID_ARG for a wrong struct_size, a slot outside [0, kf_capacity) or named twice, mn_id < 0, a count above its
+ * stride, a covisible / child / parent / prev slot outside [-1, kf_capacity), a missing list. */
+int orbfe_covis_set_keyframes(orbfe_handle *h, orbfe_covis *g, int n, const orbfe_covis_keyframe *recs);
+/* Sets the observation lists (MapPoint::GetObservations, key-frame slots) of n points in CSR form: point ids[i] is observed by
+ * kf_slots[off[i] .. off[i + 1]); an empty range clears.  Ordering and validation as above: ORBFE_ERR_INVALID_ARG for an id outside the
+ * map or named twice, descending offsets, a range longer than obs_stride, a slot outside [0, kf_capacity).  HOST pointers. */
+int orbfe_covis_set_observations(orbfe_handle *h, orbfe_covis *g, int n, const int *ids, const int *off, const int *kf_slots);
+
+typedef struct orbfe_local_map_params {
+    int struct_size;          /* sizeof(orbfe_local_map_params) at the caller's compile time */
+    int max_local_kf;         /* mMaxLocalKFCount, 1..64 (the nodes pass 10 / 15) */
+    int n_covisible;          /* mCovisibilityKeyFrameNd, 0..ORBFE_COVIS_MAX_COVISIBLE (5) */
+    int n_temporal;           /* mTemporalKeyFrameNd, 0..32 (10) */
+    int inertial;             /* != 0: the temporal key frames of :1298-1314 are appended */
+    int mark_voters_seen;     /* != 0: a point that voted is emitted as ~id (:1040-1056, the frame's own points are already matched) */
+} orbfe_local_map_params;
+#define ORBFE_LOCAL_MAP_PARAMS_INIT {(int)sizeof(orbfe_local_map_params), 10, 5, 10, 1, 0}
+
+/* The pointers of orbfe_update_local_map_batch_device: DEVICE pointers.  Versioned by struct_size.  B = batch, M = n_points. */
+typedef struct orbfe_local_map_io {
+    int struct_size;          /* sizeof(orbfe_local_map_io) at the caller's compile time */
+    int reserved;             /* 0 */
+    const int *d_vote_ids;    /* B x vote_stride: the point id at every keypoint of the frame whose matches vote (the current frame
+                               * before IMU initialisation, the last frame after it, :1164 / :1188); outside the map = no point */
+    const int *d_n_votes;     /* B: keypoints of that frame (clamped to [0, vote_stride]) */
+    const int *d_last_kf;     /* B: mCurrentFrame->mpLastKeyFrame as a slot, outside [0, kf_capacity) = none; read when inertial != 0 */
+    int *d_ids_out;           /* B x M: the local map points in mvpLocalMapPoints order, then ORBFE_NO_POINT */
+    int *d_n_local_points;    /* B: the true count, also when it exceeds M (nothing is written past slot M) */
+    int *d_local_kfs;         /* B x ORBFE_LOCAL_KF_MAX: mvpLocalKeyFrames as slots, then -1 */
+    int *d_n_local_kfs;       /* B */
+    int *d_vote_ids_out;      /* B x vote_stride, may be NULL, may be d_vote_ids: entry i < n_votes is the input, or -1 where the
+                               * point is bad (:1181, :1207); entries from n_votes on are not written */
+} orbfe_local_map_io;
+
+/* S24 for `batch` independent frames against one graph.  Per frame: every non-bad voter adds one to each key frame that observes it
+ * (a point at two keypoints votes twice); the key frames are ranked by count descending, equal counts in ascending mn_id (S24 pins the
+ * order std::sort leaves open); the first min(max_local_kf, voted) are taken, a bad one is skipped but uses its place; then, over
+ * those in order: the first of the best n_covisible covisibles that is not bad and not yet listed, the first such child, and the
+ * parent when not yet listed -- with no bad test, and ending the expansion (:1292); with `inertial`, last_kf and its mPrevKF chain
+ * while they are new, at most n_temporal (:1303-1313, a listed one stops the chain as written).  The points: the list in REVERSE, every
+ * feature slot ascending, first occurrence of a point that is not bad.
+ * Asynchronous on `stream` (NULL == the handle's): four launches of a block per frame, back to back, no host synchronisation, no allocation unless
+ * `batch` exceeds every earlier call's.  Results do not depend on `batch` or on the order the votes arrive in.  d_ids_out is laid out
+ * as orbfe_track_inertial_batch_device and orbfe_match_projection_batch_device read d_ids.
+ * ORBFE_ERR_INVALID_ARG: a wrong struct_size, a required NULL, batch < 1, n_points < 1, vote_stride < 1, a parameter outside its range,
+ * a graph of another handle or whose map is gone; all decided before the device is touched.  ORBFE_ERR_OUT_OF_MEMORY: see above. */
+int orbfe_update_local_map_batch_device(orbfe_handle *h, const orbfe_local_map_params *p, int batch, int vote_stride,
+                                        orbfe_covis *covis, int n_points, const orbfe_local_map_io *io, void *stream);
+/* The same for ONE frame from HOST pointers: one upload, the same launch, one download, one synchronisation.  n_votes >= 0 (vote_ids
+ * may be NULL when it is 0); last_kf as d_last_kf; ids_out n_points ints, local_kfs ORBFE_LOCAL_KF_MAX ints; vote_ids_out n_votes ints
+ * or NULL.  Results equal the batch call's with batch == 1. */
+int orbfe_update_local_map(orbfe_handle *h, const orbfe_local_map_params *p, int n_votes, const int *vote_ids, int last_kf,
+                           orbfe_covis *covis, int n_points, int *ids_out, int *n_local_points, int *local_kfs, int *n_local_kfs,
+                           int *vote_ids_out);
+
+/* The frame's mvpMapPoints as Track() leaves them behind TrackLocalMap (src/Tracking.cc:504-533), from what
+ * orbfe_track_inertial_batch_device left in HBM: d_out[b][i] (B x kp_stride) = the id d_ids[b][d_match[b][i]] when keypoint i < d_n[b]
+ * has a match inside [0, n_points), that id is inside the map, its Observations() >= 1 (:508) and d_outlier[b][i] == 0 (:531); -1
+ * otherwise and for i >= d_n[b].  A thread per keypoint; asynchronous on `stream`.  With it frame k's results become frame k + 1's
+ * id list without leaving HBM: this call -> orbfe_update_local_map_batch_device -> d_ids.
+ * ORBFE_ERR_INVALID_ARG: a NULL, batch < 1, kp_stride < 1, n_points < 1, a map of another handle. */
+int orbfe_frame_points_batch_device(orbfe_handle *h, const orbfe_map *map, int batch, int kp_stride, int n_points, const int *d_ids,
+                                    const int *d_match, const uint8_t *d_outlier, const int *d_n, int *d_out, void *stream);
+
+/* -------------------------------------------------------------------------------------------
  * Bundle adjustment of the initial map: the line behind orbfe_two_view_reconstruct (src/Tracking.cc:698)
  * ---------------------------------------------------------------------------------------- */
 /* the camera and the constants of Optimizer::GlobalBundleAdjustemnt(map, 20) (src/Optimizer.cc:60-369); versioned by struct_size */

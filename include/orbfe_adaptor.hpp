@@ -642,6 +642,134 @@ private:
     orbfe_map* m_ = nullptr;
 };
 
+// The graph Tracking::UpdateLocalMap walks (src/Tracking.cc:1119-1324), resident in HBM over the ids of a ResidentMap (orbfe_covis,
+// SPEC DECISION S24).  A key frame is named by a slot in [0, kfCapacity) and a map point by its id in the map; both come from the
+// caller's lookups, as ResidentMap's ids do: slotOf(pKF) -> slot or -1 (not resident), idOf(pMP) -> id or -1.  The lookups are
+// called with non-null pointers only.  `KF` needs mnId, isBad(), GetParent(), mPrevKF, GetMapPointMatches(),
+// GetBestCovisibilityKeyFrames(N) and GetChilds(); `MP` needs GetObservations() (a map keyed by the key frame).
+// When to call: INTEGRATION.md, "UpdateLocalMap on the device" -- at the moment Tracking sees mbMapUpdated, for the key frames and
+// points the mapping thread touched since the last frame.
+class ResidentCovisibility {
+public:
+    ResidentCovisibility(orbfe_handle* h, const ResidentMap& map, int kfCapacity, int kfStride, int obsStride, int childStride) : h_(h)
+    {
+        orbfe_detail::check(orbfe_covis_create(h, map.get(), kfCapacity, kfStride, obsStride, childStride, &g_), h, "orbfe_covis_create");
+    }
+    ~ResidentCovisibility() { orbfe_covis_destroy(g_); }
+    ResidentCovisibility(const ResidentCovisibility&) = delete;
+    ResidentCovisibility& operator=(const ResidentCovisibility&) = delete;
+
+    // withFeatures == false leaves the stored feature lists alone (a key frame whose flags or links changed, not its matches).
+    // The children are listed in ascending mnId: GetChilds() is ordered by address, which S24 does not follow.
+    template <class KFPtr, class SlotOf, class IdOf>
+    void UpdateKeyFrames(const std::vector<KFPtr>& vpKFs, SlotOf slotOf, IdOf idOf, bool withFeatures = true)
+    {
+        const size_t n = vpKFs.size();
+        std::vector<orbfe_covis_keyframe> recs(n > 0 ? n : 1);
+        std::vector<std::vector<int>> pts(n), cov(n), kids(n);
+        for (size_t i = 0; i < n; i++) {
+            const auto& pKF = vpKFs[i];
+            const auto slot_or_none = [&](const auto& p) { return p ? slotOf(p) : -1; };
+            if (withFeatures)
+                for (const auto& pMP : pKF->GetMapPointMatches()) pts[i].push_back(pMP ? idOf(pMP) : -1);
+            for (const auto& pN : pKF->GetBestCovisibilityKeyFrames(ORBFE_COVIS_MAX_COVISIBLE)) cov[i].push_back(slot_or_none(pN));
+            std::vector<std::pair<long long, int>> byId;
+            for (const auto& pC : pKF->GetChilds())
+                if (pC) byId.emplace_back((long long)pC->mnId, slotOf(pC));
+            std::sort(byId.begin(), byId.end());
+            for (const auto& c : byId) kids[i].push_back(c.second);
+            orbfe_covis_keyframe r{};
+            r.struct_size = (int)sizeof r;
+            r.slot = slotOf(pKF);
+            r.mn_id = (int)pKF->mnId;
+            r.bad = pKF->isBad() ? 1 : 0;
+            r.parent = slot_or_none(pKF->GetParent());
+            r.prev = slot_or_none(pKF->mPrevKF);
+            r.n_features = (int)pts[i].size();
+            r.n_covisible = (int)cov[i].size();
+            r.n_children = (int)kids[i].size();
+            static const int none = -1;
+            r.point_ids = withFeatures ? (pts[i].empty() ? &none : pts[i].data()) : nullptr;
+            r.covisible = cov[i].data();
+            r.children = kids[i].data();
+            recs[i] = r;
+        }
+        orbfe_detail::check(orbfe_covis_set_keyframes(h_, g_, (int)n, recs.data()), h_, "orbfe_covis_set_keyframes");
+    }
+
+    // GetObservations() of every point of the list; an observing key frame that is not resident is left out
+    template <class MPPtr, class IdOf, class SlotOf>
+    void UpdateObservations(const std::vector<MPPtr>& vpMPs, IdOf idOf, SlotOf slotOf)
+    {
+        std::vector<int> ids, off(1, 0), slots;
+        for (const auto& pMP : vpMPs) {
+            ids.push_back(idOf(pMP));
+            for (const auto& ob : pMP->GetObservations()) {
+                const int s = ob.first ? slotOf(ob.first) : -1;
+                if (s >= 0) slots.push_back(s);
+            }
+            off.push_back((int)slots.size());
+        }
+        orbfe_detail::check(orbfe_covis_set_observations(h_, g_, (int)ids.size(), ids.data(), off.data(), slots.data()), h_,
+                            "orbfe_covis_set_observations");
+    }
+    orbfe_covis* get() const { return g_; }
+
+private:
+    orbfe_handle* h_;
+    orbfe_covis* g_ = nullptr;
+};
+
+// Tracking::UpdateLocalMap (src/Tracking.cc:1119-1324) on the device, one frame from host pointers (orbfe_update_local_map).  What the
+// caller still does itself: mpReferenceKF is not chosen here (the reference's own choice is commented out, :1316-1320), and
+// SetReferenceMapPoints (:1126) is the viewer's.
+class LocalMapUpdater {
+public:
+    LocalMapUpdater(orbfe_handle* h, ResidentCovisibility& graph, int maxPoints, int maxLocalKFCount = 10, int covisibilityKeyFrameNd = 5,
+                    int temporalKeyFrameNd = 10)
+        : h_(h), g_(graph), ids_((size_t)(maxPoints > 0 ? maxPoints : 1))
+    {
+        p_ = orbfe_local_map_params{(int)sizeof(orbfe_local_map_params), maxLocalKFCount, covisibilityKeyFrameNd, temporalKeyFrameNd, 0, 0};
+    }
+
+    // vpVoters: the mvpMapPoints of the frame whose matches vote -- mCurrentFrame's before the IMU is initialised (markVotersSeen =
+    // true: its own points come back as ~id, "seen in this frame"), mLastFrame's after; bad ones are set to null as the reference does
+    // (:1181, :1207).  pLastKF: mCurrentFrame->mpLastKeyFrame or null.  kfOfSlot / mpOfId: the inverses of the lookups.
+    // -> mvpLocalKeyFrames, mvpLocalMapPoints; Ids() is the row the per-frame chains take as `ids` (LocalPointCount() of it are set).
+    template <class MPPtr, class KFPtr, class IdOf, class SlotOf, class KfOfSlot, class MpOfId>
+    void Update(std::vector<MPPtr>& vpVoters, const KFPtr& pLastKF, bool inertial, bool markVotersSeen, IdOf idOf, SlotOf slotOf,
+                KfOfSlot kfOfSlot, MpOfId mpOfId, std::vector<KFPtr>& vpLocalKeyFrames, std::vector<MPPtr>& vpLocalMapPoints)
+    {
+        const int n = (int)vpVoters.size();
+        votes_.assign((size_t)(n > 0 ? n : 1), -1);
+        for (int i = 0; i < n; i++)
+            if (vpVoters[i]) votes_[i] = idOf(vpVoters[i]);
+        p_.inertial = inertial ? 1 : 0;
+        p_.mark_voters_seen = markVotersSeen ? 1 : 0;
+        int kfs[ORBFE_LOCAL_KF_MAX], nKfs = 0;
+        votesOut_.resize(votes_.size());
+        orbfe_detail::check(orbfe_update_local_map(h_, &p_, n, votes_.data(), pLastKF ? slotOf(pLastKF) : -1, g_.get(), (int)ids_.size(),
+                                                   ids_.data(), &nPoints_, kfs, &nKfs, votesOut_.data()),
+                            h_, "orbfe_update_local_map");
+        for (int i = 0; i < n; i++)
+            if (vpVoters[i] && votesOut_[i] < 0) vpVoters[i] = MPPtr();
+        vpLocalKeyFrames.clear();
+        for (int i = 0; i < nKfs; i++) vpLocalKeyFrames.push_back(kfOfSlot(kfs[i]));
+        vpLocalMapPoints.clear();
+        const int m = nPoints_ < (int)ids_.size() ? nPoints_ : (int)ids_.size();
+        for (int i = 0; i < m; i++) vpLocalMapPoints.push_back(mpOfId(ids_[i] < 0 ? ~ids_[i] : ids_[i]));
+    }
+    const std::vector<int>& Ids() const { return ids_; }
+    int LocalPointCount() const { return nPoints_; }   // the true count: above Ids().size() the row was cut
+
+private:
+    orbfe_handle* h_;
+    ResidentCovisibility& g_;
+    orbfe_local_map_params p_{};
+    std::vector<int> ids_, votes_, votesOut_;
+    int nPoints_ = 0;
+};
+
 // The batched many-frame mode over several GPUs (orbfe_pool_*): member k is an extractor on devices[k] with a ring of
 // slots x slotFrames; the frames of a call are sharded in contiguous blocks (orbfe_shard_range) and the members run at the
 // same time.  Outputs are frame-major with the stride Cap(): frame i at kp[i*Cap()], desc[i*Cap()*32], n[i],

@@ -25,6 +25,7 @@
 #include "match_common.h"
 #include "match_proj.h"
 #include "keyframe.h"
+#include "local_map.h"
 #include "marginalize.h"
 #include "poseimu_math.h"
 #include "prep.h"
@@ -79,6 +80,7 @@ struct GraphCache {
 
 struct orbfe_map;
 struct orbfe_stream;
+struct orbfe_covis;
 
 struct orbfe_handle {
     orbfe_params prm{};
@@ -194,6 +196,7 @@ struct orbfe_handle {
     // that destroying them afterwards -- a binding's finalisers run in any order -- only frees the empty shell
     std::vector<orbfe_map*> maps;
     std::vector<orbfe_stream*> rings;
+    std::vector<orbfe_covis*> covis;
 
     // Cross-stream ordering of the scratch the handle owns: an event recorded behind the last enqueue that used the
     // extraction scratch (pyramid, candidates, counters, level keypoints) / the matcher arena, and the stream it ran on.
@@ -1100,6 +1103,41 @@ struct orbfe_map {  // map points resident in HBM (orbfe_map_*, further down)
     uint8_t* dDesc = nullptr;
 };
 
+struct orbfe_covis {  // the covisibility graph resident in HBM (orbfe_covis_*, SPEC DECISION S24, further down)
+    orbfe_handle* h = nullptr;
+    const orbfe_map* map = nullptr;  // null once the map is destroyed: every later call is refused
+    CovisTables T{};
+    // per-call scratch, kept here because it has to be found as it was left: first-occurrence stamps [scratchBatch][cap] at rest,
+    // vote counters [scratchBatch][kfCap + 1] at zero
+    unsigned* dStamps = nullptr;
+    int* dCounters = nullptr;
+    int scratchBatch = 0;
+};
+
+// the caller holds h->mu (or is the handle's destruction); the handle's stream is idle
+static void covis_free(orbfe_covis* g)
+{
+    void* ptrs[] = {g->T.kf, g->T.covisible, g->T.children, g->T.kfPoints, g->T.obsCount, g->T.obs, g->dStamps, g->dCounters};
+    for (void* p : ptrs)
+        if (p) (void)hipFree(p);
+    g->T.kf = nullptr;
+    g->T.covisible = g->T.children = g->T.kfPoints = g->T.obsCount = g->T.obs = nullptr;
+    g->dStamps = nullptr;
+    g->dCounters = nullptr;
+    g->scratchBatch = 0;
+}
+static void covis_orphan(orbfe_covis* g)
+{
+    covis_free(g);
+    g->h = nullptr;
+    g->map = nullptr;
+}
+static void covis_detach_map(orbfe_handle* h, const orbfe_map* m)
+{
+    for (orbfe_covis* g : h->covis)
+        if (g->map == m) g->map = nullptr;
+}
+
 namespace {
 
 // map points per graph: rounded up so that a local map that grows by a few points replays the same graph; the padding
@@ -1891,6 +1929,7 @@ static void map_release(orbfe_map* m)
             st->map = nullptr;
             st->maxPoints = 0;
         }
+    covis_detach_map(h, m);  // a graph over this map's ids: its later calls are refused
     if (m->dPts) (void)hipFree(m->dPts);
     if (m->dDesc) (void)hipFree(m->dDesc);
     m->dPts = nullptr;
@@ -1959,6 +1998,8 @@ void orphan_children(orbfe_handle* h)
         st->h = nullptr;
     }
     h->rings.clear();
+    for (orbfe_covis* g : h->covis) covis_orphan(g);
+    h->covis.clear();
     for (orbfe_map* m : h->maps) {
         map_release(m);
         m->h = nullptr;
@@ -2743,6 +2784,309 @@ int orbfe_imu_reintegrate_batch_device(orbfe_handle* h, const orbfe_imu_noise* n
     if (!h || !d_steps || !d_bias || !d_out) return ORBFE_ERR_INVALID_ARG;
     return match_call(h, (hipStream_t)stream_, [&](hipStream_t s, std::string& e) {
         return imu_reintegrate_batch_device(h->match, s, noise, batch, d_steps, step_off, d_bias, d_out, e);
+    });
+}
+
+// ---- Tracking::UpdateLocalMap from a resident covisibility graph (SPEC DECISION S24) ----
+
+int orbfe_covis_create(orbfe_handle* h, const orbfe_map* map, int kf_capacity, int kf_stride, int obs_stride, int child_stride,
+                       orbfe_covis** out)
+{
+    if (!h || !out || !map || map->h != h || kf_capacity < 1 || kf_capacity > kCovisMaxKf || kf_stride < 1 || kf_stride > kCovisMaxKfStride ||
+        obs_stride < 1 || obs_stride > kCovisMaxShort || child_stride < 1 || child_stride > kCovisMaxShort)
+        return ORBFE_ERR_INVALID_ARG;
+    *out = nullptr;
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIPCHK(h, hipSetDevice(h->device));
+    orbfe_covis* g = new (std::nothrow) orbfe_covis();
+    if (!g) return ORBFE_ERR_OUT_OF_MEMORY;
+    g->h = h;
+    g->map = map;
+    CovisTables& T = g->T;
+    T.kfCap = kf_capacity;
+    T.kfStride = kf_stride;
+    T.obsStride = obs_stride;
+    T.childStride = child_stride;
+    T.cap = map->cap;
+    const size_t K = (size_t)kf_capacity, C = (size_t)map->cap;
+    if (hipMalloc(&T.kf, K * sizeof(CovisKf)) != hipSuccess || hipMalloc(&T.covisible, K * ORBFE_COVIS_MAX_COVISIBLE * sizeof(int)) != hipSuccess ||
+        hipMalloc(&T.children, K * child_stride * sizeof(int)) != hipSuccess || hipMalloc(&T.kfPoints, K * kf_stride * sizeof(int)) != hipSuccess ||
+        hipMalloc(&T.obsCount, C * sizeof(int)) != hipSuccess || hipMalloc(&T.obs, C * obs_stride * sizeof(int)) != hipSuccess) {
+        (void)hipGetLastError();
+        covis_free(g);
+        delete g;
+        h->err = "orbfe_covis_create: allocation failed";
+        return ORBFE_ERR_OUT_OF_MEMORY;
+    }
+    std::string err;
+    int rc = covis_init_launch(h->stream, T, err);
+    if (rc == ORBFE_OK && hipStreamSynchronize(h->stream) != hipSuccess) {
+        err = "orbfe_covis_create: hipStreamSynchronize failed";
+        rc = ORBFE_ERR_HIP;
+    }
+    if (rc != ORBFE_OK) {
+        (void)hipGetLastError();
+        covis_free(g);
+        delete g;
+        h->err = err;
+        return rc;
+    }
+    h->covis.push_back(g);
+    *out = g;
+    return ORBFE_OK;
+}
+
+void orbfe_covis_destroy(orbfe_covis* g)
+{
+    if (!g) return;
+    if (g->h) {  // (null: the handle went first, orphan_children)
+        orbfe_handle* h = g->h;
+        std::lock_guard<std::mutex> lk(h->mu);
+        for (size_t i = 0; i < h->covis.size(); i++)
+            if (h->covis[i] == g) h->covis.erase(h->covis.begin() + (long)i--);
+        (void)hipSetDevice(h->device);
+        (void)hipStreamSynchronize(h->stream);
+        if (h->matchUsed) (void)hipEventSynchronize(h->evMatch);  // a call on another stream
+        covis_free(g);
+    }
+    delete g;
+}
+
+}  // extern "C"
+
+// one staged block up, run(device block), synchronised: what the two setters share; the caller holds nothing
+template <class Fill, class Run>
+static int covis_staged_call(orbfe_handle* h, size_t bytes, Fill fill, Run run)
+{
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIPCHK(h, hipSetDevice(h->device));
+    std::string err;
+    MatchScope scope_(h, h->stream);
+    if (scope_.rc != ORBFE_OK) return scope_.rc;
+    int rc = ensure(h->match, bytes, bytes, err);
+    if (rc != ORBFE_OK) {
+        h->err = err;
+        return rc;
+    }
+    fill(static_cast<int*>(h->match.hpin));
+    HIPCHK(h, hipMemcpyAsync(h->match.d, h->match.hpin, bytes, hipMemcpyHostToDevice, h->stream));
+    rc = run(static_cast<const int*>(h->match.d), err);
+    if (rc != ORBFE_OK) {
+        h->err = err;
+        return rc;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return ORBFE_OK;
+}
+
+extern "C" {
+
+int orbfe_covis_set_keyframes(orbfe_handle* h, orbfe_covis* g, int n, const orbfe_covis_keyframe* recs)
+{
+    if (!h || !g || g->h != h || !g->map || n < 0 || (n > 0 && !recs)) return ORBFE_ERR_INVALID_ARG;
+    const CovisTables& T = g->T;
+    auto slot_or_none = [&](int s) { return s >= -1 && s < T.kfCap; };
+    std::vector<char> seen((size_t)T.kfCap, 0);
+    size_t ints = (size_t)n * (sizeof(CovisStagedKf) / sizeof(int));
+    for (int i = 0; i < n; i++) {
+        const orbfe_covis_keyframe& r = recs[i];
+        if (r.struct_size != (int)sizeof(orbfe_covis_keyframe)) {
+            std::lock_guard<std::mutex> lk(h->mu);
+            h->err = "orbfe_covis_keyframe.struct_size does not match this library (rebuild the caller against include/orbfe.h)";
+            return ORBFE_ERR_INVALID_ARG;
+        }
+        if (r.slot < 0 || r.slot >= T.kfCap || seen[(size_t)r.slot] || r.mn_id < 0 || !slot_or_none(r.parent) || !slot_or_none(r.prev) ||
+            r.n_covisible < 0 || r.n_covisible > ORBFE_COVIS_MAX_COVISIBLE || r.n_children < 0 || r.n_children > T.childStride ||
+            (r.n_covisible > 0 && !r.covisible) || (r.n_children > 0 && !r.children) ||
+            (r.point_ids && (r.n_features < 0 || r.n_features > T.kfStride)))
+            return ORBFE_ERR_INVALID_ARG;
+        seen[(size_t)r.slot] = 1;
+        for (int j = 0; j < r.n_covisible; j++)
+            if (!slot_or_none(r.covisible[j])) return ORBFE_ERR_INVALID_ARG;
+        for (int j = 0; j < r.n_children; j++)
+            if (!slot_or_none(r.children[j])) return ORBFE_ERR_INVALID_ARG;
+        ints += (size_t)(r.point_ids ? r.n_features : 0) + (size_t)r.n_covisible + (size_t)r.n_children;
+    }
+    if (n == 0) return ORBFE_OK;
+    if (ints > (size_t)0x7fffffff) return ORBFE_ERR_INVALID_ARG;  // offsets are ints: split the call
+    return covis_staged_call(
+        h, ints * sizeof(int),
+        [&](int* blk) {
+            CovisStagedKf* st = reinterpret_cast<CovisStagedKf*>(blk);
+            size_t at = (size_t)n * (sizeof(CovisStagedKf) / sizeof(int));
+            for (int i = 0; i < n; i++) {
+                const orbfe_covis_keyframe& r = recs[i];
+                const int nf = r.point_ids ? r.n_features : -1;
+                st[i] = CovisStagedKf{r.slot, r.mn_id, r.bad != 0, r.parent, r.prev, nf, r.n_covisible, r.n_children, 0, 0, 0, 0};
+                st[i].oPoints = (int)at;
+                if (nf > 0) memcpy(blk + at, r.point_ids, (size_t)nf * sizeof(int));
+                at += (size_t)std::max(nf, 0);
+                st[i].oCovisible = (int)at;
+                if (r.n_covisible > 0) memcpy(blk + at, r.covisible, (size_t)r.n_covisible * sizeof(int));
+                at += (size_t)r.n_covisible;
+                st[i].oChildren = (int)at;
+                if (r.n_children > 0) memcpy(blk + at, r.children, (size_t)r.n_children * sizeof(int));
+                at += (size_t)r.n_children;
+            }
+        },
+        [&](const int* dBlk, std::string& err) { return covis_scatter_keyframes_launch(h->stream, T, n, dBlk, err); });
+}
+
+int orbfe_covis_set_observations(orbfe_handle* h, orbfe_covis* g, int n, const int* ids, const int* off, const int* kf_slots)
+{
+    if (!h || !g || g->h != h || !g->map || n < 0 || (n > 0 && (!ids || !off))) return ORBFE_ERR_INVALID_ARG;
+    if (n == 0) return ORBFE_OK;
+    const CovisTables& T = g->T;
+    if (off[0] < 0) return ORBFE_ERR_INVALID_ARG;
+    for (int i = 0; i < n; i++)
+        if (ids[i] < 0 || ids[i] >= T.cap || off[i + 1] < off[i] || off[i + 1] - off[i] > T.obsStride) return ORBFE_ERR_INVALID_ARG;
+    {
+        std::vector<int> sorted(ids, ids + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return ORBFE_ERR_INVALID_ARG;
+    }
+    const int total = off[n];
+    if (total > off[0] && !kf_slots) return ORBFE_ERR_INVALID_ARG;
+    for (int k = off[0]; k < total; k++)
+        if (kf_slots[k] < 0 || kf_slots[k] >= T.kfCap) return ORBFE_ERR_INVALID_ARG;
+    Carver c;
+    const size_t oIds = c.take((size_t)n * sizeof(int));
+    const size_t oOff = c.take((size_t)(n + 1) * sizeof(int));
+    const size_t oSlots = c.take((size_t)std::max(total, 1) * sizeof(int));
+    return covis_staged_call(
+        h, c.off,
+        [&](int* blk) {
+            memcpy(blk + oIds / sizeof(int), ids, (size_t)n * sizeof(int));
+            memcpy(blk + oOff / sizeof(int), off, (size_t)(n + 1) * sizeof(int));
+            if (total > 0) memcpy(blk + oSlots / sizeof(int), kf_slots, (size_t)total * sizeof(int));
+        },
+        [&](const int* dBlk, std::string& err) {
+            return covis_scatter_observations_launch(h->stream, T, n, dBlk + oIds / sizeof(int), dBlk + oOff / sizeof(int),
+                                                     dBlk + oSlots / sizeof(int), err);
+        });
+}
+
+// what the arguments alone decide, for both per-frame calls: no handle is looked at
+static int local_map_refuse(const orbfe_local_map_params* p, int batch, int vote_stride, const orbfe_covis* g, int M, std::string& err)
+{
+    if (!p) return ORBFE_ERR_INVALID_ARG;
+    const int crc = local_map_check(p, err);
+    if (crc != ORBFE_OK) return crc;
+    if (batch < 1 || vote_stride < 1 || M < 1 || !g) return ORBFE_ERR_INVALID_ARG;
+    return ORBFE_OK;
+}
+
+// the scratch for `batch` frames, left at rest; the caller holds h->mu.  Grows only: a call allocates when its batch is the largest so far.
+static int covis_scratch(orbfe_handle* h, orbfe_covis* g, int batch, hipStream_t s, std::string& err)
+{
+    if (batch <= g->scratchBatch) return ORBFE_OK;
+    const size_t stamps = (size_t)batch * g->T.cap, counters = (size_t)batch * ((size_t)g->T.kfCap + 1);
+    if (stamps > kCovisMaxStamps) {
+        err = "orbfe_update_local_map: batch x map capacity exceeds the 2^28 first-occurrence stamps of one call";
+        return ORBFE_ERR_OUT_OF_MEMORY;
+    }
+    // the blocks in use may still be read by a call in flight on another stream: hipFree waits for the device
+    if (g->dStamps) (void)hipFree(g->dStamps);
+    if (g->dCounters) (void)hipFree(g->dCounters);
+    g->dStamps = nullptr;
+    g->dCounters = nullptr;
+    g->scratchBatch = 0;
+    if (hipMalloc(&g->dStamps, stamps * sizeof(unsigned)) != hipSuccess || hipMalloc(&g->dCounters, counters * sizeof(int)) != hipSuccess) {
+        (void)hipGetLastError();
+        if (g->dStamps) (void)hipFree(g->dStamps);
+        g->dStamps = nullptr;
+        err = "orbfe_update_local_map: allocation of the per-frame scratch failed";
+        return ORBFE_ERR_OUT_OF_MEMORY;
+    }
+    MCHK(hipMemsetAsync(g->dStamps, 0xff, stamps * sizeof(unsigned), s));
+    MCHK(hipMemsetAsync(g->dCounters, 0, counters * sizeof(int), s));
+    g->scratchBatch = batch;
+    return ORBFE_OK;
+}
+
+int orbfe_update_local_map_batch_device(orbfe_handle* h, const orbfe_local_map_params* p, int batch, int vote_stride, orbfe_covis* g,
+                                        int n_points, const orbfe_local_map_io* io, void* stream_)
+{
+    std::string err;
+    int crc = local_map_refuse(p, batch, vote_stride, g, n_points, err);
+    if (crc == ORBFE_OK && !io) crc = ORBFE_ERR_INVALID_ARG;
+    if (crc == ORBFE_OK && io->struct_size != (int)sizeof(orbfe_local_map_io)) {
+        err = "orbfe_local_map_io.struct_size does not match this library (rebuild the caller against include/orbfe.h)";
+        crc = ORBFE_ERR_INVALID_ARG;
+    }
+    if (crc != ORBFE_OK) return refuse(h, crc, err, kKeep);
+    if (!io->d_vote_ids || !io->d_n_votes || (p->inertial != 0 && !io->d_last_kf) || !io->d_ids_out || !io->d_n_local_points ||
+        !io->d_local_kfs || !io->d_n_local_kfs)
+        return ORBFE_ERR_INVALID_ARG;
+    if (!h || g->h != h || !g->map) return ORBFE_ERR_INVALID_ARG;
+    return match_call(h, (hipStream_t)stream_, [&](hipStream_t s, std::string& e) -> int {
+        const int rc = covis_scratch(h, g, batch, s, e);
+        if (rc != ORBFE_OK) return rc;
+        return local_map_launch(s, p, batch, vote_stride, g->T, g->map->dPts, n_points, io, g->dStamps, g->dCounters, e);
+    });
+}
+
+int orbfe_update_local_map(orbfe_handle* h, const orbfe_local_map_params* p, int n_votes, const int* vote_ids, int last_kf, orbfe_covis* g,
+                           int n_points, int* ids_out, int* n_local_points, int* local_kfs, int* n_local_kfs, int* vote_ids_out)
+{
+    std::string err;
+    const int crc = local_map_refuse(p, 1, 1, g, n_points, err);
+    if (crc != ORBFE_OK) return refuse(h, crc, err, kKeep);
+    if (n_votes < 0 || (n_votes > 0 && !vote_ids) || !ids_out || !n_local_points || !local_kfs || !n_local_kfs) return ORBFE_ERR_INVALID_ARG;
+    if (!h || g->h != h || !g->map) return ORBFE_ERR_INVALID_ARG;
+    const int stride = std::max(n_votes, 1), M = n_points;
+    // in:  [vote ids | n_votes, last_kf]      out: [ids (M) | n_local_points, n_local_kfs | local_kfs | vote ids out]
+    Carver c;
+    const size_t oVotes = c.take((size_t)stride * sizeof(int));
+    const size_t oScal = c.take(2 * sizeof(int));
+    const size_t inBytes = c.off;
+    const size_t oIds = c.take((size_t)M * sizeof(int));
+    const size_t oCounts = c.take(2 * sizeof(int));
+    const size_t oKfs = c.take((size_t)ORBFE_LOCAL_KF_MAX * sizeof(int));
+    const size_t oVotesOut = c.take((size_t)stride * sizeof(int));
+    return match_call(h, nullptr, [&](hipStream_t s, std::string& e) -> int {
+        int rc = ensure(h->match, c.off, c.off, e);
+        if (rc != ORBFE_OK) return rc;
+        rc = covis_scratch(h, g, 1, s, e);
+        if (rc != ORBFE_OK) return rc;
+        uint8_t* hp = static_cast<uint8_t*>(h->match.hpin);
+        uint8_t* dp = static_cast<uint8_t*>(h->match.d);
+        if (n_votes > 0) memcpy(hp + oVotes, vote_ids, (size_t)n_votes * sizeof(int));
+        const int scal[2] = {n_votes, last_kf};
+        memcpy(hp + oScal, scal, sizeof scal);
+        auto& err = e;
+        MCHK(hipMemcpyAsync(dp, hp, inBytes, hipMemcpyHostToDevice, s));
+        orbfe_local_map_io io{};
+        io.struct_size = (int)sizeof io;
+        io.d_vote_ids = reinterpret_cast<const int*>(dp + oVotes);
+        io.d_n_votes = reinterpret_cast<const int*>(dp + oScal);
+        io.d_last_kf = io.d_n_votes + 1;
+        io.d_ids_out = reinterpret_cast<int*>(dp + oIds);
+        io.d_n_local_points = reinterpret_cast<int*>(dp + oCounts);
+        io.d_n_local_kfs = io.d_n_local_points + 1;
+        io.d_local_kfs = reinterpret_cast<int*>(dp + oKfs);
+        io.d_vote_ids_out = reinterpret_cast<int*>(dp + oVotesOut);
+        rc = local_map_launch(s, p, 1, stride, g->T, g->map->dPts, M, &io, g->dStamps, g->dCounters, e);
+        if (rc != ORBFE_OK) return rc;
+        MCHK(hipMemcpyAsync(hp + oIds, dp + oIds, c.off - oIds, hipMemcpyDeviceToHost, s));
+        MCHK(hipStreamSynchronize(s));
+        memcpy(ids_out, hp + oIds, (size_t)M * sizeof(int));
+        *n_local_points = reinterpret_cast<const int*>(hp + oCounts)[0];
+        *n_local_kfs = reinterpret_cast<const int*>(hp + oCounts)[1];
+        memcpy(local_kfs, hp + oKfs, (size_t)ORBFE_LOCAL_KF_MAX * sizeof(int));
+        if (vote_ids_out && n_votes > 0) memcpy(vote_ids_out, hp + oVotesOut, (size_t)n_votes * sizeof(int));
+        return ORBFE_OK;
+    });
+}
+
+int orbfe_frame_points_batch_device(orbfe_handle* h, const orbfe_map* map, int batch, int kp_stride, int n_points, const int* d_ids,
+                                    const int* d_match, const uint8_t* d_outlier, const int* d_n, int* d_out, void* stream_)
+{
+    if (!map || batch < 1 || kp_stride < 1 || kp_stride > kPoseMaxKp || n_points < 1 || !d_ids || !d_match || !d_outlier || !d_n || !d_out)
+        return ORBFE_ERR_INVALID_ARG;
+    if (!h || map->h != h) return ORBFE_ERR_INVALID_ARG;
+    return match_call(h, (hipStream_t)stream_, [&](hipStream_t s, std::string& e) {
+        return frame_points_launch(s, batch, kp_stride, n_points, map->cap, map->dPts, d_ids, d_match, d_outlier, d_n, d_out, e);
     });
 }
 

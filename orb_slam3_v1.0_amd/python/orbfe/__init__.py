@@ -440,6 +440,48 @@ class TrackInertialResult(C.Structure):
         self.struct_size = C.sizeof(TrackInertialResult)
 
 
+# SPEC DECISION S24 (include/orbfe.h): the figures the tests need are mirrored here, and checked against the header by tests/test_local_map_abi.py
+COVIS_MAX_COVISIBLE = 16
+LOCAL_KF_MAX = 288
+NO_POINT = 0x7fffffff
+LOCAL_MAP_BLOCK = 1024       # threads of the points kernel's block: the chunk of the points walk
+LOCAL_MAP_VOTE_TABLE = 512   # distinct voted key frames the LDS table holds before the call counts in HBM
+
+
+class CovisKeyframe(C.Structure):
+    """orbfe_covis_keyframe: one key frame as orbfe_covis_set_keyframes takes it (HOST pointers)."""
+    _fields_ = [("struct_size", C.c_int), ("slot", C.c_int), ("mn_id", C.c_int), ("bad", C.c_int), ("parent", C.c_int), ("prev", C.c_int),
+                ("n_features", C.c_int), ("n_covisible", C.c_int), ("n_children", C.c_int), ("reserved", C.c_int),
+                ("point_ids", C.c_void_p), ("covisible", C.c_void_p), ("children", C.c_void_p)]
+
+    def __init__(self, **k):
+        super().__init__(**k)
+        self.struct_size = C.sizeof(CovisKeyframe)
+
+
+class LocalMapParams(C.Structure):
+    """orbfe_local_map_params: mMaxLocalKFCount, mCovisibilityKeyFrameNd, mTemporalKeyFrameNd, the sensor kind and whether the voters are
+    the current frame's own points (SPEC DECISION S24)."""
+    _fields_ = [("struct_size", C.c_int), ("max_local_kf", C.c_int), ("n_covisible", C.c_int), ("n_temporal", C.c_int),
+                ("inertial", C.c_int), ("mark_voters_seen", C.c_int)]
+
+    def __init__(self, max_local_kf=10, n_covisible=5, n_temporal=10, inertial=1, mark_voters_seen=0):
+        super().__init__(C.sizeof(LocalMapParams), int(max_local_kf), int(n_covisible), int(n_temporal), int(inertial), int(mark_voters_seen))
+
+
+LOCAL_MAP_IO_FIELDS = ("d_vote_ids", "d_n_votes", "d_last_kf", "d_ids_out", "d_n_local_points", "d_local_kfs", "d_n_local_kfs",
+                       "d_vote_ids_out")
+
+
+class LocalMapIO(C.Structure):
+    """orbfe_local_map_io: the device pointers of orbfe_update_local_map_batch_device (as ints)."""
+    _fields_ = [("struct_size", C.c_int), ("reserved", C.c_int)] + [(k, C.c_void_p) for k in LOCAL_MAP_IO_FIELDS]
+
+    def __init__(self, **k):
+        super().__init__(**k)
+        self.struct_size = C.sizeof(LocalMapIO)
+
+
 class FrameView(C.Structure):
     _fields_ = [("n", C.c_int), ("kp", C.c_void_p), ("desc", C.c_void_p), ("grid_cols", C.c_int),
                 ("grid_rows", C.c_int), ("min_x", C.c_float), ("min_y", C.c_float),
@@ -471,6 +513,8 @@ SYMBOLS = [
     "orbfe_imu_preintegrate_frame", "orbfe_imu_reintegrate", "orbfe_imu_predict", "orbfe_imu_frame_batch_device",
     "orbfe_imu_reintegrate_batch_device",
     "orbfe_track_inertial_batch_device", "orbfe_track_frame_inertial",
+    "orbfe_covis_create", "orbfe_covis_destroy", "orbfe_covis_set_keyframes", "orbfe_covis_set_observations",
+    "orbfe_update_local_map_batch_device", "orbfe_update_local_map", "orbfe_frame_points_batch_device",
     "orbfe_shard_range", "orbfe_pool_create", "orbfe_pool_destroy", "orbfe_pool_size", "orbfe_pool_member",
     "orbfe_pool_member_frames", "orbfe_pool_last_error", "orbfe_pool_extract", "orbfe_pool_enable_track",
     "orbfe_pool_map_update", "orbfe_pool_track",
@@ -624,6 +668,15 @@ def lib():
         L.orbfe_track_frame_inertial.argtypes = [vp, C.POINTER(TrackInertialParams), vp, ci, ci, vp, C.c_double, C.c_double, vp, vp,
                                                  C.POINTER(ImuPreint), C.POINTER(ImuPreint), vp, ci, vp, C.POINTER(PoseImuPrior), vp, vp,
                                                  C.POINTER(ci), vp, C.POINTER(TrackInertialResult)]
+    if hasattr(L, "orbfe_update_local_map_batch_device"):  # (as above)
+        L.orbfe_covis_create.argtypes = [vp, vp, ci, ci, ci, ci, C.POINTER(vp)]
+        L.orbfe_covis_destroy.argtypes = [vp]
+        L.orbfe_covis_destroy.restype = None
+        L.orbfe_covis_set_keyframes.argtypes = [vp, vp, ci, vp]
+        L.orbfe_covis_set_observations.argtypes = [vp, vp, ci, vp, vp, vp]
+        L.orbfe_update_local_map_batch_device.argtypes = [vp, C.POINTER(LocalMapParams), ci, ci, vp, ci, C.POINTER(LocalMapIO), vp]
+        L.orbfe_update_local_map.argtypes = [vp, C.POINTER(LocalMapParams), ci, vp, ci, vp, ci, vp, C.POINTER(ci), vp, C.POINTER(ci), vp]
+        L.orbfe_frame_points_batch_device.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "orbfe_initial_bundle_adjustment"):  # (as above)
         L.orbfe_initial_bundle_adjustment.argtypes = [vp, C.POINTER(InitialBAParams), ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                                       C.POINTER(InitialBAInfo)]
@@ -840,6 +893,48 @@ class MapPoints:
     def close(self):
         if getattr(self, "h", None):
             self.L.orbfe_map_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+
+class Covisibility:
+    """orbfe_covis: the graph Tracking::UpdateLocalMap walks, resident in HBM over the ids of one MapPoints (SPEC DECISION S24)."""
+
+    def __init__(self, extractor, map_points, kf_capacity, kf_stride, obs_stride, child_stride):
+        self.e, self.L, self.map = extractor, extractor.L, map_points
+        self.kf_capacity, self.kf_stride, self.obs_stride, self.child_stride = int(kf_capacity), int(kf_stride), int(obs_stride), int(child_stride)
+        self.h = C.c_void_p()
+        extractor._chk(self.L.orbfe_covis_create(extractor.h, map_points.h, self.kf_capacity, self.kf_stride, self.obs_stride,
+                                                 self.child_stride, C.byref(self.h)), "orbfe_covis_create")
+
+    def set_keyframes(self, recs):
+        """recs: dicts with slot, mn_id, bad, parent, prev, covisible, children and point_ids (None keeps the stored feature list)"""
+        arr = (CovisKeyframe * max(len(recs), 1))()
+        keep = []
+        for r, k in zip(arr, recs):
+            lists = {}
+            for name in ("point_ids", "covisible", "children"):
+                v = k.get(name)
+                lists[name] = None if v is None else np.ascontiguousarray(v, np.int32)
+            keep.append(lists)
+            pts, cov, ch = lists["point_ids"], lists["covisible"], lists["children"]
+            r.__init__(slot=int(k["slot"]), mn_id=int(k["mn_id"]), bad=int(k.get("bad", 0)), parent=int(k.get("parent", -1)),
+                       prev=int(k.get("prev", -1)), n_features=0 if pts is None else len(pts), n_covisible=0 if cov is None else len(cov),
+                       n_children=0 if ch is None else len(ch), point_ids=None if pts is None else pts.ctypes.data,
+                       covisible=None if cov is None or not len(cov) else cov.ctypes.data,
+                       children=None if ch is None or not len(ch) else ch.ctypes.data)
+        self.e._chk(self.L.orbfe_covis_set_keyframes(self.e.h, self.h, len(recs), C.cast(arr, C.c_void_p)), "orbfe_covis_set_keyframes")
+
+    def set_observations(self, ids, off, kf_slots):
+        ids, off, kf_slots = (np.ascontiguousarray(a, np.int32) for a in (ids, off, kf_slots))
+        assert len(off) == len(ids) + 1
+        self.e._chk(self.L.orbfe_covis_set_observations(self.e.h, self.h, len(ids), _p(ids), _p(off), _p(kf_slots) if len(kf_slots) else None),
+                    "orbfe_covis_set_observations")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.orbfe_covis_destroy(self.h)
             self.h = None
 
     __del__ = close
@@ -1756,6 +1851,33 @@ def track_inertial_batch_device(extractor, params, batch, kp_stride, map_points,
     extractor._chk(extractor.L.orbfe_track_inertial_batch_device(extractor.h, C.byref(params), int(batch), int(kp_stride),
                                                                  map_points.h if map_points is not None else None, int(n_points),
                                                                  C.byref(io), stream), "orbfe_track_inertial_batch_device")
+
+
+def update_local_map_batch_device(extractor, params, batch, vote_stride, covis, n_points, io, stream=None):
+    """orbfe_update_local_map_batch_device: Tracking::UpdateLocalMap for `batch` independent frames against the resident graph (SPEC
+    DECISION S24); io: a LocalMapIO of raw device pointers.  d_ids_out is what the per-frame chains read as d_ids."""
+    extractor._chk(extractor.L.orbfe_update_local_map_batch_device(extractor.h, C.byref(params), int(batch), int(vote_stride),
+                                                                   covis.h if covis is not None else None, int(n_points), C.byref(io),
+                                                                   stream), "orbfe_update_local_map_batch_device")
+
+
+def update_local_map(extractor, params, vote_ids, last_kf, covis, n_points):
+    """orbfe_update_local_map: one frame from host arrays -> dict(ids, n_local_points, local_kfs, n_local_kfs, vote_ids)"""
+    votes = np.ascontiguousarray(vote_ids, np.int32)
+    ids, kfs, votes_out = np.empty(int(n_points), np.int32), np.empty(LOCAL_KF_MAX, np.int32), np.empty(len(votes), np.int32)
+    n_pts, n_kfs = C.c_int(), C.c_int()
+    extractor._chk(extractor.L.orbfe_update_local_map(extractor.h, C.byref(params), len(votes), _p(votes) if len(votes) else None, int(last_kf),
+                                                      covis.h, int(n_points), _p(ids), C.byref(n_pts), _p(kfs), C.byref(n_kfs),
+                                                      _p(votes_out) if len(votes) else None), "orbfe_update_local_map")
+    return dict(ids=ids, n_local_points=n_pts.value, local_kfs=kfs, n_local_kfs=n_kfs.value, vote_ids=votes_out)
+
+
+def frame_points_batch_device(extractor, map_points, batch, kp_stride, n_points, d_ids_ptr, d_match_ptr, d_outlier_ptr, d_n_ptr, d_out_ptr,
+                              stream=None):
+    """orbfe_frame_points_batch_device: the frames' mvpMapPoints as Track() leaves them, from what the inertial chain left in HBM"""
+    extractor._chk(extractor.L.orbfe_frame_points_batch_device(extractor.h, map_points.h, int(batch), int(kp_stride), int(n_points), d_ids_ptr,
+                                                               d_match_ptr, d_outlier_ptr, d_n_ptr, d_out_ptr, stream),
+                   "orbfe_frame_points_batch_device")
 
 
 def track_inertial_io(sample_off, **ptrs):
