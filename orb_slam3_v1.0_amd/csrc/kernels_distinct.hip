@@ -56,29 +56,24 @@ int distinctive_run(MatchScratch& m, hipStream_t s, int nSets, const int* setOff
         if (bestMedian) bestMedian[q] = 0;
     }
     if (nRows == 0) return ORBFE_OK;
-    Carver in;
-    const size_t oOff = in.take((size_t)(nSets + 1) * sizeof(int));
-    const size_t oRowSet = in.take((size_t)nRows * sizeof(int));
-    const size_t oDesc = in.take((size_t)nRows * 32);
-    const size_t oBest = in.take((size_t)nSets * sizeof(unsigned int));
-    const size_t inBytes = in.off;
-    int rc = ensure(m, inBytes, inBytes + (size_t)nSets * sizeof(unsigned int) + 256, err);
+    Staging st;
+    const auto bOff = st.in<int>((size_t)nSets + 1);
+    const auto bRowSet = st.in<int>(nRows);
+    const auto bDesc = st.in<uint8_t>((size_t)nRows * 32);
+    const auto bBest = st.inout<unsigned int>(nSets);   // goes up as "none", comes down as the packed minimum
+    int rc = reserve(m, st, err);
     if (rc != ORBFE_OK) return rc;
-    uint8_t* hp = static_cast<uint8_t*>(m.hpin);
-    uint8_t* dp = static_cast<uint8_t*>(m.d);
-    memcpy(hp + oOff, setOff, (size_t)(nSets + 1) * sizeof(int));
-    int* rowSet = reinterpret_cast<int*>(hp + oRowSet);
+    st.put(bOff, setOff);
+    int* rowSet = st.host(bRowSet);
     for (int q = 0; q < nSets; q++)
         for (int r = setOff[q]; r < setOff[q + 1]; r++) rowSet[r] = q;
-    memcpy(hp + oDesc, desc, (size_t)nRows * 32);
-    memset(hp + oBest, 0xff, (size_t)nSets * sizeof(unsigned int));
-    MCHK(hipMemcpyAsync(dp, hp, inBytes, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(distinct_kernel, dim3((nRows + 255) / 256), dim3(256), 0, s, nRows, reinterpret_cast<const int*>(dp + oRowSet),
-                       reinterpret_cast<const int*>(dp + oOff), dp + oDesc, reinterpret_cast<unsigned int*>(dp + oBest));
-    MCHK(hipGetLastError());
-    unsigned int* hBest = reinterpret_cast<unsigned int*>(hp + inBytes);
-    MCHK(hipMemcpyAsync(hBest, dp + oBest, (size_t)nSets * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
-    MCHK(hipStreamSynchronize(s));
+    st.put(bDesc, desc);
+    memset(st.host(bBest), 0xff, bBest.bytes());
+    if ((rc = upload(st, s, err)) != ORBFE_OK) return rc;
+    hipLaunchKernelGGL(distinct_kernel, dim3((nRows + 255) / 256), dim3(256), 0, s, nRows, st.dev(bRowSet), st.dev(bOff), st.dev(bDesc),
+                       st.dev(bBest));
+    if ((rc = download_span(st, s, bBest.off, bBest.end(), err)) != ORBFE_OK) return rc;
+    const unsigned int* hBest = st.res(bBest);
     for (int q = 0; q < nSets; q++)
         if (setOff[q + 1] > setOff[q]) {
             bestIdx[q] = (int)(hBest[q] & 0xFFFFFu);

@@ -238,123 +238,106 @@ int imu_preintegrate_run(MatchScratch& m, hipStream_t s, const orbfe_imu_noise* 
                          int* nSteps, std::string& err)
 {
     // up: [samples | tPrev, tCur | bias | off | kf]; down: [kf | frame | steps | nSteps]
-    Carver c;
-    const size_t oSamples = c.take((size_t)n * sizeof(orbfe_imu_sample));
-    const size_t oTimes = c.take(2 * sizeof(double));
-    const size_t oBias = c.take(6 * sizeof(float));
-    const size_t oOff = c.take(2 * sizeof(int));
-    const size_t oKf = c.take(sizeof(orbfe_imu_preint));
-    const size_t inBytes = c.off;
-    const size_t oFrame = c.take(sizeof(orbfe_imu_preint));
-    const size_t oSteps = c.take((size_t)(n - 1) * sizeof(orbfe_imu_step));
-    const size_t oN = c.take(sizeof(int));
-    const size_t resBytes = c.off - oKf;
-    int rc = ensure(m, c.off + 256, c.off + 256, err);
+    Staging st;
+    const auto bSamples = st.in<orbfe_imu_sample>(n);
+    const auto bTimes = st.in<double>(2);
+    const auto bBias = st.in<float>(6);
+    const auto bOff = st.in<int>(2);
+    const auto bKf = st.inout<orbfe_imu_preint>(1);
+    const auto bFrame = st.out<orbfe_imu_preint>(1);
+    const auto bSteps = st.out<orbfe_imu_step>((size_t)(n - 1));
+    const auto bN = st.out<int>(1);
+    int rc = reserve(m, st, err);
     if (rc != ORBFE_OK) return rc;
-    uint8_t* hp = static_cast<uint8_t*>(m.hpin);
-    uint8_t* dp = static_cast<uint8_t*>(m.d);
-    memcpy(hp + oSamples, samples, (size_t)n * sizeof(orbfe_imu_sample));
+    st.put(bSamples, samples);
     const double times[2] = {tPrev, tCur};
-    memcpy(hp + oTimes, times, sizeof times);
-    memcpy(hp + oBias, frameBias, 6 * sizeof(float));
+    st.put(bTimes, times);
+    st.put(bBias, frameBias);
     const int off[2] = {0, n};
-    memcpy(hp + oOff, off, sizeof off);
-    memcpy(hp + oKf, kf, sizeof(orbfe_imu_preint));
-    MCHK(hipMemcpyAsync(dp, hp, inBytes, hipMemcpyHostToDevice, s));
+    st.put(bOff, off);
+    st.put(bKf, kf);
+    if ((rc = upload(st, s, err)) != ORBFE_OK) return rc;
     ImuArgs G;
     memset(&G, 0, sizeof G);
     fill_noise(noise, G.cov, G.walk);
     G.doPreint = 1;
-    G.samples = reinterpret_cast<const orbfe_imu_sample*>(dp + oSamples);
-    G.off = reinterpret_cast<const int*>(dp + oOff);
-    G.tPrev = reinterpret_cast<const double*>(dp + oTimes);
+    G.samples = st.dev(bSamples);
+    G.off = st.dev(bOff);
+    G.tPrev = st.dev(bTimes);
     G.tCur = G.tPrev + 1;
-    G.frameBias = reinterpret_cast<const float*>(dp + oBias);
-    G.kf = reinterpret_cast<orbfe_imu_preint*>(dp + oKf);
-    G.frame = reinterpret_cast<orbfe_imu_preint*>(dp + oFrame);
-    G.stepsOut = reinterpret_cast<orbfe_imu_step*>(dp + oSteps);
-    G.nStepsOut = reinterpret_cast<int*>(dp + oN);
+    G.frameBias = st.dev(bBias);
+    G.kf = st.dev(bKf);
+    G.frame = st.dev(bFrame);
+    G.stepsOut = st.dev(bSteps);
+    G.nStepsOut = st.dev(bN);
     hipLaunchKernelGGL(imu_frame_kernel, dim3(1), dim3(kImuThreads), 0, s, G);
-    MCHK(hipGetLastError());
-    MCHK(hipMemcpyAsync(hp + oKf, dp + oKf, resBytes, hipMemcpyDeviceToHost, s));
-    MCHK(hipStreamSynchronize(s));
-    memcpy(kf, hp + oKf, sizeof(orbfe_imu_preint));
-    memcpy(frame, hp + oFrame, sizeof(orbfe_imu_preint));
-    if (stepsOut) memcpy(stepsOut, hp + oSteps, (size_t)(n - 1) * sizeof(orbfe_imu_step));
-    *nSteps = *reinterpret_cast<const int*>(hp + oN);
+    if ((rc = download(st, s, err)) != ORBFE_OK) return rc;
+    st.get(bKf, kf);
+    st.get(bFrame, frame);
+    st.get(bSteps, stepsOut);
+    *nSteps = *st.res(bN);
     return ORBFE_OK;
 }
 
 int imu_reintegrate_run(MatchScratch& m, hipStream_t s, const orbfe_imu_noise* noise, const float* bias, int n, const orbfe_imu_step* steps,
                         orbfe_imu_preint* out, std::string& err)
 {
-    Carver c;
-    const size_t oSteps = c.take((size_t)n * sizeof(orbfe_imu_step));
-    const size_t oBias = c.take(6 * sizeof(float));
-    const size_t oOff = c.take(2 * sizeof(int));
-    const size_t inBytes = c.off;
-    const size_t oOut = c.take(sizeof(orbfe_imu_preint));
-    int rc = ensure(m, c.off + 256, c.off + 256, err);
+    Staging st;
+    const auto bSteps = st.in<orbfe_imu_step>(n);
+    const auto bBias = st.in<float>(6);
+    const auto bOff = st.in<int>(2);
+    const auto bOut = st.out<orbfe_imu_preint>(1);
+    int rc = reserve(m, st, err);
     if (rc != ORBFE_OK) return rc;
-    uint8_t* hp = static_cast<uint8_t*>(m.hpin);
-    uint8_t* dp = static_cast<uint8_t*>(m.d);
-    if (n > 0) memcpy(hp + oSteps, steps, (size_t)n * sizeof(orbfe_imu_step));
-    memcpy(hp + oBias, bias, 6 * sizeof(float));
+    if (n > 0) st.put(bSteps, steps);
+    st.put(bBias, bias);
     const int off[2] = {0, n};
-    memcpy(hp + oOff, off, sizeof off);
-    MCHK(hipMemcpyAsync(dp, hp, inBytes, hipMemcpyHostToDevice, s));
+    st.put(bOff, off);
+    if ((rc = upload(st, s, err)) != ORBFE_OK) return rc;
     ReintArgs G;
     memset(&G, 0, sizeof G);
     fill_noise(noise, G.cov, G.walk);
-    G.steps = reinterpret_cast<const orbfe_imu_step*>(dp + oSteps);
-    G.off = reinterpret_cast<const int*>(dp + oOff);
-    G.bias = reinterpret_cast<const float*>(dp + oBias);
-    G.out = reinterpret_cast<orbfe_imu_preint*>(dp + oOut);
+    G.steps = st.dev(bSteps);
+    G.off = st.dev(bOff);
+    G.bias = st.dev(bBias);
+    G.out = st.dev(bOut);
     hipLaunchKernelGGL(imu_reintegrate_kernel, dim3(1), dim3(kImuThreads), 0, s, G);
-    MCHK(hipGetLastError());
-    MCHK(hipMemcpyAsync(hp + oOut, dp + oOut, sizeof(orbfe_imu_preint), hipMemcpyDeviceToHost, s));
-    MCHK(hipStreamSynchronize(s));
-    memcpy(out, hp + oOut, sizeof(orbfe_imu_preint));
+    if ((rc = download_span(st, s, bOut.off, bOut.end(), err)) != ORBFE_OK) return rc;
+    st.get(bOut, out);
     return ORBFE_OK;
 }
 
 int imu_predict_run(MatchScratch& m, hipStream_t s, const orbfe_imu_predict_params* P, const float* state1, const orbfe_imu_preint* kf,
                     const orbfe_imu_preint* frame, float* stateOut, void* linkOut, int* infoOk, std::string& err)
 {
-    Carver c;
-    const size_t oState1 = c.take(kImuState1 * sizeof(float));
-    const size_t oKf = c.take(sizeof(orbfe_imu_preint));
-    const size_t oFrame = c.take(sizeof(orbfe_imu_preint));
-    const size_t inBytes = c.off;
-    const size_t oState = c.take(kImuStateIn * sizeof(float));
-    const size_t oLink = c.take(link_bytes(P->which));
-    const size_t oOk = c.take(sizeof(int));
-    const size_t resBytes = c.off - oState;
-    int rc = ensure(m, c.off + 256, c.off + 256, err);
+    Staging st;
+    const auto bState1 = st.in<float>(kImuState1);
+    const auto bKf = st.in<orbfe_imu_preint>(1);
+    const auto bFrame = st.in<orbfe_imu_preint>(1);
+    const auto bState = st.out<float>(kImuStateIn);
+    const auto bLink = st.out<uint8_t>(link_bytes(P->which));
+    const auto bOk = st.out<int>(1);
+    int rc = reserve(m, st, err);
     if (rc != ORBFE_OK) return rc;
-    uint8_t* hp = static_cast<uint8_t*>(m.hpin);
-    uint8_t* dp = static_cast<uint8_t*>(m.d);
-    memcpy(hp + oState1, state1, kImuState1 * sizeof(float));
-    memcpy(hp + oKf, kf, sizeof(orbfe_imu_preint));
-    if (frame) memcpy(hp + oFrame, frame, sizeof(orbfe_imu_preint));
-    else memset(hp + oFrame, 0, sizeof(orbfe_imu_preint));
-    MCHK(hipMemcpyAsync(dp, hp, inBytes, hipMemcpyHostToDevice, s));
+    st.put(bState1, state1);
+    st.put(bKf, kf);
+    if (frame) st.put(bFrame, frame);
+    else memset(st.host(bFrame), 0, sizeof(orbfe_imu_preint));
+    if ((rc = upload(st, s, err)) != ORBFE_OK) return rc;
     ImuArgs G;
     memset(&G, 0, sizeof G);
     fill_predict(G, P);
-    G.state1 = reinterpret_cast<const float*>(dp + oState1);
-    G.kf = reinterpret_cast<orbfe_imu_preint*>(dp + oKf);
-    G.frame = reinterpret_cast<orbfe_imu_preint*>(dp + oFrame);
-    G.stateIn = reinterpret_cast<float*>(dp + oState);
-    G.links = dp + oLink;
-    G.infoOk = reinterpret_cast<int*>(dp + oOk);
+    G.state1 = st.dev(bState1);
+    G.kf = st.dev(bKf);
+    G.frame = st.dev(bFrame);
+    G.stateIn = st.dev(bState);
+    G.links = st.dev(bLink);
+    G.infoOk = st.dev(bOk);
     hipLaunchKernelGGL(imu_frame_kernel, dim3(1), dim3(kImuThreads), 0, s, G);
-    MCHK(hipGetLastError());
-    MCHK(hipMemcpyAsync(hp + oState, dp + oState, resBytes, hipMemcpyDeviceToHost, s));
-    MCHK(hipStreamSynchronize(s));
-    memcpy(stateOut, hp + oState, kImuStateIn * sizeof(float));
-    memcpy(linkOut, hp + oLink, link_bytes(P->which));
-    *infoOk = *reinterpret_cast<const int*>(hp + oOk);
+    if ((rc = download(st, s, err)) != ORBFE_OK) return rc;
+    st.get(bState, stateOut);
+    st.get(bLink, linkOut);
+    *infoOk = *st.res(bOk);
     return ORBFE_OK;
 }
 

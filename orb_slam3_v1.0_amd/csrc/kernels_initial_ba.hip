@@ -435,22 +435,18 @@ int initial_ba_run_host(MatchScratch& m, hipStream_t s, const orbfe_initial_ba_p
     const bool parked = Pw > kBaRegisterP;
 
     // up: [obs | x0]; device only: [park]; down: [info | xOut | chi2 | front]
-    Carver c;
-    const size_t oObs = c.take((size_t)N * 6 * sizeof(float));
-    const size_t oX0 = c.take((size_t)N * 3 * sizeof(float));
-    const size_t inBytes = c.off;
-    const size_t oPark = c.take(parked ? (size_t)kBaState * Pw * sizeof(double) : 0);
-    const size_t oInfo = c.take(sizeof(BaDeviceInfo));
-    const size_t oXOut = c.take((size_t)N * 3 * sizeof(float));
-    const size_t oChi2 = c.take((size_t)2 * N * sizeof(double));
-    const size_t oFront = c.take((size_t)2 * N);
-    const size_t resBytes = c.off - oInfo;
-    int rc = ensure(m, c.off, inBytes + resBytes + 256, err);
+    Staging st;
+    const auto bObs = st.in<float>((size_t)N * 6);
+    const auto bX0 = st.in<float>((size_t)N * 3);
+    const auto bPark = st.scratch<double>(parked ? (size_t)kBaState * Pw : 0);
+    const auto bInfo = st.out<BaDeviceInfo>(1);
+    const auto bXOut = st.out<float>((size_t)N * 3);
+    const auto bChi2 = st.out<double>((size_t)2 * N);
+    const auto bFront = st.out<uint8_t>((size_t)2 * N);
+    int rc = reserve(m, st, err);
     if (rc != ORBFE_OK) return rc;
-    uint8_t* hp = static_cast<uint8_t*>(m.hpin);
-    uint8_t* dp = static_cast<uint8_t*>(m.d);
-    float* hObs = reinterpret_cast<float*>(hp + oObs);
-    float* hX0 = reinterpret_cast<float*>(hp + oX0);
+    float* hObs = st.host(bObs);
+    float* hX0 = st.host(bX0);
     for (int p = 0; p < N; p++) {
         const int i = first[(size_t)p];
         const orbfe_keypoint& a = kp1[i];
@@ -464,20 +460,20 @@ int initial_ba_run_host(MatchScratch& m, hipStream_t s, const orbfe_initial_ba_p
         o[5] = invLevelSigma2[b.octave];
         for (int k = 0; k < 3; k++) hX0[3 * (size_t)p + k] = points[3 * (size_t)i + k];
     }
-    MCHK(hipMemcpyAsync(dp, hp, inBytes, hipMemcpyHostToDevice, s));
-    MCHK(hipMemsetAsync(dp + oInfo, 0, sizeof(BaDeviceInfo), s));
+    if ((rc = upload(st, s, err)) != ORBFE_OK) return rc;
+    MCHK(hipMemsetAsync(st.dev(bInfo), 0, sizeof(BaDeviceInfo), s));
 
     BaArgs G;
     memset(&G, 0, sizeof G);
     G.N = N;
     G.P = Pw;
-    G.obs = reinterpret_cast<const float*>(dp + oObs);
-    G.x0 = reinterpret_cast<const float*>(dp + oX0);
-    G.park = parked ? reinterpret_cast<double*>(dp + oPark) : nullptr;
-    G.xOut = reinterpret_cast<float*>(dp + oXOut);
-    G.chi2 = reinterpret_cast<double*>(dp + oChi2);
-    G.front = dp + oFront;
-    G.info = reinterpret_cast<BaDeviceInfo*>(dp + oInfo);
+    G.obs = st.dev(bObs);
+    G.x0 = st.dev(bX0);
+    G.park = parked ? st.dev(bPark) : nullptr;
+    G.xOut = st.dev(bXOut);
+    G.chi2 = st.dev(bChi2);
+    G.front = st.dev(bFront);
+    G.info = st.dev(bInfo);
     for (int i = 0; i < 9; i++) {
         G.Ra[i] = (double)Rcw1[i];
         G.R0[i] = (double)Rcw2[i];
@@ -490,12 +486,9 @@ int initial_ba_run_host(MatchScratch& m, hipStream_t s, const orbfe_initial_ba_p
     G.iterations = P->iterations;
     G.huber = P->robust;
     hipLaunchKernelGGL(initial_ba_kernel, dim3(1), dim3(Pw <= 64 ? 64 : kTreeThreads), 0, s, G);
-    MCHK(hipGetLastError());
-    MCHK(hipMemcpyAsync(hp + inBytes, dp + oInfo, resBytes, hipMemcpyDeviceToHost, s));
-    MCHK(hipStreamSynchronize(s));
-    const uint8_t* r = hp + inBytes;
-    const BaDeviceInfo* I = reinterpret_cast<const BaDeviceInfo*>(r);
-    const float* xOut = reinterpret_cast<const float*>(r + (oXOut - oInfo));
+    if ((rc = download(st, s, err)) != ORBFE_OK) return rc;
+    const BaDeviceInfo* I = st.res(bInfo);
+    const float* xOut = st.res(bXOut);
     fill_tcw(I->pose, I->pose + 9, TcwOut);
     for (int p = 0; p < N; p++)
         for (int k = 0; k < 3; k++) pointsOut[3 * (size_t)first[(size_t)p] + k] = xOut[3 * (size_t)p + k];
@@ -507,8 +500,8 @@ int initial_ba_run_host(MatchScratch& m, hipStream_t s, const orbfe_initial_ba_p
         memcpy(info->cost, I->cost, sizeof I->cost);
         memcpy(info->lambda, I->lambda, sizeof I->lambda);
         memcpy(info->pose, I->pose, sizeof I->pose);
-        if (info->chi2) memcpy(info->chi2, r + (oChi2 - oInfo), (size_t)2 * N * sizeof(double));
-        if (info->depth_positive) memcpy(info->depth_positive, r + (oFront - oInfo), (size_t)2 * N);
+        st.get(bChi2, info->chi2);
+        st.get(bFront, info->depth_positive);
     }
     return ORBFE_OK;
 }

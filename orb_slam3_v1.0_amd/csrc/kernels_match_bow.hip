@@ -348,66 +348,60 @@ int match_bow_run(MatchScratch& m, hipStream_t s, int G, const int* kfOff, const
     for (int i = 0; i < nFIdx; i++)
         if (fIdx[i] < 0 || fIdx[i] >= nF) return ORBFE_ERR_INVALID_ARG;
 
-    Carver in;
-    const size_t oKfOff = in.take((size_t)(G + 1) * sizeof(int));
-    const size_t oFOff = in.take((size_t)(G + 1) * sizeof(int));
-    const size_t oKfIdx = in.take((size_t)std::max(nKfIdx, 1) * sizeof(int));
-    const size_t oFIdx = in.take((size_t)std::max(nFIdx, 1) * sizeof(int));
-    const size_t oKfDesc = in.take((size_t)nKF * 32);
-    const size_t oFDesc = in.take((size_t)nF * 32);
-    const size_t oKfHas = in.take((size_t)nKF);
-    const size_t oKfAng = in.take((size_t)nKF * sizeof(float));
-    const size_t oFAng = in.take((size_t)nF * sizeof(float));
-    const size_t inBytes = in.off;
-    Carver sc = in;
-    const size_t oMatch = sc.take((size_t)nF * sizeof(int));
-    const size_t oBin = sc.take((size_t)nF * sizeof(int));
-    const size_t oNM = sc.take(sizeof(int));
-    int rc = ensure(m, sc.off, inBytes + (size_t)nF * sizeof(int) + 256, err);
+    Staging st;
+    const auto bKfOff = st.in<int>((size_t)G + 1);
+    const auto bFOff = st.in<int>((size_t)G + 1);
+    const auto bKfIdx = st.in<int>(std::max(nKfIdx, 1));
+    const auto bFIdx = st.in<int>(std::max(nFIdx, 1));
+    const auto bKfDesc = st.in<uint8_t>((size_t)nKF * 32);
+    const auto bFDesc = st.in<uint8_t>((size_t)nF * 32);
+    const auto bKfHas = st.in<uint8_t>(nKF);
+    const auto bKfAng = st.in<float>(nKF);
+    const auto bFAng = st.in<float>(nF);
+    const auto bMatch = st.out<int>(nF);
+    const auto bBin = st.scratch<int>(nF);   // between the two pieces that come down, as the layout always had it
+    const auto bNM = st.out<int>(1);
+    int rc = reserve(m, st, err);
     if (rc != ORBFE_OK) return rc;
-    uint8_t* hp = static_cast<uint8_t*>(m.hpin);
-    uint8_t* dp = static_cast<uint8_t*>(m.d);
-    memcpy(hp + oKfOff, kfOff, (size_t)(G + 1) * sizeof(int));
-    memcpy(hp + oFOff, fOff, (size_t)(G + 1) * sizeof(int));
-    memcpy(hp + oKfIdx, kfIdx, (size_t)nKfIdx * sizeof(int));
-    memcpy(hp + oFIdx, fIdx, (size_t)nFIdx * sizeof(int));
-    memcpy(hp + oKfDesc, kfDesc, (size_t)nKF * 32);
-    memcpy(hp + oFDesc, fDesc, (size_t)nF * 32);
-    memcpy(hp + oKfHas, kfHasMP, (size_t)nKF);
-    if (kfAngle) memcpy(hp + oKfAng, kfAngle, (size_t)nKF * sizeof(float));
-    if (fAngle) memcpy(hp + oFAng, fAngle, (size_t)nF * sizeof(float));
-    MCHK(hipMemcpyAsync(dp, hp, inBytes, hipMemcpyHostToDevice, s));
+    st.put(bKfOff, kfOff);
+    st.put(bFOff, fOff);
+    st.put(bKfIdx, kfIdx, nKfIdx);
+    st.put(bFIdx, fIdx, nFIdx);
+    st.put(bKfDesc, kfDesc);
+    st.put(bFDesc, fDesc);
+    st.put(bKfHas, kfHasMP);
+    st.put(bKfAng, kfAngle);
+    st.put(bFAng, fAngle);
+    if ((rc = upload(st, s, err)) != ORBFE_OK) return rc;
 
     BowArgs A{};
     A.G = G;
-    A.kfOff = reinterpret_cast<const int*>(dp + oKfOff);
-    A.fOff = reinterpret_cast<const int*>(dp + oFOff);
-    A.kfIdx = reinterpret_cast<const int*>(dp + oKfIdx);
-    A.fIdx = reinterpret_cast<const int*>(dp + oFIdx);
-    A.kfDesc = dp + oKfDesc;
-    A.fDesc = dp + oFDesc;
-    A.kfHasMP = dp + oKfHas;
-    A.kfAngle = reinterpret_cast<const float*>(dp + oKfAng);
-    A.fAngle = reinterpret_cast<const float*>(dp + oFAng);
+    A.kfOff = st.dev(bKfOff);
+    A.fOff = st.dev(bFOff);
+    A.kfIdx = st.dev(bKfIdx);
+    A.fIdx = st.dev(bFIdx);
+    A.kfDesc = st.dev(bKfDesc);
+    A.fDesc = st.dev(bFDesc);
+    A.kfHasMP = st.dev(bKfHas);
+    A.kfAngle = st.dev(bKfAng);
+    A.fAngle = st.dev(bFAng);
     A.nF = nF;
     A.nLeft = nLeft;
     A.nnRatio = nnRatio;
     A.checkOrientation = checkOrientation;
-    A.matchOut = reinterpret_cast<int*>(dp + oMatch);
-    A.binOf = reinterpret_cast<int*>(dp + oBin);
-    A.nMatches = reinterpret_cast<int*>(dp + oNM);
+    A.matchOut = st.dev(bMatch);
+    A.binOf = st.dev(bBin);
+    A.nMatches = st.dev(bNM);
     const dim3 blk(256);
     hipLaunchKernelGGL(fill_kernel, dim3((nF + 255) / 256), blk, 0, s, A.matchOut, -1, (size_t)nF);
     hipLaunchKernelGGL(bow_match_kernel, dim3((G + 3) / 4), blk, 0, s, A);
     hipLaunchKernelGGL(bow_finalize_kernel, dim3(1), blk, 0, s, A);
     MCHK(hipGetLastError());
-    int* hMatch = reinterpret_cast<int*>(hp + inBytes);
-    int* hNM = hMatch + nF;
-    MCHK(hipMemcpyAsync(hMatch, A.matchOut, (size_t)nF * sizeof(int), hipMemcpyDeviceToHost, s));
-    MCHK(hipMemcpyAsync(hNM, A.nMatches, sizeof(int), hipMemcpyDeviceToHost, s));
+    if ((rc = fetch_span(st, s, bMatch.off, bMatch.end(), err)) != ORBFE_OK) return rc;
+    if ((rc = fetch_span(st, s, bNM.off, bNM.end(), err)) != ORBFE_OK) return rc;
     MCHK(hipStreamSynchronize(s));
-    memcpy(matchOut, hMatch, (size_t)nF * sizeof(int));
-    *nMatches = *hNM;
+    st.get(bMatch, matchOut);
+    *nMatches = *st.res(bNM);
     return ORBFE_OK;
 }
 

@@ -490,61 +490,58 @@ int match_initialization_run(MatchScratch& m, hipStream_t s, const orbfe_frame_v
     *nMatches = 0;
     if (n1 == 0 || n2 == 0) return ORBFE_OK;
     if (n2 >= (1 << 20) || F2->grid_cols > 65535 || F2->grid_rows > 32767) return ORBFE_ERR_UNSUPPORTED;
-    Carver c;
-    const size_t oKp1 = c.take((size_t)n1 * sizeof(orbfe_keypoint));
-    const size_t oD1 = c.take((size_t)n1 * 32);
-    const size_t oKp2 = c.take((size_t)n2 * sizeof(orbfe_keypoint));
-    const size_t oD2 = c.take((size_t)n2 * 32);
-    const size_t oL0 = c.take((size_t)n1 * sizeof(int));  // uploaded for the fast path, written by the sequential kernel otherwise
-    const size_t inBytes = c.off;
-    const size_t oM12 = c.take((size_t)n1 * sizeof(int));
-    const size_t oNM = c.take(sizeof(int));
-    const size_t outBytes = c.off - oM12;
-    const size_t oM21 = c.take((size_t)n2 * sizeof(int));
-    const size_t oMD = c.take((size_t)n2 * sizeof(int));
-    const size_t oCell = c.take((size_t)n2 * sizeof(int));
-    const size_t oBin = c.take((size_t)n1 * sizeof(int));
     int n0 = 0;  // level-0 keypoints of frame 1 (:346-347): selects the kernel and sizes its candidate scratch
     for (int i = 0; i < n1; i++) n0 += F1->kp[i].octave <= 0;
     bool fast = n2 <= kInitN && n0 <= kFastN0;
-    const size_t oCand = c.take(fast ? (size_t)std::max(n0, 1) * n2 * sizeof(unsigned long long) : 8);
-    const size_t oHdr = c.take(fast ? (size_t)std::max(n0, 1) * sizeof(InitRowHdr) : 8);
-    int rc = ensure(m, c.off, inBytes + outBytes + 256, err);
+    // (the scratch lies behind the results here: the layout of this call is older than the three phases and stays)
+    Staging st;
+    const auto bKp1 = st.in<orbfe_keypoint>(n1);
+    const auto bD1 = st.in<uint8_t>((size_t)n1 * 32);
+    const auto bKp2 = st.in<orbfe_keypoint>(n2);
+    const auto bD2 = st.in<uint8_t>((size_t)n2 * 32);
+    const auto bL0 = st.in<int>(n1);  // uploaded for the fast path, written by the sequential kernel otherwise
+    const auto bM12 = st.out<int>(n1);
+    const auto bNM = st.out<int>(1);
+    const auto bM21 = st.scratch<int>(n2);
+    const auto bMD = st.scratch<int>(n2);
+    const auto bCell = st.scratch<int>(n2);
+    const auto bBin = st.scratch<int>(n1);
+    const auto bCand = st.scratch<unsigned long long>(fast ? (size_t)std::max(n0, 1) * n2 : 1);
+    const auto bHdr = st.scratch<InitRowHdr>(fast ? (size_t)std::max(n0, 1) : 1);
+    int rc = reserve(m, st, err);
     if (rc != ORBFE_OK) return rc;
-    uint8_t* hp = static_cast<uint8_t*>(m.hpin);
-    uint8_t* dp = static_cast<uint8_t*>(m.d);
-    memcpy(hp + oKp1, F1->kp, (size_t)n1 * sizeof(orbfe_keypoint));
-    memcpy(hp + oD1, F1->desc, (size_t)n1 * 32);
-    memcpy(hp + oKp2, F2->kp, (size_t)n2 * sizeof(orbfe_keypoint));
-    memcpy(hp + oD2, F2->desc, (size_t)n2 * 32);
+    st.put(bKp1, F1->kp);
+    st.put(bD1, F1->desc);
+    st.put(bKp2, F2->kp);
+    st.put(bD2, F2->desc);
     if (fast) {  // row t of the candidate pass = t-th level-0 keypoint of frame 1 (level1 > 0 -> continue, :346-347)
-        int* l0 = reinterpret_cast<int*>(hp + oL0);
+        int* l0 = st.host(bL0);
         for (int i = 0, t = 0; i < n1; i++)
             if (F1->kp[i].octave <= 0) l0[t++] = i;
     }
-    MCHK(hipMemcpyAsync(dp, hp, inBytes, hipMemcpyHostToDevice, s));
+    if ((rc = upload(st, s, err)) != ORBFE_OK) return rc;
     InitArgs A{};
     A.n1 = n1; A.n2 = n2;
     A.n2Dev = nullptr;
     A.candStride = n2;
-    A.kp1 = reinterpret_cast<const orbfe_keypoint*>(dp + oKp1);
-    A.desc1 = dp + oD1;
-    A.kp2 = reinterpret_cast<const orbfe_keypoint*>(dp + oKp2);
-    A.desc2 = dp + oD2;
+    A.kp1 = st.dev(bKp1);
+    A.desc1 = st.dev(bD1);
+    A.kp2 = st.dev(bKp2);
+    A.desc2 = st.dev(bD2);
     A.cols = F2->grid_cols; A.rows = F2->grid_rows;
     A.minX = F2->min_x; A.minY = F2->min_y; A.invW = F2->grid_inv_w; A.invH = F2->grid_inv_h;
     A.r = (float)windowSize;
     A.nnRatio = nnRatio;
     A.checkOrientation = checkOrientation;
-    A.matches12 = reinterpret_cast<int*>(dp + oM12);
-    A.nMatches = reinterpret_cast<int*>(dp + oNM);
-    A.matched21 = reinterpret_cast<int*>(dp + oM21);
-    A.matchedDist = reinterpret_cast<int*>(dp + oMD);
-    A.cell2 = reinterpret_cast<int*>(dp + oCell);
-    A.list0 = reinterpret_cast<int*>(dp + oL0);
-    A.binOf = reinterpret_cast<int*>(dp + oBin);
-    A.cand = reinterpret_cast<unsigned long long*>(dp + oCand);
-    A.hdr = reinterpret_cast<InitRowHdr*>(dp + oHdr);
+    A.matches12 = st.dev(bM12);
+    A.nMatches = st.dev(bNM);
+    A.matched21 = st.dev(bM21);
+    A.matchedDist = st.dev(bMD);
+    A.cell2 = st.dev(bCell);
+    A.list0 = st.dev(bL0);
+    A.binOf = st.dev(bBin);
+    A.cand = st.dev(bCand);
+    A.hdr = st.dev(bHdr);
 #ifdef ORBFE_DIAG
     if (getenv("ORBFE_INIT_SLOW")) fast = false;  // liborbfe_diag.so only: force the sequential block kernel
 #endif
@@ -556,12 +553,9 @@ int match_initialization_run(MatchScratch& m, hipStream_t s, const orbfe_frame_v
         hipLaunchKernelGGL(init_match_kernel<true>, dim3(1), dim3(kInitThreads), 0, s, A);
     else
         hipLaunchKernelGGL(init_match_kernel<false>, dim3(1), dim3(kInitThreads), 0, s, A);
-    MCHK(hipGetLastError());
-    uint8_t* hOut = hp + inBytes;
-    MCHK(hipMemcpyAsync(hOut, dp + oM12, outBytes, hipMemcpyDeviceToHost, s));
-    MCHK(hipStreamSynchronize(s));
-    memcpy(matches12Out, hOut, (size_t)n1 * sizeof(int));
-    *nMatches = *reinterpret_cast<int*>(hOut + (oNM - oM12));
+    if ((rc = download(st, s, err)) != ORBFE_OK) return rc;
+    st.get(bM12, matches12Out);
+    *nMatches = *st.res(bNM);
     return ORBFE_OK;
 }
 

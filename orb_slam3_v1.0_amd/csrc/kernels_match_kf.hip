@@ -341,56 +341,50 @@ int fuse_search_run(MatchScratch& m, hipStream_t s, const orbfe_frame_view* KF, 
         (long long)KF->grid_cols * KF->grid_rows > kMaxCells)
         return ORBFE_ERR_UNSUPPORTED;
     if (F->n_levels > KF->n_levels) return ORBFE_ERR_INVALID_ARG;  // predicted levels index the key frame's scale tables
-    Carver in;
-    const size_t oKp = in.take((size_t)n * sizeof(orbfe_keypoint));
-    const size_t oDesc = in.take((size_t)n * 32);
-    const size_t oPts = in.take((size_t)M * sizeof(orbfe_world_point));
-    const size_t oMpDesc = in.take((size_t)M * 32);
-    const size_t oSf = in.take((size_t)KF->n_levels * sizeof(float));
-    const size_t oIs2 = in.take((size_t)KF->n_levels * sizeof(float));
-    const size_t oUr = in.take((size_t)n * sizeof(float));
-    const size_t oN = in.take(sizeof(int));
-    const size_t oRight = in.take((size_t)(nRight > 0 ? nRight : 0) * 32);  // rows NLeft .. of mDescriptors (bRight)
-    const size_t inBytes = in.off;
-    const size_t oMatch = in.take((size_t)n * sizeof(int));  // the grid kernel clears a match array
-    const size_t oBest = in.take((size_t)M * 2 * sizeof(int));
+    Staging st;
+    const auto bKp = st.in<orbfe_keypoint>(n);
+    const auto bDesc = st.in<uint8_t>((size_t)n * 32);
+    const auto bPts = st.in<orbfe_world_point>(M);
+    const auto bMpDesc = st.in<uint8_t>((size_t)M * 32);
+    const auto bSf = st.in<float>(KF->n_levels);
+    const auto bIs2 = st.in<float>(KF->n_levels);
+    const auto bUr = st.in<float>(n);
+    const auto bN = st.in<int>(1);
+    const auto bRight = st.in<unsigned long long>((size_t)(nRight > 0 ? nRight : 0) * 4);  // rows NLeft .. of mDescriptors (bRight)
+    const auto bMatch = st.scratch<int>(n);  // the grid kernel clears a match array
+    const auto bBest = st.out<int>((size_t)M * 2);  // [bestIdx | bestDist]
     ProjArgs A{};
     A.B = 1; A.M = 1; A.kpStride = n;
     A.g = GridDesc{KF->grid_cols, KF->grid_rows, KF->min_x, KF->min_y, KF->grid_inv_w, KF->grid_inv_h};
     A.nnRatio = 1.0f;
     A.nLevels = KF->n_levels;
-    int rc = proj_setup(m, A, in, inBytes + (size_t)M * 2 * sizeof(int) + 64, err);
+    const ProjTables T = proj_tables(st, A);
+    int rc = reserve(m, st, err);
     if (rc != ORBFE_OK) return rc;
-    uint8_t* hp = static_cast<uint8_t*>(m.hpin);
-    uint8_t* dp = static_cast<uint8_t*>(m.d);
-    memcpy(hp + oKp, KF->kp, (size_t)n * sizeof(orbfe_keypoint));
-    memcpy(hp + oDesc, KF->desc, (size_t)n * 32);
-    memcpy(hp + oPts, pts, (size_t)M * sizeof(orbfe_world_point));
-    memcpy(hp + oMpDesc, mpDesc, (size_t)M * 32);
-    memcpy(hp + oSf, KF->scale_factors, (size_t)KF->n_levels * sizeof(float));
-    if (invLevelSigma2) memcpy(hp + oIs2, invLevelSigma2, (size_t)KF->n_levels * sizeof(float));
-    if (uRight) memcpy(hp + oUr, uRight, (size_t)n * sizeof(float));
-    memcpy(hp + oN, &n, sizeof(int));
-    if (nRight > 0) memcpy(hp + oRight, KF->desc + (size_t)n * 32, (size_t)nRight * 32);
-    MCHK(hipMemcpyAsync(dp, hp, inBytes, hipMemcpyHostToDevice, s));
-    A.kp = reinterpret_cast<const orbfe_keypoint*>(dp + oKp);
-    A.desc = dp + oDesc;
-    A.nKp = reinterpret_cast<const int*>(dp + oN);
-    A.scaleFactors = reinterpret_cast<const float*>(dp + oSf);
-    A.matchOut = reinterpret_cast<int*>(dp + oMatch);
+    proj_bind(st, T, A);
+    st.put(bKp, KF->kp);
+    st.put(bDesc, KF->desc);
+    st.put(bPts, pts);
+    st.put(bMpDesc, mpDesc);
+    st.put(bSf, KF->scale_factors);
+    st.put(bIs2, invLevelSigma2);
+    st.put(bUr, uRight);
+    st.put(bN, &n);
+    st.put(bRight, KF->desc + (size_t)n * 32);
+    if ((rc = upload(st, s, err)) != ORBFE_OK) return rc;
+    A.kp = st.dev(bKp);
+    A.desc = st.dev(bDesc);
+    A.nKp = st.dev(bN);
+    A.scaleFactors = st.dev(bSf);
+    A.matchOut = st.dev(bMatch);
     proj_prepare_launch(s, A, false);
-    int* dBest = reinterpret_cast<int*>(dp + oBest);
-    hipLaunchKernelGGL(fuse_search_kernel<false>, dim3((M + 63) / 64), dim3(64), 0, s, A, *F, th, M, nullptr, 0,
-                       reinterpret_cast<const orbfe_world_point*>(dp + oPts), dp + oMpDesc,
-                       reinterpret_cast<const float*>(dp + oIs2), uRight ? reinterpret_cast<const float*>(dp + oUr) : nullptr,
-                       chi2Gate, nRight >= 0 ? reinterpret_cast<const unsigned long long*>(dp + oRight) : nullptr, nRight, dBest,
-                       dBest + M);
-    MCHK(hipGetLastError());
-    int* hBest = reinterpret_cast<int*>(hp + inBytes);
-    MCHK(hipMemcpyAsync(hBest, dBest, (size_t)M * 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-    MCHK(hipStreamSynchronize(s));
-    memcpy(bestIdxOut, hBest, (size_t)M * sizeof(int));
-    memcpy(bestDistOut, hBest + M, (size_t)M * sizeof(int));
+    int* dBest = st.dev(bBest);
+    hipLaunchKernelGGL(fuse_search_kernel<false>, dim3((M + 63) / 64), dim3(64), 0, s, A, *F, th, M, nullptr, 0, st.dev(bPts),
+                       st.dev(bMpDesc), st.dev(bIs2), uRight ? st.dev(bUr) : nullptr, chi2Gate, nRight >= 0 ? st.dev(bRight) : nullptr, nRight,
+                       dBest, dBest + M);
+    if ((rc = download_span(st, s, bBest.off, bBest.end(), err)) != ORBFE_OK) return rc;
+    st.get(bBest, bestIdxOut, M);
+    memcpy(bestDistOut, st.res(bBest) + M, (size_t)M * sizeof(int));
     return ORBFE_OK;
 }
 
@@ -452,25 +446,19 @@ int fuse_search_keyframe_run(MatchScratch& m, hipStream_t s, const KeyFrameDev* 
     }
     if (K->n == 0 || M == 0) return ORBFE_OK;
     if (F->n_levels > K->nLevels) return ORBFE_ERR_INVALID_ARG;  // predicted levels index the key frame's scale tables
-    Carver c;
-    const size_t oIds = c.take((size_t)M * sizeof(int));
-    const size_t oBest = c.take((size_t)M * 2 * sizeof(int));
-    int rc = ensure(m, c.off, c.off, err);
+    Staging st;
+    const auto bIds = st.in<int>(M);
+    const auto bBest = st.out<int>((size_t)M * 2);  // [bestIdx | bestDist]
+    int rc = reserve(m, st, err);
     if (rc != ORBFE_OK) return rc;
-    uint8_t* hp = static_cast<uint8_t*>(m.hpin);
-    uint8_t* dp = static_cast<uint8_t*>(m.d);
-    memcpy(hp + oIds, ids, (size_t)M * sizeof(int));
-    MCHK(hipMemcpyAsync(dp + oIds, hp + oIds, (size_t)M * sizeof(int), hipMemcpyHostToDevice, s));
-    int* dBest = reinterpret_cast<int*>(dp + oBest);
-    hipLaunchKernelGGL(fuse_search_kernel<true>, dim3((M + 63) / 64), dim3(64), 0, s, K->grid, *F, th, M,
-                       reinterpret_cast<const int*>(dp + oIds), mapCap, mapPts, mapDesc, K->invLevelSigma2, K->uRight, 1,
-                       static_cast<const unsigned long long*>(nullptr), -1, dBest, dBest + M);
-    MCHK(hipGetLastError());
-    int* hBest = reinterpret_cast<int*>(hp + oBest);
-    MCHK(hipMemcpyAsync(hBest, dBest, (size_t)M * 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-    MCHK(hipStreamSynchronize(s));
-    memcpy(bestIdxOut, hBest, (size_t)M * sizeof(int));
-    memcpy(bestDistOut, hBest + M, (size_t)M * sizeof(int));
+    st.put(bIds, ids);
+    if ((rc = upload_span(st, s, bIds.off, bIds.end(), err)) != ORBFE_OK) return rc;
+    int* dBest = st.dev(bBest);
+    hipLaunchKernelGGL(fuse_search_kernel<true>, dim3((M + 63) / 64), dim3(64), 0, s, K->grid, *F, th, M, st.dev(bIds), mapCap, mapPts,
+                       mapDesc, K->invLevelSigma2, K->uRight, 1, static_cast<const unsigned long long*>(nullptr), -1, dBest, dBest + M);
+    if ((rc = download_span(st, s, bBest.off, bBest.end(), err)) != ORBFE_OK) return rc;
+    st.get(bBest, bestIdxOut, M);
+    memcpy(bestDistOut, st.res(bBest) + M, (size_t)M * sizeof(int));
     return ORBFE_OK;
 }
 
@@ -480,18 +468,14 @@ int fuse_search_keyframes_run(MatchScratch& m, hipStream_t s, int K, const KeyFr
                               int* candCountOut, std::string& err)
 {
     const size_t KM = (size_t)K * M;
-    Carver c;
-    const size_t oTab = c.take((size_t)K * sizeof(FuseTarget));
-    const size_t oIds = c.take((size_t)M * sizeof(int));
-    const size_t oSkip = c.take(skip ? KM : 0);
-    const size_t inBytes = c.off;
-    const size_t outInts = KM * (size_t)(candCap > 0 ? 3 + candCap : 2);  // [bestIdx | bestDist | candCount | candIdx]
-    const size_t oOut = c.take(outInts * sizeof(int));
-    int rc = ensure(m, c.off, c.off, err);
+    Staging st;
+    const auto bTab = st.in<FuseTarget>(K);
+    const auto bIds = st.in<int>(M);
+    const auto bSkip = st.in<uint8_t>(skip ? KM : 0);
+    const auto bOut = st.out<int>(KM * (size_t)(candCap > 0 ? 3 + candCap : 2));  // [bestIdx | bestDist | candCount | candIdx]
+    int rc = reserve(m, st, err);
     if (rc != ORBFE_OK) return rc;
-    uint8_t* hp = static_cast<uint8_t*>(m.hpin);
-    uint8_t* dp = static_cast<uint8_t*>(m.d);
-    FuseTarget* hTab = reinterpret_cast<FuseTarget*>(hp + oTab);
+    FuseTarget* hTab = st.host(bTab);
     for (int k = 0; k < K; k++) {
         hTab[k].A = kfs[k]->grid;
         hTab[k].F = frusta[k];
@@ -499,13 +483,13 @@ int fuse_search_keyframes_run(MatchScratch& m, hipStream_t s, int K, const KeyFr
         hTab[k].uRight = kfs[k]->uRight;
         hTab[k].n = kfs[k]->n;
     }
-    memcpy(hp + oIds, ids, (size_t)M * sizeof(int));
-    if (skip) memcpy(hp + oSkip, skip, KM);
-    MCHK(hipMemcpyAsync(dp, hp, inBytes, hipMemcpyHostToDevice, s));  // table, ids and skip flags in one copy
-    int* dOut = reinterpret_cast<int*>(dp + oOut);
-    const FuseTarget* dTab = reinterpret_cast<const FuseTarget*>(dp + oTab);
-    const int* dIds = reinterpret_cast<const int*>(dp + oIds);
-    const uint8_t* dSkip = skip ? dp + oSkip : nullptr;
+    st.put(bIds, ids);
+    st.put(bSkip, skip);
+    if ((rc = upload(st, s, err)) != ORBFE_OK) return rc;  // table, ids and skip flags in one copy
+    int* dOut = st.dev(bOut);
+    const FuseTarget* dTab = st.dev(bTab);
+    const int* dIds = st.dev(bIds);
+    const uint8_t* dSkip = skip ? st.dev(bSkip) : nullptr;
     const dim3 grid((M + 63) / 64, K);
     if (candCap > 0)
         hipLaunchKernelGGL(fuse_neighbors_kernel<true>, grid, dim3(64), 0, s, dTab, th, M, dIds, dSkip, mapCap, mapPts, mapDesc, dOut,
@@ -513,10 +497,8 @@ int fuse_search_keyframes_run(MatchScratch& m, hipStream_t s, int K, const KeyFr
     else
         hipLaunchKernelGGL(fuse_neighbors_kernel<false>, grid, dim3(64), 0, s, dTab, th, M, dIds, dSkip, mapCap, mapPts, mapDesc, dOut,
                            dOut + KM, 0, static_cast<int*>(nullptr), static_cast<int*>(nullptr));
-    MCHK(hipGetLastError());
-    int* hOut = reinterpret_cast<int*>(hp + oOut);
-    MCHK(hipMemcpyAsync(hOut, dOut, outInts * sizeof(int), hipMemcpyDeviceToHost, s));
-    MCHK(hipStreamSynchronize(s));
+    if ((rc = download_span(st, s, bOut.off, bOut.end(), err)) != ORBFE_OK) return rc;
+    const int* hOut = st.res(bOut);
     memcpy(bestIdxOut, hOut, KM * sizeof(int));
     memcpy(bestDistOut, hOut + KM, KM * sizeof(int));
     if (candCap > 0) {
@@ -558,36 +540,34 @@ int view_unsupported(const orbfe_frame_view* V)
            (long long)V->grid_cols * V->grid_rows > kMaxCells;
 }
 
-// host staging offsets of one key frame's inputs for the thread-per-point searches
-struct ViewStage {
-    size_t oKp, oDesc, oSf, oN, oMatch;
-};
+// one key frame's inputs for the thread-per-point searches, and the match array the grid kernel clears
+struct ViewBlocks { Block<orbfe_keypoint> kp; Block<uint8_t> desc; Block<float> sf; Block<int> n, match; };
 
-ViewStage view_carve(Carver& in, const orbfe_frame_view* V)
+ViewBlocks view_in(Staging& st, const orbfe_frame_view* V)
 {
-    ViewStage st;
-    st.oKp = in.take((size_t)V->n * sizeof(orbfe_keypoint));
-    st.oDesc = in.take((size_t)V->n * 32);
-    st.oSf = in.take((size_t)V->n_levels * sizeof(float));
-    st.oN = in.take(sizeof(int));
-    return st;
+    ViewBlocks b;
+    b.kp = st.in<orbfe_keypoint>(V->n);
+    b.desc = st.in<uint8_t>((size_t)V->n * 32);
+    b.sf = st.in<float>(V->n_levels);
+    b.n = st.in<int>(1);
+    return b;
 }
 
-void view_fill(uint8_t* hp, const ViewStage& st, const orbfe_frame_view* V)
+void view_fill(const Staging& st, const ViewBlocks& b, const orbfe_frame_view* V)
 {
-    memcpy(hp + st.oKp, V->kp, (size_t)V->n * sizeof(orbfe_keypoint));
-    memcpy(hp + st.oDesc, V->desc, (size_t)V->n * 32);
-    memcpy(hp + st.oSf, V->scale_factors, (size_t)V->n_levels * sizeof(float));
-    memcpy(hp + st.oN, &V->n, sizeof(int));
+    st.put(b.kp, V->kp);
+    st.put(b.desc, V->desc);
+    st.put(b.sf, V->scale_factors);
+    st.put(b.n, &V->n);
 }
 
-void view_bind(ProjArgs& A, uint8_t* dp, const ViewStage& st)
+void view_bind(ProjArgs& A, const Staging& st, const ViewBlocks& b)
 {
-    A.kp = reinterpret_cast<const orbfe_keypoint*>(dp + st.oKp);
-    A.desc = dp + st.oDesc;
-    A.nKp = reinterpret_cast<const int*>(dp + st.oN);
-    A.scaleFactors = reinterpret_cast<const float*>(dp + st.oSf);
-    A.matchOut = reinterpret_cast<int*>(dp + st.oMatch);
+    A.kp = st.dev(b.kp);
+    A.desc = st.dev(b.desc);
+    A.nKp = st.dev(b.n);
+    A.scaleFactors = st.dev(b.sf);
+    A.matchOut = st.dev(b.match);
 }
 
 ProjArgs view_args(const orbfe_frame_view* V)
@@ -620,61 +600,43 @@ int search_by_sim3_run(MatchScratch& m, hipStream_t s, const orbfe_frame_view* K
     // predicted levels index the target key frame's scale tables
     if (d12->n_levels > KF2->n_levels || d21->n_levels > KF1->n_levels || d12->n_levels < 1 || d21->n_levels < 1)
         return ORBFE_ERR_INVALID_ARG;
-    Carver in;
-    ViewStage s1 = view_carve(in, KF1), s2 = view_carve(in, KF2);
-    const size_t oP1 = in.take((size_t)n1 * sizeof(orbfe_world_point));
-    const size_t oD1 = in.take((size_t)n1 * 32);
-    const size_t oP2 = in.take((size_t)n2 * sizeof(orbfe_world_point));
-    const size_t oD2 = in.take((size_t)n2 * 32);
-    const size_t inBytes = in.off;
-    s1.oMatch = in.take((size_t)n1 * sizeof(int));  // the grid kernels clear a match array each
-    s2.oMatch = in.take((size_t)n2 * sizeof(int));
-    const size_t oVn1 = in.take((size_t)n1 * sizeof(int));
-    const size_t oVn2 = in.take((size_t)n2 * sizeof(int));
-    const size_t oOut = in.take((size_t)(n1 + 1) * sizeof(int));
-    const size_t hostNeed = inBytes + (size_t)(n1 + 1) * sizeof(int) + 64;
+    Staging st;
+    ViewBlocks v1 = view_in(st, KF1), v2 = view_in(st, KF2);
+    const auto bP1 = st.in<orbfe_world_point>(n1);
+    const auto bD1 = st.in<uint8_t>((size_t)n1 * 32);
+    const auto bP2 = st.in<orbfe_world_point>(n2);
+    const auto bD2 = st.in<uint8_t>((size_t)n2 * 32);
+    v1.match = st.scratch<int>(n1);  // the grid kernels clear a match array each
+    v2.match = st.scratch<int>(n2);
+    const auto bVn1 = st.scratch<int>(n1);
+    const auto bVn2 = st.scratch<int>(n2);
+    const auto bOut = st.out<int>((size_t)n1 + 1);  // matches, then the count
     ProjArgs A1 = view_args(KF1), A2 = view_args(KF2);
-    size_t end1 = 0;
-    int rc = proj_setup(m, A1, in, hostNeed, err, &end1);
+    const ProjTables T1 = proj_tables(st, A1), T2 = proj_tables(st, A2);
+    int rc = reserve(m, st, err);  // once, for both table sets
     if (rc != ORBFE_OK) return rc;
-    Carver after1;
-    after1.off = end1;
-    const void* d0 = m.d;
-    rc = proj_setup(m, A2, after1, hostNeed, err);
-    if (rc != ORBFE_OK) return rc;
-    if (m.d != d0) {  // the arena grew: bind the first table set again (no further growth: the size is covered now)
-        rc = proj_setup(m, A1, in, hostNeed, err);
-        if (rc != ORBFE_OK) return rc;
-    }
-    uint8_t* hp = static_cast<uint8_t*>(m.hpin);
-    uint8_t* dp = static_cast<uint8_t*>(m.d);
-    view_fill(hp, s1, KF1);
-    view_fill(hp, s2, KF2);
-    memcpy(hp + oP1, mp1, (size_t)n1 * sizeof(orbfe_world_point));
-    memcpy(hp + oD1, mpDesc1, (size_t)n1 * 32);
-    memcpy(hp + oP2, mp2, (size_t)n2 * sizeof(orbfe_world_point));
-    memcpy(hp + oD2, mpDesc2, (size_t)n2 * 32);
-    MCHK(hipMemcpyAsync(dp, hp, inBytes, hipMemcpyHostToDevice, s));
-    view_bind(A1, dp, s1);
-    view_bind(A2, dp, s2);
+    proj_bind(st, T1, A1);
+    proj_bind(st, T2, A2);
+    view_fill(st, v1, KF1);
+    view_fill(st, v2, KF2);
+    st.put(bP1, mp1);
+    st.put(bD1, mpDesc1);
+    st.put(bP2, mp2);
+    st.put(bD2, mpDesc2);
+    if ((rc = upload(st, s, err)) != ORBFE_OK) return rc;
+    view_bind(A1, st, v1);
+    view_bind(A2, st, v2);
     view_prepare(s, A1);
     view_prepare(s, A2);
-    int* vn1 = reinterpret_cast<int*>(dp + oVn1);
-    int* vn2 = reinterpret_cast<int*>(dp + oVn2);
-    int* dOut = reinterpret_cast<int*>(dp + oOut);
+    int *vn1 = st.dev(bVn1), *vn2 = st.dev(bVn2), *dOut = st.dev(bOut);
     // key frame 1's map points into key frame 2 (tables A2), then the other way round
-    hipLaunchKernelGGL(sim3_search_kernel, dim3((n1 + 63) / 64), dim3(64), 0, s, A2, *d12, th, n1,
-                       reinterpret_cast<const orbfe_world_point*>(dp + oP1), dp + oD1, vn1);
-    hipLaunchKernelGGL(sim3_search_kernel, dim3((n2 + 63) / 64), dim3(64), 0, s, A1, *d21, th, n2,
-                       reinterpret_cast<const orbfe_world_point*>(dp + oP2), dp + oD2, vn2);
+    hipLaunchKernelGGL(sim3_search_kernel, dim3((n1 + 63) / 64), dim3(64), 0, s, A2, *d12, th, n1, st.dev(bP1), st.dev(bD1), vn1);
+    hipLaunchKernelGGL(sim3_search_kernel, dim3((n2 + 63) / 64), dim3(64), 0, s, A1, *d21, th, n2, st.dev(bP2), st.dev(bD2), vn2);
     MCHK(hipMemsetAsync(dOut + n1, 0, sizeof(int), s));
     hipLaunchKernelGGL(sim3_agree_kernel, dim3((n1 + 255) / 256), dim3(256), 0, s, n1, vn1, vn2, dOut, dOut + n1);
-    MCHK(hipGetLastError());
-    int* hOut = reinterpret_cast<int*>(hp + inBytes);
-    MCHK(hipMemcpyAsync(hOut, dOut, (size_t)(n1 + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
-    MCHK(hipStreamSynchronize(s));
-    memcpy(match12Out, hOut, (size_t)n1 * sizeof(int));
-    *nFound = hOut[n1];
+    if ((rc = download_span(st, s, bOut.off, bOut.end(), err)) != ORBFE_OK) return rc;
+    st.get(bOut, match12Out, n1);
+    *nFound = st.res(bOut)[n1];
     return ORBFE_OK;
 }
 
@@ -689,49 +651,42 @@ int match_projection_kf_run(MatchScratch& m, hipStream_t s, const orbfe_frame_vi
     if (n == 0 || M == 0) return ORBFE_OK;
     if (view_unsupported(F)) return ORBFE_ERR_UNSUPPORTED;
     if (Fr->n_levels > F->n_levels || Fr->n_levels < 1) return ORBFE_ERR_INVALID_ARG;
-    Carver in;
-    ViewStage st = view_carve(in, F);
-    const size_t oPts = in.take((size_t)M * sizeof(orbfe_world_point));
-    const size_t oMpDesc = in.take((size_t)M * 32);
-    const size_t oAng = in.take((size_t)M * sizeof(float));
-    const size_t oObs = in.take((size_t)n * sizeof(int));
-    const size_t inBytes = in.off;
-    st.oMatch = in.take((size_t)(n + 1) * sizeof(int));  // matches, then the count
-    const size_t oMp = in.take((size_t)M * sizeof(orbfe_map_point));
-    const size_t hostNeed = inBytes + (size_t)(n + 1) * sizeof(int) + 64;
+    Staging st;
+    ViewBlocks v = view_in(st, F);
+    const auto bPts = st.in<orbfe_world_point>(M);
+    const auto bMpDesc = st.in<uint8_t>((size_t)M * 32);
+    const auto bAng = st.in<float>(M);
+    const auto bObs = st.in<int>(n);
+    v.match = st.out<int>((size_t)n + 1);  // matches, then the count
+    const auto bMp = st.scratch<orbfe_map_point>(M);
     ProjArgs A = view_args(F);
     A.M = M;
     A.mode = kModeReloc;
     A.th = th;
     A.nnRatio = 3.0e38f;  // "best <= nnRatio * second" always holds: this overload has no ratio test
-    int rc = proj_setup(m, A, in, hostNeed, err);
+    const ProjTables T = proj_tables(st, A);
+    int rc = reserve(m, st, err);
     if (rc != ORBFE_OK) return rc;
-    uint8_t* hp = static_cast<uint8_t*>(m.hpin);
-    uint8_t* dp = static_cast<uint8_t*>(m.d);
-    view_fill(hp, st, F);
-    memcpy(hp + oPts, pts, (size_t)M * sizeof(orbfe_world_point));
-    memcpy(hp + oMpDesc, mpDesc, (size_t)M * 32);
-    if (kfAngle) memcpy(hp + oAng, kfAngle, (size_t)M * sizeof(float));
-    int* hObs = reinterpret_cast<int*>(hp + oObs);
+    proj_bind(st, T, A);
+    view_fill(st, v, F);
+    st.put(bPts, pts);
+    st.put(bMpDesc, mpDesc);
+    st.put(bAng, kfAngle);
+    int* hObs = st.host(bObs);
     for (int i = 0; i < n; i++) hObs[i] = (frameHasMP && frameHasMP[i]) ? 1 : -1;  // :1268: an occupied slot is never a candidate
-    MCHK(hipMemcpyAsync(dp, hp, inBytes, hipMemcpyHostToDevice, s));
-    view_bind(A, dp, st);
-    A.mps = reinterpret_cast<const orbfe_map_point*>(dp + oMp);
-    A.mpDesc = dp + oMpDesc;
-    A.initObs = reinterpret_cast<const int*>(dp + oObs);
+    if ((rc = upload(st, s, err)) != ORBFE_OK) return rc;
+    view_bind(A, st, v);
+    A.mps = st.dev(bMp);
+    A.mpDesc = st.dev(bMpDesc);
+    A.initObs = st.dev(bObs);
     A.nMatches = A.matchOut + n;
-    hipLaunchKernelGGL(reloc_project_kernel, dim3((M + 255) / 256), dim3(256), 0, s, *Fr, M,
-                       reinterpret_cast<const orbfe_world_point*>(dp + oPts), reinterpret_cast<orbfe_map_point*>(dp + oMp));
+    hipLaunchKernelGGL(reloc_project_kernel, dim3((M + 255) / 256), dim3(256), 0, s, *Fr, M, st.dev(bPts), st.dev(bMp));
     rc = proj_launch(s, A, err);
     if (rc != ORBFE_OK) return rc;
-    hipLaunchKernelGGL(reloc_finalize_kernel, dim3(1), dim3(256), 0, s, n, A.kp, reinterpret_cast<const float*>(dp + oAng),
-                       checkOrientation, A.matchOut, A.nMatches);
-    MCHK(hipGetLastError());
-    int* hOut = reinterpret_cast<int*>(hp + inBytes);
-    MCHK(hipMemcpyAsync(hOut, A.matchOut, (size_t)(n + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
-    MCHK(hipStreamSynchronize(s));
-    memcpy(matchOut, hOut, (size_t)n * sizeof(int));
-    *nMatches = hOut[n];
+    hipLaunchKernelGGL(reloc_finalize_kernel, dim3(1), dim3(256), 0, s, n, A.kp, st.dev(bAng), checkOrientation, A.matchOut, A.nMatches);
+    if ((rc = download_span(st, s, v.match.off, v.match.end(), err)) != ORBFE_OK) return rc;
+    st.get(v.match, matchOut, n);
+    *nMatches = st.res(v.match)[n];
     return ORBFE_OK;
 }
 

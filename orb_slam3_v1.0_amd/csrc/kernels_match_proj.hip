@@ -1056,43 +1056,55 @@ int proj_dcut(float nnRatio)
     return std::max(D, ORBFE_TH_HIGH + 1);
 }
 
-// carve the device scratch after whatever `sc` already holds; sets A's scratch pointers
-int proj_setup(MatchScratch& m, ProjArgs& A, Carver sc, size_t hostNeed, std::string& err, size_t* endOff)
+ProjTables proj_tables(Staging& st, ProjArgs& A)
 {
-    const int B = A.B, M = A.M;
+    const size_t B = (size_t)A.B, Mx = (size_t)std::max(A.M, 1), stride = (size_t)A.kpStride;
     A.sortCap = 1;
     while (A.sortCap < A.kpStride) A.sortCap <<= 1;
     const bool ldsSort = A.kpStride <= kSortLds;
-    const size_t oKeys = sc.take(ldsSort ? 8 : (size_t)B * A.sortCap * sizeof(unsigned long long));
     A.tabLevels = std::min(std::max(A.nLevels, 1), 32);
     A.dCut = proj_dcut(A.nnRatio);
-    const size_t oOrder = sc.take((size_t)B * A.kpStride * sizeof(int));
-    const size_t oOct = sc.take((size_t)B * A.kpStride);
-    const size_t oRankOf = sc.take(ldsSort ? 8 : (size_t)B * A.kpStride * sizeof(int));
-    const size_t oRec = sc.take((size_t)B * A.kpStride * sizeof(int4));
-    const size_t oDescS = sc.take((size_t)B * A.kpStride * 32);
-    const size_t oCol = sc.take((size_t)B * A.tabLevels * ((size_t)A.g.cols + 1) * sizeof(int));
-    const size_t oCnt = sc.take((size_t)B * std::max(M, 1) * sizeof(int));
-    const size_t oTopk = sc.take((size_t)B * kTopK * std::max(M, 1) * sizeof(uint32_t));
-    const size_t oClaim = sc.take((size_t)B * 3 * A.kpStride * sizeof(int));  // three rotating claim tables per frame
-    const size_t oPerm = sc.take((size_t)B * std::max(M, 1) * sizeof(int));
-    const size_t oDbg = sc.take((size_t)B * 4 * sizeof(int));
-    if (endOff) *endOff = sc.off;
-    int rc = ensure(m, sc.off, hostNeed + 256, err);
+    ProjTables T;
+    T.keys = st.scratch<unsigned long long>(ldsSort ? 1 : B * A.sortCap);
+    T.order = st.scratch<int>(B * stride);
+    T.oct = st.scratch<uint8_t>(B * stride);
+    T.rankOf = st.scratch<int>(ldsSort ? 2 : B * stride);
+    T.rec = st.scratch<int4>(B * stride);
+    T.descS = st.scratch<unsigned long long>(B * stride * 4);
+    T.col = st.scratch<int>(B * A.tabLevels * ((size_t)A.g.cols + 1));
+    T.cnt = st.scratch<int>(B * Mx);
+    T.topk = st.scratch<uint32_t>(B * kTopK * Mx);
+    T.claim = st.scratch<int>(B * 3 * stride);  // three rotating claim tables per frame
+    T.perm = st.scratch<int>(B * Mx);
+    T.dbg = st.scratch<int>(B * 4);
+    return T;
+}
+
+void proj_bind(const Staging& st, const ProjTables& T, ProjArgs& A)
+{
+    A.sortKeys = st.dev(T.keys);
+    A.order = st.dev(T.order);
+    A.octByRank = st.dev(T.oct);
+    A.rankOf = st.dev(T.rankOf);
+    A.rec = st.dev(T.rec);
+    A.descS = st.dev(T.descS);
+    A.colStart = st.dev(T.col);
+    A.cnt = st.dev(T.cnt);
+    A.topk = st.dev(T.topk);
+    A.claimG = st.dev(T.claim);
+    A.perm = st.dev(T.perm);
+    A.dbg = st.dev(T.dbg);
+}
+
+int proj_setup(MatchScratch& m, ProjArgs& A, Carver sc, size_t hostNeed, std::string& err)
+{
+    Staging st;
+    st.c = sc;
+    const ProjTables T = proj_tables(st, A);
+    const int rc = ensure(m, st.device_bytes(), hostNeed + 256, err);
     if (rc != ORBFE_OK) return rc;
-    uint8_t* dp = static_cast<uint8_t*>(m.d);
-    A.sortKeys = reinterpret_cast<unsigned long long*>(dp + oKeys);
-    A.order = reinterpret_cast<int*>(dp + oOrder);
-    A.octByRank = dp + oOct;
-    A.rankOf = reinterpret_cast<int*>(dp + oRankOf);
-    A.rec = reinterpret_cast<int4*>(dp + oRec);
-    A.descS = reinterpret_cast<unsigned long long*>(dp + oDescS);
-    A.colStart = reinterpret_cast<int*>(dp + oCol);
-    A.cnt = reinterpret_cast<int*>(dp + oCnt);
-    A.topk = reinterpret_cast<uint32_t*>(dp + oTopk);
-    A.claimG = reinterpret_cast<int*>(dp + oClaim);
-    A.perm = reinterpret_cast<int*>(dp + oPerm);
-    A.dbg = reinterpret_cast<int*>(dp + oDbg);
+    st.bind(static_cast<uint8_t*>(m.hpin), static_cast<uint8_t*>(m.d));
+    proj_bind(st, T, A);
     return ORBFE_OK;
 }
 
@@ -1191,52 +1203,46 @@ int match_projection_run(MatchScratch& m, hipStream_t s, const orbfe_frame_view*
     for (int i = 0; i < M; i++)
         if (mps[i].in_view && (mps[i].level < 0 || mps[i].level >= F->n_levels)) return ORBFE_ERR_INVALID_ARG;
 
-    // one pinned staging block -> one H2D copy
-    Carver in;
-    const size_t oKp = in.take((size_t)n * sizeof(orbfe_keypoint));
-    const size_t oDesc = in.take((size_t)n * 32);
-    const size_t oMp = in.take((size_t)M * sizeof(orbfe_map_point));
-    const size_t oMpDesc = in.take((size_t)M * 32);
-    const size_t oObs = in.take((size_t)n * sizeof(int));
-    const size_t oSf = in.take((size_t)F->n_levels * sizeof(float));
-    const size_t oN = in.take(sizeof(int));
-    const size_t oMatch = in.take((size_t)n * sizeof(int));
-    const size_t oNM = in.take(sizeof(int));
-    const size_t inBytes = in.off;
-    const size_t hostNeed = inBytes + (size_t)n * sizeof(int) + 64;
-
     ProjArgs A{};
     A.B = 1; A.M = M; A.kpStride = n;
     A.g = GridDesc{F->grid_cols, F->grid_rows, F->min_x, F->min_y, F->grid_inv_w, F->grid_inv_h};
     A.th = th; A.thFar = thFar; A.nnRatio = nnRatio; A.farPoints = farPoints; A.bFactor = th != 1.0;
     A.nLevels = F->n_levels;
-    int rc = proj_setup(m, A, in, hostNeed, err);
+    Staging st;
+    const auto bKp = st.in<orbfe_keypoint>(n);
+    const auto bDesc = st.in<uint8_t>((size_t)n * 32);
+    const auto bMp = st.in<orbfe_map_point>(M);
+    const auto bMpDesc = st.in<uint8_t>((size_t)M * 32);
+    const auto bObs = st.in<int>(n);
+    const auto bSf = st.in<float>(F->n_levels);
+    const auto bN = st.in<int>(1);
+    const auto bMatch = st.out<int>(n);
+    const auto bNM = st.out<int>(1);
+    const ProjTables T = proj::proj_tables(st, A);
+    int rc = reserve(m, st, err);
     if (rc != ORBFE_OK) return rc;
-    uint8_t* hp = static_cast<uint8_t*>(m.hpin);
-    uint8_t* dp = static_cast<uint8_t*>(m.d);
-    memcpy(hp + oKp, F->kp, (size_t)n * sizeof(orbfe_keypoint));
-    memcpy(hp + oDesc, F->desc, (size_t)n * 32);
-    memcpy(hp + oMp, mps, (size_t)M * sizeof(orbfe_map_point));
-    memcpy(hp + oMpDesc, mpDesc, (size_t)M * 32);
-    if (initObs) memcpy(hp + oObs, initObs, (size_t)n * sizeof(int));
-    memcpy(hp + oSf, F->scale_factors, (size_t)F->n_levels * sizeof(float));
-    memcpy(hp + oN, &n, sizeof(int));
-    MCHK(hipMemcpyAsync(dp, hp, oMatch, hipMemcpyHostToDevice, s));
-    A.kp = reinterpret_cast<const orbfe_keypoint*>(dp + oKp);
-    A.desc = dp + oDesc;
-    A.nKp = reinterpret_cast<const int*>(dp + oN);
-    A.mps = reinterpret_cast<const orbfe_map_point*>(dp + oMp);
-    A.mpDesc = dp + oMpDesc;
-    A.initObs = initObs ? reinterpret_cast<const int*>(dp + oObs) : nullptr;
-    A.scaleFactors = reinterpret_cast<const float*>(dp + oSf);
-    A.matchOut = reinterpret_cast<int*>(dp + oMatch);
-    A.nMatches = reinterpret_cast<int*>(dp + oNM);
-    int* hNM = reinterpret_cast<int*>(hp + inBytes);
-    int* hMatch = hNM + 2;
+    proj::proj_bind(st, T, A);
+    st.put(bKp, F->kp);
+    st.put(bDesc, F->desc);
+    st.put(bMp, mps);
+    st.put(bMpDesc, mpDesc);
+    st.put(bObs, initObs);
+    st.put(bSf, F->scale_factors);
+    st.put(bN, &n);
+    if ((rc = upload(st, s, err)) != ORBFE_OK) return rc;
+    A.kp = st.dev(bKp);
+    A.desc = st.dev(bDesc);
+    A.nKp = st.dev(bN);
+    A.mps = st.dev(bMp);
+    A.mpDesc = st.dev(bMpDesc);
+    A.initObs = initObs ? st.dev(bObs) : nullptr;
+    A.scaleFactors = st.dev(bSf);
+    A.matchOut = st.dev(bMatch);
+    A.nMatches = st.dev(bNM);
     rc = proj_launch(s, A, err);
     if (rc != ORBFE_OK) return rc;
-    MCHK(hipMemcpyAsync(hMatch, A.matchOut, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-    MCHK(hipMemcpyAsync(hNM, A.nMatches, sizeof(int), hipMemcpyDeviceToHost, s));
+    if ((rc = fetch_span(st, s, bMatch.off, bMatch.end(), err)) != ORBFE_OK) return rc;
+    if ((rc = fetch_span(st, s, bNM.off, bNM.end(), err)) != ORBFE_OK) return rc;
     MCHK(hipStreamSynchronize(s));
 #ifdef ORBFE_DIAG
     if (getenv("ORBFE_DEBUG_MATCH")) {  // liborbfe_diag.so only (tools/diag_match.py, tools/resolve_stats.py)
@@ -1246,8 +1252,8 @@ int match_projection_run(MatchScratch& m, hipStream_t s, const orbfe_frame_view*
                 dbg[2]);
     }
 #endif
-    memcpy(matchOut, hMatch, (size_t)n * sizeof(int));
-    *nMatches = *hNM;
+    st.get(bMatch, matchOut);
+    *nMatches = *st.res(bNM);
     return ORBFE_OK;
 }
 

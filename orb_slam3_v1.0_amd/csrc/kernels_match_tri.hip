@@ -450,61 +450,57 @@ int match_triangulation_run(MatchScratch& m, hipStream_t s, int G, const int* of
         if (kp2[i].octave < 0 || kp2[i].octave >= nLevels2) return ORBFE_ERR_INVALID_ARG;  // indexes mvScaleFactors
     if (nPos1 == 0) return ORBFE_OK;
 
-    Carver in;
-    const size_t oIdx1 = in.take((size_t)nPos1 * sizeof(int));
-    const size_t oGrp1 = in.take((size_t)nPos1 * sizeof(int));
-    const size_t oOff2 = in.take((size_t)(G + 1) * sizeof(int));
-    const size_t oIdx2 = in.take((size_t)std::max(nPos2, 1) * sizeof(int));
-    const size_t oKp1 = in.take((size_t)n1 * sizeof(orbfe_keypoint));
-    const size_t oKp2 = in.take((size_t)n2 * sizeof(orbfe_keypoint));
-    const size_t oD1 = in.take((size_t)n1 * 32);
-    const size_t oD2 = in.take((size_t)n2 * 32);
-    const size_t oH1 = in.take((size_t)n1);
-    const size_t oH2 = in.take((size_t)n2);
-    const size_t oS1 = in.take((size_t)n1);
-    const size_t oS2 = in.take((size_t)n2);
-    const size_t oSf = in.take((size_t)nLevels2 * sizeof(float));
-    const size_t inBytes = in.off;
-    Carver sc = in;
-    const size_t oMatch = sc.take((size_t)n1 * sizeof(int));
-    const size_t oBin = sc.take((size_t)n1 * sizeof(int));
-    const size_t oNM = sc.take(sizeof(int));
-    int rc = ensure(m, sc.off, inBytes + (size_t)n1 * sizeof(int) + 256, err);
+    Staging st;
+    const auto bIdx1 = st.in<int>(nPos1);
+    const auto bGrp1 = st.in<int>(nPos1);
+    const auto bOff2 = st.in<int>((size_t)G + 1);
+    const auto bIdx2 = st.in<int>(std::max(nPos2, 1));
+    const auto bKp1 = st.in<orbfe_keypoint>(n1);
+    const auto bKp2 = st.in<orbfe_keypoint>(n2);
+    const auto bD1 = st.in<uint8_t>((size_t)n1 * 32);
+    const auto bD2 = st.in<uint8_t>((size_t)n2 * 32);
+    const auto bH1 = st.in<uint8_t>(n1);
+    const auto bH2 = st.in<uint8_t>(n2);
+    const auto bS1 = st.in<uint8_t>(n1);
+    const auto bS2 = st.in<uint8_t>(n2);
+    const auto bSf = st.in<float>(nLevels2);
+    const auto bMatch = st.out<int>(n1);
+    const auto bBin = st.scratch<int>(n1);   // between the two pieces that come down, as the layout always had it
+    const auto bNM = st.out<int>(1);
+    int rc = reserve(m, st, err);
     if (rc != ORBFE_OK) return rc;
-    uint8_t* hp = static_cast<uint8_t*>(m.hpin);
-    uint8_t* dp = static_cast<uint8_t*>(m.d);
-    memcpy(hp + oIdx1, idx1, (size_t)nPos1 * sizeof(int));
-    int* grp = reinterpret_cast<int*>(hp + oGrp1);
+    st.put(bIdx1, idx1);
+    int* grp = st.host(bGrp1);
     for (int g = 0; g < G; g++)
         for (int i = off1[g]; i < off1[g + 1]; i++) grp[i] = g;
-    memcpy(hp + oOff2, off2, (size_t)(G + 1) * sizeof(int));
-    memcpy(hp + oIdx2, idx2, (size_t)nPos2 * sizeof(int));
-    memcpy(hp + oKp1, kp1, (size_t)n1 * sizeof(orbfe_keypoint));
-    memcpy(hp + oKp2, kp2, (size_t)n2 * sizeof(orbfe_keypoint));
-    memcpy(hp + oD1, desc1, (size_t)n1 * 32);
-    memcpy(hp + oD2, desc2, (size_t)n2 * 32);
-    memcpy(hp + oH1, hasMP1, (size_t)n1);
-    memcpy(hp + oH2, hasMP2, (size_t)n2);
-    if (stereo1) memcpy(hp + oS1, stereo1, (size_t)n1);
-    if (stereo2) memcpy(hp + oS2, stereo2, (size_t)n2);
-    memcpy(hp + oSf, sf2, (size_t)nLevels2 * sizeof(float));
-    MCHK(hipMemcpyAsync(dp, hp, inBytes, hipMemcpyHostToDevice, s));
+    st.put(bOff2, off2);
+    st.put(bIdx2, idx2, nPos2);
+    st.put(bKp1, kp1);
+    st.put(bKp2, kp2);
+    st.put(bD1, desc1);
+    st.put(bD2, desc2);
+    st.put(bH1, hasMP1);
+    st.put(bH2, hasMP2);
+    st.put(bS1, stereo1);
+    st.put(bS2, stereo2);
+    st.put(bSf, sf2);
+    if ((rc = upload(st, s, err)) != ORBFE_OK) return rc;
 
     TriArgs A{};
     A.nPos1 = nPos1;
-    A.idx1 = reinterpret_cast<const int*>(dp + oIdx1);
-    A.grp1 = reinterpret_cast<const int*>(dp + oGrp1);
-    A.off2 = reinterpret_cast<const int*>(dp + oOff2);
-    A.idx2 = reinterpret_cast<const int*>(dp + oIdx2);
-    A.kp1 = reinterpret_cast<const orbfe_keypoint*>(dp + oKp1);
-    A.kp2 = reinterpret_cast<const orbfe_keypoint*>(dp + oKp2);
-    A.desc1 = dp + oD1;
-    A.desc2 = dp + oD2;
-    A.hasMP1 = dp + oH1;
-    A.hasMP2 = dp + oH2;
-    A.stereo1 = stereo1 ? dp + oS1 : nullptr;
-    A.stereo2 = stereo2 ? dp + oS2 : nullptr;
-    A.sf2 = reinterpret_cast<const float*>(dp + oSf);
+    A.idx1 = st.dev(bIdx1);
+    A.grp1 = st.dev(bGrp1);
+    A.off2 = st.dev(bOff2);
+    A.idx2 = st.dev(bIdx2);
+    A.kp1 = st.dev(bKp1);
+    A.kp2 = st.dev(bKp2);
+    A.desc1 = st.dev(bD1);
+    A.desc2 = st.dev(bD2);
+    A.hasMP1 = st.dev(bH1);
+    A.hasMP2 = st.dev(bH2);
+    A.stereo1 = stereo1 ? st.dev(bS1) : nullptr;
+    A.stereo2 = stereo2 ? st.dev(bS2) : nullptr;
+    A.sf2 = st.dev(bSf);
     for (int i = 0; i < 9; i++) A.F12[i] = P->f12[i];
     A.epx = P->ep_x;
     A.epy = P->ep_y;
@@ -526,21 +522,19 @@ int match_triangulation_run(MatchScratch& m, hipStream_t s, int G, const int* of
         for (int i = 0; i < n1; i++)
             if (kp1[i].octave < 0 || kp1[i].octave >= kMaxLevels) return ORBFE_ERR_INVALID_ARG;  // indexes mvLevelSigma2
     A.n1 = n1;
-    A.match12 = reinterpret_cast<int*>(dp + oMatch);
-    A.binOf = reinterpret_cast<int*>(dp + oBin);
-    A.nMatches = reinterpret_cast<int*>(dp + oNM);
+    A.match12 = st.dev(bMatch);
+    A.binOf = st.dev(bBin);
+    A.nMatches = st.dev(bNM);
     const dim3 blk(256);
     hipLaunchKernelGGL(fill_kernel, dim3((n1 + 255) / 256), blk, 0, s, A.match12, -1, (size_t)n1);
     hipLaunchKernelGGL(tri_match_kernel, dim3((nPos1 + 63) / 64), dim3(64), 0, s, A);
     hipLaunchKernelGGL(tri_finalize_kernel, dim3(1), blk, 0, s, A);
     MCHK(hipGetLastError());
-    int* hMatch = reinterpret_cast<int*>(hp + inBytes);
-    int* hNM = hMatch + n1;
-    MCHK(hipMemcpyAsync(hMatch, A.match12, (size_t)n1 * sizeof(int), hipMemcpyDeviceToHost, s));
-    MCHK(hipMemcpyAsync(hNM, A.nMatches, sizeof(int), hipMemcpyDeviceToHost, s));
+    if ((rc = fetch_span(st, s, bMatch.off, bMatch.end(), err)) != ORBFE_OK) return rc;
+    if ((rc = fetch_span(st, s, bNM.off, bNM.end(), err)) != ORBFE_OK) return rc;
     MCHK(hipStreamSynchronize(s));
-    memcpy(matches12, hMatch, (size_t)n1 * sizeof(int));
-    *nMatches = *hNM;
+    st.get(bMatch, matches12);
+    *nMatches = *st.res(bNM);
     return ORBFE_OK;
 }
 
@@ -727,32 +721,23 @@ int triangulate_pairs_run(MatchScratch& m, hipStream_t s, const KeyFrameDev* kf1
     for (int p = 0; p < nPairs; p++)
         if (idx1[p] < 0 || idx1[p] >= kf1->n || idx2[p] < 0 || idx2[p] >= kf2->n) return ORBFE_ERR_INVALID_ARG;
     if (nPairs == 0) return ORBFE_OK;
-    Carver in;
-    const size_t oGeo = in.take(sizeof(NewPtNeighbour));
-    const size_t oI1 = in.take((size_t)nPairs * sizeof(int));
-    const size_t oI2 = in.take((size_t)nPairs * sizeof(int));
-    const size_t inBytes = in.off;
-    Carver sc = in;
-    const size_t oVerdict = sc.take((size_t)nPairs);
-    const size_t oX3d = sc.take((size_t)nPairs * 3 * sizeof(float));
-    const size_t outBytes = sc.off - oVerdict;
-    const int rc = ensure(m, sc.off, inBytes + outBytes + 256, err);
+    Staging st;
+    const auto bGeo = st.in<NewPtNeighbour>(1);
+    const auto bI1 = st.in<int>(nPairs);
+    const auto bI2 = st.in<int>(nPairs);
+    const auto bVerdict = st.out<uint8_t>(nPairs);
+    const auto bX3d = st.out<float>((size_t)nPairs * 3);
+    int rc = reserve(m, st, err);
     if (rc != ORBFE_OK) return rc;
-    uint8_t* hp = static_cast<uint8_t*>(m.hpin);
-    uint8_t* dp = static_cast<uint8_t*>(m.d);
-    fill_newpt(*reinterpret_cast<NewPtNeighbour*>(hp + oGeo), kf2, *NP);
-    memcpy(hp + oI1, idx1, (size_t)nPairs * sizeof(int));
-    memcpy(hp + oI2, idx2, (size_t)nPairs * sizeof(int));
-    MCHK(hipMemcpyAsync(dp, hp, inBytes, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(newpoints_kernel, dim3((nPairs + 63) / 64, 1), dim3(64), 0, s, reinterpret_cast<const NewPtNeighbour*>(dp + oGeo),
-                       nPairs, kf1->kp, kf1->sf, reinterpret_cast<const int*>(dp + oI1), reinterpret_cast<const int*>(dp + oI2),
-                       reinterpret_cast<float*>(dp + oX3d), dp + oVerdict);
-    MCHK(hipGetLastError());
-    uint8_t* hOut = hp + inBytes;
-    MCHK(hipMemcpyAsync(hOut, dp + oVerdict, outBytes, hipMemcpyDeviceToHost, s));
-    MCHK(hipStreamSynchronize(s));
-    memcpy(verdict, hOut, (size_t)nPairs);
-    memcpy(x3d, hOut + (oX3d - oVerdict), (size_t)nPairs * 3 * sizeof(float));
+    fill_newpt(*st.host(bGeo), kf2, *NP);
+    st.put(bI1, idx1);
+    st.put(bI2, idx2);
+    if ((rc = upload(st, s, err)) != ORBFE_OK) return rc;
+    hipLaunchKernelGGL(newpoints_kernel, dim3((nPairs + 63) / 64, 1), dim3(64), 0, s, st.dev(bGeo), nPairs, kf1->kp, kf1->sf, st.dev(bI1),
+                       st.dev(bI2), st.dev(bX3d), st.dev(bVerdict));
+    if ((rc = download(st, s, err)) != ORBFE_OK) return rc;
+    st.get(bVerdict, verdict);
+    st.get(bX3d, x3d);
     return ORBFE_OK;
 }
 

@@ -498,35 +498,35 @@ int pose_imu_run(MatchScratch& m, hipStream_t s, const orbfe_pose_inertial_param
 {
     // the unit's blocks (EdgeStaging, match_common.h): up [state | link]; down [state | nInliers | rounds | H]
     EdgeStaging st(n, first, trackDepth);
-    const size_t oState = st.c.take(kImuStateIn * sizeof(float));
-    const size_t oLink = st.c.take(sizeof(orbfe_imu_link));
+    const auto bState = st.in<float>(kImuStateIn);
+    const auto bLink = st.in<orbfe_imu_link>(1);
     st.inputs_done();
-    const size_t oStateOut = st.c.take(kImuState * sizeof(float));
-    const size_t oNInl = st.c.take(sizeof(int));
-    const size_t oRounds = st.c.take(sizeof(PoseImuRounds));
-    const size_t oH = st.c.take(kImuN * kImuN * sizeof(double));
+    const auto bStateOut = st.out<float>(kImuState);
+    const auto bNInl = st.out<int>(1);
+    const auto bRounds = st.out<PoseImuRounds>(1);
+    const auto bH = st.out<double>(kImuN * kImuN);
     int rc = st.stage(m, kp, first, mpIndex, points, trackDepth, err);
     if (rc != ORBFE_OK) return rc;
-    memcpy(st.host<float>(oState), stateIn, kImuStateIn * sizeof(float));
-    memcpy(st.host<orbfe_imu_link>(oLink), link, sizeof(orbfe_imu_link));
-    rc = st.upload(s, oRounds, sizeof(PoseImuRounds), err);
+    st.put(bState, stateIn);
+    st.put(bLink, link);
+    rc = st.upload(s, bRounds, err);
     if (rc != ORBFE_OK) return rc;
 
     PoseImuArgs G;
     fill_args(G, P, invLevelSigma2, nLevels);
-    st.set_args(G, oNInl, oRounds);
-    G.depth = st.dev<const float>(st.oDepth);
-    G.link = st.dev<const orbfe_imu_link>(oLink);
-    G.stateIn = st.dev<const float>(oState);
-    G.stateOut = st.dev<float>(oStateOut);
-    G.Hout = st.dev<double>(oH);
+    st.set_args(G, bNInl, bRounds);
+    G.depth = st.dev(st.bDepth);
+    G.link = st.dev(bLink);
+    G.stateIn = st.dev(bState);
+    G.stateOut = st.dev(bStateOut);
+    G.Hout = st.dev(bH);
     hipLaunchKernelGGL(pose_imu_kernel, dim3(1), dim3(kTreeThreads), 0, s, G);
     rc = st.download(s, outlier, err);
     if (rc != ORBFE_OK) return rc;
-    memcpy(stateOut, st.res<float>(oStateOut), kImuState * sizeof(float));
-    *nInliers = *st.res<int>(oNInl);
-    memcpy(Hout, st.res<double>(oH), kImuN * kImuN * sizeof(double));
-    if (info) fill_inertial_info(info, st.res<PoseImuRounds>(oRounds), st);
+    st.get(bStateOut, stateOut);
+    *nInliers = *st.res(bNInl);
+    st.get(bH, Hout);
+    if (info) fill_inertial_info(info, st.res(bRounds), st);
     return ORBFE_OK;
 }
 

@@ -442,44 +442,44 @@ int pose_prev_run(MatchScratch& m, hipStream_t s, const orbfe_pose_inertial_prev
 {
     // the unit's blocks (EdgeStaging, match_common.h): up [state | link | prior]; down [state | nInliers, accepted | rounds | H30 | Hprior]
     EdgeStaging st(n, first, trackDepth);
-    const size_t oState = st.c.take(kImuStateIn * sizeof(float));
-    const size_t oLink = st.c.take(sizeof(orbfe_imu_link_free));
-    const size_t oPrior = st.c.take(sizeof(orbfe_pose_imu_prior));
+    const auto bState = st.in<float>(kImuStateIn);
+    const auto bLink = st.in<orbfe_imu_link_free>(1);
+    const auto bPrior = st.in<orbfe_pose_imu_prior>(1);
     st.inputs_done();
-    const size_t oStateOut = st.c.take(kImuState * sizeof(float));
-    const size_t oNInl = st.c.take(2 * sizeof(int));
-    const size_t oRounds = st.c.take(sizeof(PrevRoundsOut));
-    const size_t oH = st.c.take(kPrevH * sizeof(double));
-    const size_t oHp = st.c.take(kMargN * kMargN * sizeof(double));
+    const auto bStateOut = st.out<float>(kImuState);
+    const auto bNInl = st.out<int>(2);  // nInliers, accepted
+    const auto bRounds = st.out<PrevRoundsOut>(1);
+    const auto bH = st.out<double>(kPrevH);
+    const auto bHp = st.out<double>(kMargN * kMargN);
     int rc = st.stage(m, kp, first, mpIndex, points, trackDepth, err);
     if (rc != ORBFE_OK) return rc;
-    memcpy(st.host<float>(oState), stateIn, kImuStateIn * sizeof(float));
-    memcpy(st.host<orbfe_imu_link_free>(oLink), link, sizeof(orbfe_imu_link_free));
-    memcpy(st.host<orbfe_pose_imu_prior>(oPrior), prior, sizeof(orbfe_pose_imu_prior));
-    rc = st.upload(s, oRounds, sizeof(PrevRoundsOut), err);
+    st.put(bState, stateIn);
+    st.put(bLink, link);
+    st.put(bPrior, prior);
+    rc = st.upload(s, bRounds, err);
     if (rc != ORBFE_OK) return rc;
 
     PosePrevArgs G;
     fill_args(G, P, invLevelSigma2, nLevels);
-    st.set_args(G, oNInl, oRounds);
-    G.depth = st.dev<const float>(st.oDepth);
-    G.link = st.dev<const orbfe_imu_link_free>(oLink);
-    G.prior = st.dev<const orbfe_pose_imu_prior>(oPrior);
-    G.stateIn = st.dev<const float>(oState);
-    G.stateOut = st.dev<float>(oStateOut);
-    G.H30 = st.dev<double>(oH);
-    G.Hprior = HpriorOut ? st.dev<double>(oHp) : nullptr;
+    st.set_args(G, bNInl, bRounds);
+    G.depth = st.dev(st.bDepth);
+    G.link = st.dev(bLink);
+    G.prior = st.dev(bPrior);
+    G.stateIn = st.dev(bState);
+    G.stateOut = st.dev(bStateOut);
+    G.H30 = st.dev(bH);
+    G.Hprior = HpriorOut ? st.dev(bHp) : nullptr;
     G.accepted = G.nInliers + 1;
     hipLaunchKernelGGL(pose_prev_kernel, dim3(1), dim3(kTreeThreads), 0, s, G);
     rc = st.download(s, outlier, err);
     if (rc != ORBFE_OK) return rc;
-    memcpy(stateOut, st.res<float>(oStateOut), kImuState * sizeof(float));
-    *nInliers = st.res<int>(oNInl)[0];
-    *accepted = st.res<int>(oNInl)[1];
-    memcpy(H30out, st.res<double>(oH), kPrevH * sizeof(double));
-    if (HpriorOut) memcpy(HpriorOut, st.res<double>(oHp), kMargN * kMargN * sizeof(double));
+    st.get(bStateOut, stateOut);
+    *nInliers = st.res(bNInl)[0];
+    *accepted = st.res(bNInl)[1];
+    st.get(bH, H30out);
+    st.get(bHp, HpriorOut);
     if (info) {
-        const PrevRoundsOut* I = st.res<PrevRoundsOut>(oRounds);
+        const PrevRoundsOut* I = st.res(bRounds);
         fill_inertial_info(info, I, st);
         memcpy(info->prior_chi2, I->priorChi2, sizeof I->priorChi2);
         memcpy(info->prior_weight, I->priorWeight, sizeof I->priorWeight);

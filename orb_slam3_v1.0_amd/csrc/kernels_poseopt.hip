@@ -427,31 +427,31 @@ int pose_opt_run(MatchScratch& m, hipStream_t s, const orbfe_pose_opt_params* P,
 
     // the unit's blocks (EdgeStaging, match_common.h): up [pose]; down [pose | nInliers | rounds]
     EdgeStaging st(n, first, nullptr);
-    const size_t oPose = st.c.take(12 * sizeof(float));
+    const auto bPose = st.in<float>(12);
     st.inputs_done();
-    const size_t oPoseOut = st.c.take(12 * sizeof(float));
-    const size_t oNInl = st.c.take(sizeof(int));
-    const size_t oRounds = st.c.take(sizeof(PoseOptRounds));
+    const auto bPoseOut = st.out<float>(12);
+    const auto bNInl = st.out<int>(1);
+    const auto bRounds = st.out<PoseOptRounds>(1);
     int rc = st.stage(m, kp, first, mpIndex, points, nullptr, err);
     if (rc != ORBFE_OK) return rc;
-    float* hPose = st.host<float>(oPose);
+    float* hPose = st.host(bPose);
     for (int i = 0; i < 9; i++) hPose[i] = Rcw[i];
     for (int i = 0; i < 3; i++) hPose[9 + i] = tcw[i];
-    rc = st.upload(s, oRounds, sizeof(PoseOptRounds), err);
+    rc = st.upload(s, bRounds, err);
     if (rc != ORBFE_OK) return rc;
 
     PoseOptArgs G;
     fill_args(G, P, invLevelSigma2, nLevels);
-    st.set_args(G, oNInl, oRounds);
-    G.poseIn = st.dev<const float>(oPose);
-    G.poseOut = st.dev<float>(oPoseOut);
+    st.set_args(G, bNInl, bRounds);
+    G.poseIn = st.dev(bPose);
+    G.poseOut = st.dev(bPoseOut);
     hipLaunchKernelGGL(pose_opt_kernel, dim3(1), dim3(Ne <= 64 ? 64 : kPoseOptThreads), 0, s, G);
     rc = st.download(s, outlier, err);
     if (rc != ORBFE_OK) return rc;
-    const float* pose = st.res<float>(oPoseOut);
-    const PoseOptRounds* I = st.res<PoseOptRounds>(oRounds);
+    const float* pose = st.res(bPoseOut);
+    const PoseOptRounds* I = st.res(bRounds);
     fill_tcw(pose, pose + 9, TcwOut);
-    *nInliers = *st.res<int>(oNInl);
+    *nInliers = *st.res(bNInl);
     if (info) {
         info->rounds_run = I->roundsRun;
         memcpy(info->iterations, I->iterations, sizeof I->iterations);

@@ -3,11 +3,11 @@
 #pragma once
 #include <cstring>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "match.h"
 #include "poseopt_math.h"
+#include "staging.h"
 
 namespace orbfe {
 
@@ -190,11 +190,6 @@ inline int ensure(MatchScratch& m, size_t dBytes, size_t hBytes, std::string& er
     return ORBFE_OK;
 }
 
-struct Carver {
-    size_t off = 0;
-    size_t take(size_t bytes) { const size_t o = off; off = (off + bytes + 255) / 256 * 256; return o; }
-};
-
 // mvKeyPointIndices of MLPnPsolver (src/MLPnPsolver.cpp:67-94) and the edge list of PoseOptimization: the keypoints that have a map
 // point, in keypoint order.  false: a map point index or an octave is out of range.
 inline bool matched_keypoints(int n, const orbfe_keypoint* kp, const int* mpIndex, int nPoints, int nLevels, std::vector<int>& first)
@@ -262,6 +257,42 @@ inline int solver_check_common(const Params* P, const char* entry, const char* b
         if (e_ != hipSuccess) { err = std::string(#call) + ": " + hipGetErrorString(e_); return ORBFE_ERR_HIP; } \
     } while (0)
 
+// ---- a Staging (staging.h) on a handle's arenas ----
+// the arenas for the finished layout, exactly as large as it is
+inline int reserve(MatchScratch& m, Staging& st, std::string& err)
+{
+    if (!st.ordered) { err = "Staging: an input block taken behind scratch or results"; return ORBFE_ERR_INVALID_ARG; }
+    const int rc = ensure(m, st.device_bytes(), st.host_bytes(), err);
+    if (rc != ORBFE_OK) return rc;
+    st.bind(static_cast<uint8_t*>(m.hpin), static_cast<uint8_t*>(m.d));
+    return ORBFE_OK;
+}
+// bytes [from, to) of the inputs go up
+inline int upload_span(const Staging& st, hipStream_t s, size_t from, size_t to, std::string& err)
+{
+    MCHK(hipMemcpyAsync(st.dp + from, st.hp + from, to - from, hipMemcpyHostToDevice, s));
+    return ORBFE_OK;
+}
+// all inputs in one copy
+inline int upload(const Staging& st, hipStream_t s, std::string& err) { return upload_span(st, s, 0, st.inBytes, err); }
+// device bytes [from, to) of the result span come down to their mirror: the copy alone, for a call that brings down several pieces
+inline int fetch_span(const Staging& st, hipStream_t s, size_t from, size_t to, std::string& err)
+{
+    MCHK(hipMemcpyAsync(st.hp + st.mirror(from), st.dp + from, to - from, hipMemcpyDeviceToHost, s));
+    return ORBFE_OK;
+}
+// behind the launches: the launch error, one piece down, synchronise
+inline int download_span(const Staging& st, hipStream_t s, size_t from, size_t to, std::string& err)
+{
+    MCHK(hipGetLastError());
+    const int rc = fetch_span(st, s, from, to, err);
+    if (rc != ORBFE_OK) return rc;
+    MCHK(hipStreamSynchronize(s));
+    return ORBFE_OK;
+}
+// the whole result span
+inline int download(const Staging& st, hipStream_t s, std::string& err) { return download_span(st, s, st.oRes, st.oRes + st.resBytes, err); }
+
 // ---- what the pose solvers' host halves share (S14, S19, S20): host text only, the kernels and their Args stay per unit (r20) ----
 // what a *_begin does after its unit's check: the keypoint bound and the edge list
 inline int pose_edge_list(int nLevels, int n, const orbfe_keypoint* kp, const int* mpIndex, int nPoints, std::vector<int>& first)
@@ -271,81 +302,70 @@ inline int pose_edge_list(int nLevels, int n, const orbfe_keypoint* kp, const in
     return ORBFE_OK;
 }
 
-// The arenas of a host-pointer pose call, one upload and one download:
-//   up [kp | match (edge order index into pts) | pts | depth (with trackDepth) | the unit's input blocks]; device only [edgeIdx];
-//   down [the unit's result blocks | outlier | roundOutlier].
-// The unit takes its own blocks from `c`, and the order of a call is fixed: the constructor, the unit's input takes, inputs_done(),
-// the unit's result takes (the first of them is where the download starts), stage() -- which appends outlier and roundOutlier --,
-// the unit's copies into host(), upload(), set_args() and the unit's own fields, the launch, download(), then res().
-struct EdgeStaging {
-    Carver c;
+// What a host-pointer pose call adds to Staging: the edge-list blocks, the fields the three Args name alike, the rounds record.
+//   up [kp | match (edge order index into pts) | pts | depth (with trackDepth) | the unit's in()]; device only [edgeIdx];
+//   down [the unit's out() | outlier | roundOutlier].
+// The order of a call: the constructor, the unit's in() takes, inputs_done(), the unit's out() takes, stage(), the unit's put()s,
+// upload(), set_args() and the unit's own fields, the launch, download(), then res() / get().
+struct EdgeStaging : Staging {
     const int n, Ne;
-    size_t oKp, oMatch, oPts, oDepth, inBytes = 0, oIdx = 0, oRes = 0, oOutlier = 0, oRoundOut = 0, resBytes = 0;
-    uint8_t *hp = nullptr, *dp = nullptr;
+    Block<orbfe_keypoint> bKp;
+    Block<int> bMatch, bIdx;
+    Block<float> bPts, bDepth;
+    Block<uint8_t> bOutlier, bRoundOut;
 
     EdgeStaging(int n_, const std::vector<int>& first, const float* trackDepth) : n(n_), Ne((int)first.size())
     {
-        oKp = c.take((size_t)n * sizeof(orbfe_keypoint));
-        oMatch = c.take((size_t)n * sizeof(int));
-        oPts = c.take((size_t)Ne * 3 * sizeof(float));
-        oDepth = c.take(trackDepth ? (size_t)Ne * sizeof(float) : 0);
+        bKp = in<orbfe_keypoint>(n);
+        bMatch = in<int>(n);
+        bPts = in<float>((size_t)Ne * 3);
+        bDepth = in<float>(trackDepth ? Ne : 0);
     }
-    void inputs_done()
-    {
-        inBytes = c.off;
-        oIdx = c.take((size_t)n * sizeof(int));
-        oRes = c.off;
-    }
+    void inputs_done() { bIdx = scratch<int>(n); }
     // the arenas for the finished layout, the keypoints and the edge list `first` in the pinned one
     int stage(MatchScratch& m, const orbfe_keypoint* kp, const std::vector<int>& first, const int* mpIndex, const float* points,
               const float* trackDepth, std::string& err)
     {
-        oOutlier = c.take((size_t)n);
-        oRoundOut = c.take((size_t)4 * Ne);
-        resBytes = c.off - oRes;
-        const int rc = ensure(m, c.off + 256, inBytes + resBytes + 256, err);
+        bOutlier = out<uint8_t>(n);
+        bRoundOut = out<uint8_t>((size_t)4 * Ne);
+        const int rc = reserve(m, *this, err);
         if (rc != ORBFE_OK) return rc;
-        hp = static_cast<uint8_t*>(m.hpin);
-        dp = static_cast<uint8_t*>(m.d);
-        if (n > 0) memcpy(hp + oKp, kp, (size_t)n * sizeof(orbfe_keypoint));
-        stage_edge_list(n, first, mpIndex, points, host<int>(oMatch), host<float>(oPts), trackDepth, host<float>(oDepth));
+        put(bKp, kp);
+        stage_edge_list(n, first, mpIndex, points, host(bMatch), host(bPts), trackDepth, host(bDepth));
         return ORBFE_OK;
     }
-    template <class T> T* host(size_t o) const { return reinterpret_cast<T*>(hp + o); }   // an input block, before the upload
-    template <class T> T* dev(size_t o) const { return reinterpret_cast<T*>(dp + o); }
-    template <class T> const T* res(size_t o) const { return reinterpret_cast<const T*>(hp + inBytes + (o - oRes)); }   // after download()
-
-    // the inputs go up and the rounds record (roundsBytes at oRounds) is zeroed
-    int upload(hipStream_t s, size_t oRounds, size_t roundsBytes, std::string& err)
+    // the inputs go up and the rounds record is zeroed
+    template <class R>
+    int upload(hipStream_t s, Block<R> rounds, std::string& err)
     {
-        MCHK(hipMemcpyAsync(dp, hp, inBytes, hipMemcpyHostToDevice, s));
-        MCHK(hipMemsetAsync(dp + oRounds, 0, roundsBytes, s));
+        const int rc = orbfe::upload(*this, s, err);
+        if (rc != ORBFE_OK) return rc;
+        MCHK(hipMemsetAsync(dev(rounds), 0, rounds.bytes(), s));
         return ORBFE_OK;
     }
     // the fields the three Args name alike (dN stays null: one frame of n keypoints)
-    template <class Args>
-    void set_args(Args& G, size_t oNInl, size_t oRounds) const
+    template <class Args, class R>
+    void set_args(Args& G, Block<int> nInl, Block<R> rounds) const
     {
         G.nSingle = n;
         G.kpStride = n;
-        G.kp = dev<const orbfe_keypoint>(oKp);
-        G.match = dev<const int>(oMatch);
+        G.kp = dev(bKp);
+        G.match = dev(bMatch);
         G.nPoints = Ne;
-        G.pts = dev<const float>(oPts);
+        G.pts = dev(bPts);
         G.ptRec = 3;
-        G.outlier = dp + oOutlier;
-        G.nInliers = dev<int>(oNInl);
-        G.edgeIdx = dev<int>(oIdx);
-        G.rounds = dev<typename std::remove_pointer<decltype(Args::rounds)>::type>(oRounds);
-        G.roundOutlier = dp + oRoundOut;
+        G.outlier = dev(bOutlier);
+        G.nInliers = dev(nInl);
+        G.edgeIdx = dev(bIdx);
+        G.rounds = dev(rounds);
+        G.roundOutlier = dev(bRoundOut);
     }
     // behind the launch: the result span comes down in one copy; the keypoints' flags are unpacked
     int download(hipStream_t s, uint8_t* outlier, std::string& err)
     {
-        MCHK(hipGetLastError());
-        MCHK(hipMemcpyAsync(hp + inBytes, dp + oRes, resBytes, hipMemcpyDeviceToHost, s));
-        MCHK(hipStreamSynchronize(s));
-        if (n > 0) memcpy(outlier, res<uint8_t>(oOutlier), (size_t)n);
+        const int rc = orbfe::download(*this, s, err);
+        if (rc != ORBFE_OK) return rc;
+        get(bOutlier, outlier);
         return ORBFE_OK;
     }
     // info->outlier [4][N_e]: the rows of the rounds that ran, zeros below
@@ -353,7 +373,7 @@ struct EdgeStaging {
     {
         if (!out || Ne <= 0) return;
         memset(out, 0, (size_t)4 * Ne);
-        memcpy(out, res<uint8_t>(oRoundOut), (size_t)roundsRun * Ne);
+        get(bRoundOut, out, (size_t)roundsRun * Ne);
     }
 };
 

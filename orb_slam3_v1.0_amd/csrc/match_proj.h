@@ -135,8 +135,19 @@ __device__ __forceinline__ uint32_t make_key32(int dist, int rank) { return ((ui
 
 // host side (kernels_match_proj.hip)
 int proj_dcut(float nnRatio);
-// carve the device scratch after whatever `sc` already holds; sets A's scratch pointers
-int proj_setup(MatchScratch& m, ProjArgs& A, Carver sc, size_t hostNeed, std::string& err, size_t* endOff = nullptr);
+// the device-only tables of one ProjArgs, as blocks behind whatever the call's layout already holds
+struct ProjTables {
+    Block<unsigned long long> keys, descS;
+    Block<int> order, rankOf, col, cnt, claim, perm, dbg;
+    Block<uint8_t> oct;
+    Block<int4> rec;
+    Block<uint32_t> topk;
+};
+// takes the tables from st (and sets A's sortCap, tabLevels, dCut); proj_bind points A at them once st is bound to the arenas
+ProjTables proj_tables(Staging& st, ProjArgs& A);
+void proj_bind(const Staging& st, const ProjTables& T, ProjArgs& A);
+// the device-resident callers: tables behind whatever `sc` already holds, arenas grown, A's scratch pointers set
+int proj_setup(MatchScratch& m, ProjArgs& A, Carver sc, size_t hostNeed, std::string& err);
 // grid only (sortMps == false: cell per keypoint, visit-order sort, level-major storage, column-start tables) or grid +
 // (level, tile) order of the map points
 void proj_prepare_launch(hipStream_t s, const ProjArgs& A, bool sortMps);

@@ -2854,23 +2854,23 @@ void orbfe_covis_destroy(orbfe_covis* g)
 
 }  // extern "C"
 
-// one staged block up, run(device block), synchronised: what the two setters share; the caller holds nothing
+// the inputs of st filled, `bytes` of them up, run() behind them, synchronised: what the two setters share; the caller holds nothing
 template <class Fill, class Run>
-static int covis_staged_call(orbfe_handle* h, size_t bytes, Fill fill, Run run)
+static int covis_staged_call(orbfe_handle* h, Staging& st, size_t bytes, Fill fill, Run run)
 {
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->device));
     std::string err;
     MatchScope scope_(h, h->stream);
     if (scope_.rc != ORBFE_OK) return scope_.rc;
-    int rc = ensure(h->match, bytes, bytes, err);
+    int rc = reserve(h->match, st, err);
     if (rc != ORBFE_OK) {
         h->err = err;
         return rc;
     }
-    fill(static_cast<int*>(h->match.hpin));
-    HIPCHK(h, hipMemcpyAsync(h->match.d, h->match.hpin, bytes, hipMemcpyHostToDevice, h->stream));
-    rc = run(static_cast<const int*>(h->match.d), err);
+    fill();
+    HIPCHK(h, hipMemcpyAsync(st.dp, st.hp, bytes, hipMemcpyHostToDevice, h->stream));
+    rc = run(err);
     if (rc != ORBFE_OK) {
         h->err = err;
         return rc;
@@ -2909,10 +2909,13 @@ int orbfe_covis_set_keyframes(orbfe_handle* h, orbfe_covis* g, int n, const orbf
     }
     if (n == 0) return ORBFE_OK;
     if (ints > (size_t)0x7fffffff) return ORBFE_ERR_INVALID_ARG;  // offsets are ints: split the call
+    Staging stg;
+    const auto bBlk = stg.in<int>(ints);  // [n records | their lists]: the records hold offsets in ints from the start of the block
     return covis_staged_call(
-        h, ints * sizeof(int),
-        [&](int* blk) {
-            CovisStagedKf* st = reinterpret_cast<CovisStagedKf*>(blk);
+        h, stg, bBlk.bytes(),
+        [&]() {
+            int* blk = stg.host(bBlk);
+            CovisStagedKf* st = reinterpret_cast<CovisStagedKf*>(blk);  // the head of the block seen as records
             size_t at = (size_t)n * (sizeof(CovisStagedKf) / sizeof(int));
             for (int i = 0; i < n; i++) {
                 const orbfe_covis_keyframe& r = recs[i];
@@ -2929,7 +2932,7 @@ int orbfe_covis_set_keyframes(orbfe_handle* h, orbfe_covis* g, int n, const orbf
                 at += (size_t)r.n_children;
             }
         },
-        [&](const int* dBlk, std::string& err) { return covis_scatter_keyframes_launch(h->stream, T, n, dBlk, err); });
+        [&](std::string& err) { return covis_scatter_keyframes_launch(h->stream, T, n, stg.dev(bBlk), err); });
 }
 
 int orbfe_covis_set_observations(orbfe_handle* h, orbfe_covis* g, int n, const int* ids, const int* off, const int* kf_slots)
@@ -2949,20 +2952,19 @@ int orbfe_covis_set_observations(orbfe_handle* h, orbfe_covis* g, int n, const i
     if (total > off[0] && !kf_slots) return ORBFE_ERR_INVALID_ARG;
     for (int k = off[0]; k < total; k++)
         if (kf_slots[k] < 0 || kf_slots[k] >= T.kfCap) return ORBFE_ERR_INVALID_ARG;
-    Carver c;
-    const size_t oIds = c.take((size_t)n * sizeof(int));
-    const size_t oOff = c.take((size_t)(n + 1) * sizeof(int));
-    const size_t oSlots = c.take((size_t)std::max(total, 1) * sizeof(int));
+    Staging st;
+    const auto bIds = st.in<int>(n);
+    const auto bOff = st.in<int>((size_t)n + 1);
+    const auto bSlots = st.in<int>(std::max(total, 1));
     return covis_staged_call(
-        h, c.off,
-        [&](int* blk) {
-            memcpy(blk + oIds / sizeof(int), ids, (size_t)n * sizeof(int));
-            memcpy(blk + oOff / sizeof(int), off, (size_t)(n + 1) * sizeof(int));
-            if (total > 0) memcpy(blk + oSlots / sizeof(int), kf_slots, (size_t)total * sizeof(int));
+        h, st, st.inBytes,
+        [&]() {
+            st.put(bIds, ids);
+            st.put(bOff, off);
+            st.put(bSlots, kf_slots, total);
         },
-        [&](const int* dBlk, std::string& err) {
-            return covis_scatter_observations_launch(h->stream, T, n, dBlk + oIds / sizeof(int), dBlk + oOff / sizeof(int),
-                                                     dBlk + oSlots / sizeof(int), err);
+        [&](std::string& err) {
+            return covis_scatter_observations_launch(h->stream, T, n, st.dev(bIds), st.dev(bOff), st.dev(bSlots), err);
         });
 }
 
@@ -3036,45 +3038,40 @@ int orbfe_update_local_map(orbfe_handle* h, const orbfe_local_map_params* p, int
     if (!h || g->h != h || !g->map) return ORBFE_ERR_INVALID_ARG;
     const int stride = std::max(n_votes, 1), M = n_points;
     // in:  [vote ids | n_votes, last_kf]      out: [ids (M) | n_local_points, n_local_kfs | local_kfs | vote ids out]
-    Carver c;
-    const size_t oVotes = c.take((size_t)stride * sizeof(int));
-    const size_t oScal = c.take(2 * sizeof(int));
-    const size_t inBytes = c.off;
-    const size_t oIds = c.take((size_t)M * sizeof(int));
-    const size_t oCounts = c.take(2 * sizeof(int));
-    const size_t oKfs = c.take((size_t)ORBFE_LOCAL_KF_MAX * sizeof(int));
-    const size_t oVotesOut = c.take((size_t)stride * sizeof(int));
+    Staging st;
+    const auto bVotes = st.in<int>(stride);
+    const auto bScal = st.in<int>(2);   // n_votes, last_kf
+    const auto bIds = st.out<int>(M);
+    const auto bCounts = st.out<int>(2);   // n_local_points, n_local_kfs
+    const auto bKfs = st.out<int>(ORBFE_LOCAL_KF_MAX);
+    const auto bVotesOut = st.out<int>(stride);
     return match_call(h, nullptr, [&](hipStream_t s, std::string& e) -> int {
-        int rc = ensure(h->match, c.off, c.off, e);
+        int rc = reserve(h->match, st, e);
         if (rc != ORBFE_OK) return rc;
         rc = covis_scratch(h, g, 1, s, e);
         if (rc != ORBFE_OK) return rc;
-        uint8_t* hp = static_cast<uint8_t*>(h->match.hpin);
-        uint8_t* dp = static_cast<uint8_t*>(h->match.d);
-        if (n_votes > 0) memcpy(hp + oVotes, vote_ids, (size_t)n_votes * sizeof(int));
+        st.put(bVotes, vote_ids, n_votes);
         const int scal[2] = {n_votes, last_kf};
-        memcpy(hp + oScal, scal, sizeof scal);
-        auto& err = e;
-        MCHK(hipMemcpyAsync(dp, hp, inBytes, hipMemcpyHostToDevice, s));
+        st.put(bScal, scal);
+        if ((rc = upload(st, s, e)) != ORBFE_OK) return rc;
         orbfe_local_map_io io{};
         io.struct_size = (int)sizeof io;
-        io.d_vote_ids = reinterpret_cast<const int*>(dp + oVotes);
-        io.d_n_votes = reinterpret_cast<const int*>(dp + oScal);
+        io.d_vote_ids = st.dev(bVotes);
+        io.d_n_votes = st.dev(bScal);
         io.d_last_kf = io.d_n_votes + 1;
-        io.d_ids_out = reinterpret_cast<int*>(dp + oIds);
-        io.d_n_local_points = reinterpret_cast<int*>(dp + oCounts);
+        io.d_ids_out = st.dev(bIds);
+        io.d_n_local_points = st.dev(bCounts);
         io.d_n_local_kfs = io.d_n_local_points + 1;
-        io.d_local_kfs = reinterpret_cast<int*>(dp + oKfs);
-        io.d_vote_ids_out = reinterpret_cast<int*>(dp + oVotesOut);
+        io.d_local_kfs = st.dev(bKfs);
+        io.d_vote_ids_out = st.dev(bVotesOut);
         rc = local_map_launch(s, p, 1, stride, g->T, g->map->dPts, M, &io, g->dStamps, g->dCounters, e);
         if (rc != ORBFE_OK) return rc;
-        MCHK(hipMemcpyAsync(hp + oIds, dp + oIds, c.off - oIds, hipMemcpyDeviceToHost, s));
-        MCHK(hipStreamSynchronize(s));
-        memcpy(ids_out, hp + oIds, (size_t)M * sizeof(int));
-        *n_local_points = reinterpret_cast<const int*>(hp + oCounts)[0];
-        *n_local_kfs = reinterpret_cast<const int*>(hp + oCounts)[1];
-        memcpy(local_kfs, hp + oKfs, (size_t)ORBFE_LOCAL_KF_MAX * sizeof(int));
-        if (vote_ids_out && n_votes > 0) memcpy(vote_ids_out, hp + oVotesOut, (size_t)n_votes * sizeof(int));
+        if ((rc = download(st, s, e)) != ORBFE_OK) return rc;
+        st.get(bIds, ids_out);
+        *n_local_points = st.res(bCounts)[0];
+        *n_local_kfs = st.res(bCounts)[1];
+        st.get(bKfs, local_kfs);
+        st.get(bVotesOut, vote_ids_out, n_votes);
         return ORBFE_OK;
     });
 }
