@@ -1577,6 +1577,102 @@ int orbfe_frame_points_batch_device(orbfe_handle *h, const orbfe_map *map, int b
                                     const int *d_match, const uint8_t *d_outlier, const int *d_n, int *d_out, void *stream);
 
 /* -------------------------------------------------------------------------------------------
+ * Maintaining the resident graph on the device: KeyFrame::UpdateConnections (src/KeyFrame.cc:459-553) with AddConnection (:191-204)
+ * and UpdateBestCovisibles (:206-228), and the graph part of LocalMapping::ProcessNewKeyFrame (src/LocalMapping.cc:338-361).
+ * SPEC DECISION S25; tests/covis_update_ref.py is the normative restatement.  One graph is one map: the
+ * reference's test GetMap() != mpMap (:485) has no counterpart.  Opt-in: a graph on which orbfe_covis_enable_connections was never
+ * called holds and does exactly what it did before.
+ * ---------------------------------------------------------------------------------------- */
+#define ORBFE_COVIS_MAX_CONN_STRIDE 4096
+#define ORBFE_COVIS_STATUS_OK 0          /* the key frame was processed */
+#define ORBFE_COVIS_STATUS_NO_COUNTS 1   /* UpdateConnections: nobody shares a point with it (:493); nothing was written */
+#define ORBFE_COVIS_STATUS_REFUSED 2     /* a row is full; nothing of that key frame (of that call, for add_keyframe) was written */
+
+/* Allocates, per key-frame slot, the full mConnectedKeyFrameWeights as (slot, weight) pairs, up to conn_stride of them, and a count;
+ * all rows empty.  The order of a row is not observable: no output depends on it.  Device memory: 4 * kf_capacity * (2 * conn_stride + 1)
+ * + 12 * conn_stride + 32 bytes (10 000 key frames x 512: 41 MB), released with the graph.  conn_stride in [1, 4096].
+ * ORBFE_ERR_INVALID_ARG: a NULL, a graph of another handle or whose map is gone, conn_stride outside its range, a second call on the
+ * same graph.  Waits for the handle's stream. */
+int orbfe_covis_enable_connections(orbfe_handle *h, orbfe_covis *g, int conn_stride);
+/* Imports connection rows from the host in CSR form: key frame slots[i] is connected to conn_slots[off[i] .. off[i + 1]) with
+ * weights[...]; an empty range clears the row.  Ordering and validation as orbfe_covis_set_observations, nothing is written on a
+ * refusal: ORBFE_ERR_INVALID_ARG for connections not enabled, a slot outside [0, kf_capacity) or named twice, descending offsets, a
+ * range longer than conn_stride, a connected slot outside [0, kf_capacity), a weight < 0.  HOST pointers. */
+int orbfe_covis_set_connections(orbfe_handle *h, orbfe_covis *g, int n, const int *slots, const int *off, const int *conn_slots,
+                                const int *weights);
+/* Reads one key frame back to HOST memory, waiting for the handle's stream: rec receives the scalars (struct_size must be set by the
+ * caller; slot, mn_id, bad, parent, prev, n_features, n_covisible, n_children; its pointers are set to NULL), covisible
+ * ORBFE_COVIS_MAX_COVISIBLE ints (the first n_covisible are the stored head), children child_stride ints (the first n_children),
+ * conn_slots / conn_weights conn_stride ints each and *n_conn (all three may be NULL; required NULL when connections are not
+ * enabled).  ORBFE_ERR_INVALID_ARG: a NULL, a wrong struct_size, a slot outside [0, kf_capacity), a connection pointer on a graph
+ * without connections. */
+int orbfe_covis_get_keyframe(orbfe_handle *h, orbfe_covis *g, int slot, orbfe_covis_keyframe *rec, int *covisible, int *children,
+                             int *conn_slots, int *conn_weights, int *n_conn);
+
+typedef struct orbfe_covis_update_params {
+    int struct_size;          /* sizeof(orbfe_covis_update_params) at the caller's compile time */
+    int min_weight;           /* `th` of KeyFrame.cc:500: 50 in this fork (upstream 15); [1, 2^20] */
+} orbfe_covis_update_params;
+#define ORBFE_COVIS_UPDATE_PARAMS_INIT {(int)sizeof(orbfe_covis_update_params), 50}
+
+/* The outputs of orbfe_covis_update_connections_device: DEVICE pointers, per processed key frame k.  Versioned by struct_size. */
+typedef struct orbfe_covis_update_io {
+    int struct_size;          /* sizeof(orbfe_covis_update_io) at the caller's compile time */
+    int reserved;             /* 0 */
+    int *d_slots;             /* n x conn_stride: mvpOrderedConnectedKeyFrames as slots, the whole list, then -1 */
+    int *d_weights;           /* n x conn_stride: mvOrderedWeights, then 0 */
+    int *d_count;             /* n: the length of the list; 0 unless status is ORBFE_COVIS_STATUS_OK */
+    int *d_status;            /* n: ORBFE_COVIS_STATUS_* */
+} orbfe_covis_update_io;
+
+/* KeyFrame::UpdateConnections for the key frames slots[0 .. n), a HOST array, IN ORDER, each against the graph as the one before left
+ * it (src/Tracking.cc:690-691 is n == 2), in one submission on `stream` with no host synchronisation in between.  flags (HOST):
+ * flags[k] & 1 = mbFirstConnection && mnId != GetInitKFid() (:545).  For key frame s:
+ *   counting   every feature slot of s whose id is inside the map and whose point is not bad adds one for every observer o of that
+ *              point with o != s and o not bad; a point held at two feature slots counts twice.  No counts: status 1, nothing written.
+ *   selection  every counted key frame with count >= min_weight is connected; if there is none, the one with the largest count, among
+ *              equal maxima the lowest mn_id (S25 lets mn_id stand for the address the reference's map iterates by).
+ *   own lists  the connection row of s becomes ALL counted key frames, those below min_weight included (:540, as written); the ordered
+ *              list is the connected ones, weight descending, equal weights in DESCENDING mn_id, then descending slot (S25); its first
+ *              ORBFE_COVIS_MAX_COVISIBLE become the stored head, the whole of it goes to io.
+ *   reciprocal for each connected q (AddConnection): s absent from q's row: inserted; present with the same weight: nothing happens to
+ *              q at all (a stale head stays stale); present with another weight: overwritten.  In the two changing cases q's head
+ *              becomes the first ORBFE_COVIS_MAX_COVISIBLE of q's row ordered as above, without the key frames that are bad NOW.
+ *   parent     with flags & 1: parent(s) = the front of the ordered list, and s is appended to that key frame's children unless there.
+ *   capacity   more than conn_stride counted key frames, a full row of a q where an insert is due, or a full children row: decided
+ *              before anything of that key frame is written; the graph is left untouched by it and status is 2.
+ * Four launches per key frame; results do not depend on the arrival order of any atomic.  Not offered: EraseConnection / SetBadFlag,
+ * mvOrderedWeights as resident state, loop and merge edges.
+ * ORBFE_ERR_INVALID_ARG: a wrong struct_size, a NULL, n < 1, min_weight outside its range, a slot outside [0, kf_capacity), a graph of
+ * another handle, whose map is gone or without connections; all decided before the device is touched. */
+int orbfe_covis_update_connections_device(orbfe_handle *h, const orbfe_covis_update_params *p, orbfe_covis *g, int n, const int *slots,
+                                          const int *flags, const orbfe_covis_update_io *io, void *stream);
+/* The same for ONE key frame with HOST outputs: the same launches, one download, one synchronisation.  ordered_slots /
+ * ordered_weights: conn_stride ints each.  Results equal the device call's with n == 1; ORBFE_ERR_OUT_OF_MEMORY when *status is 2. */
+int orbfe_covis_update_connections(orbfe_handle *h, const orbfe_covis_update_params *p, orbfe_covis *g, int slot, int flag,
+                                   int *ordered_slots, int *ordered_weights, int *count, int *status);
+
+/* The graph part of LocalMapping::ProcessNewKeyFrame.  rec (HOST): the scalars slot, mn_id, bad, parent, prev of the new key frame; its
+ * counts and lists are not read.  d_point_ids (DEVICE): n_features ids, < 0 or outside the map = no point -- the row
+ * orbfe_frame_points_batch_device writes is accepted as it stands.  The call writes the key frame's record (no covisibles, no
+ * children, an empty connection row) and point list, then, as :340-359, for every feature slot whose point is inside the map and
+ * not bad appends the key frame to the point's observation list unless the list holds it already (IsInKeyFrame).  d_added[i]
+ * (n_features ints): 1 where that happened (the host owes UpdateDepth / ComputeDistinctiveDescriptors for that point), 2 where the
+ * point was already in the key frame (:353-356), 0 otherwise.  Of two feature slots with the same point the LOWEST adds and the other
+ * reads 2, whatever the scheduling.  A full observation list (obs_stride) refuses the whole call before anything is written:
+ * *d_status = 2 and d_added all 0; otherwise *d_status = 0.  The map's own records (observations, bad) are not touched: they stay
+ * with orbfe_map_update.  One launch, asynchronous on `stream`; chained on one stream, this call -> orbfe_covis_update_connections_device
+ * -> orbfe_update_local_map_batch_device is the whole path from a tracked frame to the next local map with no host table in between.
+ * ORBFE_ERR_INVALID_ARG: a NULL, a wrong struct_size, a slot outside [0, kf_capacity), mn_id < 0, parent / prev outside
+ * [-1, kf_capacity), n_features outside [0, kf_stride], a graph of another handle or whose map is gone. */
+int orbfe_covis_add_keyframe_device(orbfe_handle *h, orbfe_covis *g, const orbfe_covis_keyframe *rec, const int *d_point_ids,
+                                    int n_features, int *d_added, int *d_status, void *stream);
+/* The same from HOST pointers, for a caller whose new key frame is host objects (include/orbfe_adaptor.hpp): one upload, the same
+ * launch, one download, one synchronisation.  rec->point_ids / rec->n_features are the point row (NULL allowed when n_features == 0);
+ * added: n_features ints.  Results equal the device call's; ORBFE_ERR_OUT_OF_MEMORY when *status is 2. */
+int orbfe_covis_add_keyframe(orbfe_handle *h, orbfe_covis *g, const orbfe_covis_keyframe *rec, int *added, int *status);
+
+/* -------------------------------------------------------------------------------------------
  * Bundle adjustment of the initial map: the line behind orbfe_two_view_reconstruct (src/Tracking.cc:698)
  * ---------------------------------------------------------------------------------------- */
 /* the camera and the constants of Optimizer::GlobalBundleAdjustemnt(map, 20) (src/Optimizer.cc:60-369); versioned by struct_size */

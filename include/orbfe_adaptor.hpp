@@ -713,11 +713,68 @@ public:
         orbfe_detail::check(orbfe_covis_set_observations(h_, g_, (int)ids.size(), ids.data(), off.data(), slots.data()), h_,
                             "orbfe_covis_set_observations");
     }
+    // ---- the graph maintained on the device (SPEC DECISION S25): with these three the mapping thread no longer computes
+    // UpdateConnections on its own pointer graph and pushes the result through UpdateKeyFrames / UpdateObservations ----
+
+    // the full mConnectedKeyFrameWeights per key frame, up to connStride pairs; once per graph
+    void EnableConnections(int connStride)
+    {
+        orbfe_detail::check(orbfe_covis_enable_connections(h_, g_, connStride), h_, "orbfe_covis_enable_connections");
+        connStride_ = connStride;
+    }
+
+    // The graph part of LocalMapping::ProcessNewKeyFrame (src/LocalMapping.cc:338-361) for the new key frame pKF, which takes `slot`:
+    // its record and point list, and the key frame appended to the observation list of each of its points.  -> per feature slot 1: the
+    // observation was added (the caller owes pMP->AddObservation, UpdateDepth and ComputeDistinctiveDescriptors on its own objects),
+    // 2: the point was in the key frame already (:353-356, mlpRecentAddedMapPoints), 0: no point or a bad one.
+    template <class KFPtr, class SlotOf, class IdOf>
+    std::vector<int> AddKeyFrame(const KFPtr& pKF, int slot, SlotOf slotOf, IdOf idOf)
+    {
+        std::vector<int> ids;
+        for (const auto& pMP : pKF->GetMapPointMatches()) ids.push_back(pMP ? idOf(pMP) : -1);
+        const auto slot_or_none = [&](const auto& p) { return p ? slotOf(p) : -1; };
+        orbfe_covis_keyframe r{};
+        r.struct_size = (int)sizeof r;
+        r.slot = slot;
+        r.mn_id = (int)pKF->mnId;
+        r.bad = pKF->isBad() ? 1 : 0;
+        r.parent = slot_or_none(pKF->GetParent());
+        r.prev = slot_or_none(pKF->mPrevKF);
+        r.n_features = (int)ids.size();
+        r.point_ids = ids.data();
+        std::vector<int> added(ids.size() > 0 ? ids.size() : 1, 0);
+        int status = 0;
+        orbfe_detail::check(orbfe_covis_add_keyframe(h_, g_, &r, added.data(), &status), h_, "orbfe_covis_add_keyframe");
+        added.resize(ids.size());
+        return added;
+    }
+
+    // KeyFrame::UpdateConnections (src/KeyFrame.cc:459-553) of the resident key frame pKF.  firstConnection: mbFirstConnection &&
+    // mnId != GetInitKFid() (:545), which the caller knows.  -> mvpOrderedConnectedKeyFrames as slots and mvOrderedWeights, the whole
+    // list: what GetBestCovisibilityKeyFrames(nn) of the current key frame returns to CreateNewMapPoints and SearchInNeighbors is its
+    // first nn.  false: the key frame shares no point with any other (:493) and nothing was written.
+    template <class KFPtr, class SlotOf>
+    bool UpdateConnections(const KFPtr& pKF, SlotOf slotOf, bool firstConnection, std::vector<int>& orderedSlots, std::vector<int>& orderedWeights,
+                           int minWeight = 50)
+    {
+        const orbfe_covis_update_params p{(int)sizeof(orbfe_covis_update_params), minWeight};
+        orderedSlots.assign((size_t)(connStride_ > 0 ? connStride_ : 1), -1);
+        orderedWeights.assign(orderedSlots.size(), 0);
+        int count = 0, status = 0;
+        orbfe_detail::check(orbfe_covis_update_connections(h_, &p, g_, slotOf(pKF), firstConnection ? 1 : 0, orderedSlots.data(),
+                                                           orderedWeights.data(), &count, &status),
+                            h_, "orbfe_covis_update_connections");
+        orderedSlots.resize((size_t)count);
+        orderedWeights.resize((size_t)count);
+        return status == ORBFE_COVIS_STATUS_OK;
+    }
+
     orbfe_covis* get() const { return g_; }
 
 private:
     orbfe_handle* h_;
     orbfe_covis* g_ = nullptr;
+    int connStride_ = 0;
 };
 
 // Tracking::UpdateLocalMap (src/Tracking.cc:1119-1324) on the device, one frame from host pointers (orbfe_update_local_map).  What the

@@ -26,6 +26,7 @@
 #include "match_proj.h"
 #include "keyframe.h"
 #include "local_map.h"
+#include "covis_update.h"
 #include "marginalize.h"
 #include "poseimu_math.h"
 #include "prep.h"
@@ -1112,14 +1113,17 @@ struct orbfe_covis {  // the covisibility graph resident in HBM (orbfe_covis_*, 
     unsigned* dStamps = nullptr;
     int* dCounters = nullptr;
     int scratchBatch = 0;
+    CovisConn C{};  // the connection rows (SPEC DECISION S25): connStride == 0 until orbfe_covis_enable_connections
 };
 
 // the caller holds h->mu (or is the handle's destruction); the handle's stream is idle
 static void covis_free(orbfe_covis* g)
 {
-    void* ptrs[] = {g->T.kf, g->T.covisible, g->T.children, g->T.kfPoints, g->T.obsCount, g->T.obs, g->dStamps, g->dCounters};
+    void* ptrs[] = {g->T.kf, g->T.covisible, g->T.children, g->T.kfPoints, g->T.obsCount, g->T.obs, g->dStamps, g->dCounters,
+                    g->C.slots, g->C.weights, g->C.count, g->C.work};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    g->C = CovisConn{};
     g->T.kf = nullptr;
     g->T.covisible = g->T.children = g->T.kfPoints = g->T.obsCount = g->T.obs = nullptr;
     g->dStamps = nullptr;
@@ -3084,6 +3088,256 @@ int orbfe_frame_points_batch_device(orbfe_handle* h, const orbfe_map* map, int b
     if (!h || map->h != h) return ORBFE_ERR_INVALID_ARG;
     return match_call(h, (hipStream_t)stream_, [&](hipStream_t s, std::string& e) {
         return frame_points_launch(s, batch, kp_stride, n_points, map->cap, map->dPts, d_ids, d_match, d_outlier, d_n, d_out, e);
+    });
+}
+
+// ---- maintaining the resident graph: KeyFrame::UpdateConnections and the graph part of ProcessNewKeyFrame (SPEC DECISION S25) ----
+
+int orbfe_covis_enable_connections(orbfe_handle* h, orbfe_covis* g, int conn_stride)
+{
+    if (!h || !g || g->h != h || !g->map || conn_stride < 1 || conn_stride > kCovisMaxConnStride) return ORBFE_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (g->C.connStride != 0) {
+        h->err = "orbfe_covis_enable_connections: the graph has its connection rows already";
+        return ORBFE_ERR_INVALID_ARG;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    CovisConn C{};
+    C.connStride = conn_stride;
+    const size_t rows = (size_t)g->T.kfCap * conn_stride * sizeof(int);
+    std::string err;
+    int rc = ORBFE_OK;
+    if (hipMalloc(&C.slots, rows) != hipSuccess || hipMalloc(&C.weights, rows) != hipSuccess ||
+        hipMalloc(&C.count, (size_t)g->T.kfCap * sizeof(int)) != hipSuccess ||
+        hipMalloc(&C.work, ((size_t)kWorkHead + 3 * (size_t)conn_stride) * sizeof(int)) != hipSuccess) {
+        err = "orbfe_covis_enable_connections: allocation failed";
+        rc = ORBFE_ERR_OUT_OF_MEMORY;
+    }
+    if (rc == ORBFE_OK) rc = covis_conn_init_launch(h->stream, g->T, C, err);
+    if (rc == ORBFE_OK && hipStreamSynchronize(h->stream) != hipSuccess) {
+        err = "orbfe_covis_enable_connections: hipStreamSynchronize failed";
+        rc = ORBFE_ERR_HIP;
+    }
+    if (rc != ORBFE_OK) {
+        (void)hipGetLastError();
+        void* ptrs[] = {C.slots, C.weights, C.count, C.work};
+        for (void* p : ptrs)
+            if (p) (void)hipFree(p);
+        h->err = err;
+        return rc;
+    }
+    g->C = C;
+    return ORBFE_OK;
+}
+
+int orbfe_covis_set_connections(orbfe_handle* h, orbfe_covis* g, int n, const int* slots, const int* off, const int* conn_slots,
+                                const int* weights)
+{
+    if (!h || !g || g->h != h || !g->map || g->C.connStride == 0 || n < 0 || (n > 0 && (!slots || !off))) return ORBFE_ERR_INVALID_ARG;
+    if (n == 0) return ORBFE_OK;
+    const CovisTables& T = g->T;
+    if (off[0] < 0) return ORBFE_ERR_INVALID_ARG;
+    std::vector<char> seen((size_t)T.kfCap, 0);
+    for (int i = 0; i < n; i++) {
+        if (slots[i] < 0 || slots[i] >= T.kfCap || seen[(size_t)slots[i]] || off[i + 1] < off[i] || off[i + 1] - off[i] > g->C.connStride)
+            return ORBFE_ERR_INVALID_ARG;
+        seen[(size_t)slots[i]] = 1;
+    }
+    const int total = off[n];
+    if (total > off[0] && (!conn_slots || !weights)) return ORBFE_ERR_INVALID_ARG;
+    for (int k = off[0]; k < total; k++)
+        if (conn_slots[k] < 0 || conn_slots[k] >= T.kfCap || weights[k] < 0) return ORBFE_ERR_INVALID_ARG;
+    Staging st;
+    const auto bSlots = st.in<int>(n);
+    const auto bOff = st.in<int>((size_t)n + 1);
+    const auto bConn = st.in<int>(std::max(total, 1));
+    const auto bW = st.in<int>(std::max(total, 1));
+    return covis_staged_call(
+        h, st, st.inBytes,
+        [&]() {
+            st.put(bSlots, slots);
+            st.put(bOff, off);
+            st.put(bConn, conn_slots, total);
+            st.put(bW, weights, total);
+        },
+        [&](std::string& err) {
+            return covis_scatter_connections_launch(h->stream, T, g->C, n, st.dev(bSlots), st.dev(bOff), st.dev(bConn), st.dev(bW), err);
+        });
+}
+
+int orbfe_covis_get_keyframe(orbfe_handle* h, orbfe_covis* g, int slot, orbfe_covis_keyframe* rec, int* covisible, int* children,
+                             int* conn_slots, int* conn_weights, int* n_conn)
+{
+    if (!h || !g || g->h != h || !g->map || !rec || !covisible || !children || slot < 0 || slot >= g->T.kfCap) return ORBFE_ERR_INVALID_ARG;
+    if (rec->struct_size != (int)sizeof(orbfe_covis_keyframe)) {
+        std::lock_guard<std::mutex> lk(h->mu);
+        h->err = "orbfe_covis_keyframe.struct_size does not match this library (rebuild the caller against include/orbfe.h)";
+        return ORBFE_ERR_INVALID_ARG;
+    }
+    const bool wantConn = conn_slots || conn_weights || n_conn;
+    if (wantConn && g->C.connStride == 0) return ORBFE_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIPCHK(h, hipSetDevice(h->device));
+    const CovisTables& T = g->T;
+    hipStream_t s = h->stream;
+    CovisKf k{};
+    const size_t S = (size_t)g->C.connStride;
+    HIPCHK(h, hipMemcpyAsync(&k, T.kf + slot, sizeof k, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(covisible, T.covisible + (size_t)slot * ORBFE_COVIS_MAX_COVISIBLE, ORBFE_COVIS_MAX_COVISIBLE * sizeof(int),
+                             hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(children, T.children + (size_t)slot * T.childStride, (size_t)T.childStride * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (conn_slots) HIPCHK(h, hipMemcpyAsync(conn_slots, g->C.slots + (size_t)slot * S, S * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (conn_weights) HIPCHK(h, hipMemcpyAsync(conn_weights, g->C.weights + (size_t)slot * S, S * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (n_conn) HIPCHK(h, hipMemcpyAsync(n_conn, g->C.count + slot, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    rec->slot = slot;
+    rec->mn_id = k.mnId;
+    rec->bad = k.bad;
+    rec->parent = k.parent;
+    rec->prev = k.prev;
+    rec->n_features = k.nFeatures;
+    rec->n_covisible = k.nCovisible;
+    rec->n_children = k.nChildren;
+    rec->reserved = 0;
+    rec->point_ids = rec->covisible = rec->children = nullptr;
+    return ORBFE_OK;
+}
+
+// what the arguments alone decide, for both forms: no handle is looked at
+static int covis_update_refuse(const orbfe_covis_update_params* p, const orbfe_covis* g, std::string& err)
+{
+    if (!p) return ORBFE_ERR_INVALID_ARG;
+    const int crc = covis_update_check(p, err);
+    if (crc != ORBFE_OK) return crc;
+    if (!g) return ORBFE_ERR_INVALID_ARG;
+    return ORBFE_OK;
+}
+
+int orbfe_covis_update_connections_device(orbfe_handle* h, const orbfe_covis_update_params* p, orbfe_covis* g, int n, const int* slots,
+                                          const int* flags, const orbfe_covis_update_io* io, void* stream_)
+{
+    std::string err;
+    int crc = covis_update_refuse(p, g, err);
+    if (crc == ORBFE_OK && !io) crc = ORBFE_ERR_INVALID_ARG;
+    if (crc == ORBFE_OK && io->struct_size != (int)sizeof(orbfe_covis_update_io)) {
+        err = "orbfe_covis_update_io.struct_size does not match this library (rebuild the caller against include/orbfe.h)";
+        crc = ORBFE_ERR_INVALID_ARG;
+    }
+    if (crc != ORBFE_OK) return refuse(h, crc, err, kKeep);
+    if (n < 1 || !slots || !flags || !io->d_slots || !io->d_weights || !io->d_count || !io->d_status) return ORBFE_ERR_INVALID_ARG;
+    if (!h || g->h != h || !g->map || g->C.connStride == 0) return ORBFE_ERR_INVALID_ARG;
+    for (int k = 0; k < n; k++)
+        if (slots[k] < 0 || slots[k] >= g->T.kfCap) return ORBFE_ERR_INVALID_ARG;
+    return match_call(h, (hipStream_t)stream_, [&](hipStream_t s, std::string& e) -> int {
+        int rc = covis_scratch(h, g, 1, s, e);
+        for (int k = 0; k < n && rc == ORBFE_OK; k++)
+            rc = covis_update_launch(s, g->T, g->C, g->map->dPts, p->min_weight, slots[k], flags[k], io->d_slots + (size_t)k * g->C.connStride,
+                                     io->d_weights + (size_t)k * g->C.connStride, io->d_count + k, io->d_status + k, g->dCounters, e);
+        return rc;
+    });
+}
+
+int orbfe_covis_update_connections(orbfe_handle* h, const orbfe_covis_update_params* p, orbfe_covis* g, int slot, int flag,
+                                   int* ordered_slots, int* ordered_weights, int* count, int* status)
+{
+    std::string err;
+    const int crc = covis_update_refuse(p, g, err);
+    if (crc != ORBFE_OK) return refuse(h, crc, err, kKeep);
+    if (!ordered_slots || !ordered_weights || !count || !status) return ORBFE_ERR_INVALID_ARG;
+    if (!h || g->h != h || !g->map || g->C.connStride == 0 || slot < 0 || slot >= g->T.kfCap) return ORBFE_ERR_INVALID_ARG;
+    const size_t S = (size_t)g->C.connStride;
+    Staging st;
+    const auto bSlots = st.out<int>(S);
+    const auto bWeights = st.out<int>(S);
+    const auto bScal = st.out<int>(2);  // count, status
+    const int rc = match_call(h, nullptr, [&](hipStream_t s, std::string& e) -> int {
+        int r = reserve(h->match, st, e);
+        if (r != ORBFE_OK) return r;
+        if ((r = covis_scratch(h, g, 1, s, e)) != ORBFE_OK) return r;
+        r = covis_update_launch(s, g->T, g->C, g->map->dPts, p->min_weight, slot, flag, st.dev(bSlots), st.dev(bWeights), st.dev(bScal),
+                                st.dev(bScal) + 1, g->dCounters, e);
+        if (r != ORBFE_OK) return r;
+        if ((r = download(st, s, e)) != ORBFE_OK) return r;
+        st.get(bSlots, ordered_slots);
+        st.get(bWeights, ordered_weights);
+        *count = st.res(bScal)[0];
+        *status = st.res(bScal)[1];
+        if (*status == ORBFE_COVIS_STATUS_REFUSED) {
+            e = "orbfe_covis_update_connections: a connection row or a children row is full; the graph was left as it was";
+            return ORBFE_ERR_OUT_OF_MEMORY;
+        }
+        return ORBFE_OK;
+    });
+    return rc;
+}
+
+// what both forms of add_keyframe refuse, in the header's order; k: the record the kernel writes
+static int covis_add_refuse(orbfe_handle* h, const orbfe_covis* g, const orbfe_covis_keyframe* rec, int n_features, CovisKf& k)
+{
+    if (!rec || !g || n_features < 0) return ORBFE_ERR_INVALID_ARG;
+    if (rec->struct_size != (int)sizeof(orbfe_covis_keyframe)) {
+        return refuse(h, ORBFE_ERR_INVALID_ARG,
+                      "orbfe_covis_keyframe.struct_size does not match this library (rebuild the caller against include/orbfe.h)", kKeep);
+    }
+    if (!h || g->h != h || !g->map) return ORBFE_ERR_INVALID_ARG;
+    const CovisTables& T = g->T;
+    auto slot_or_none = [&](int s) { return s >= -1 && s < T.kfCap; };
+    if (rec->slot < 0 || rec->slot >= T.kfCap || rec->mn_id < 0 || !slot_or_none(rec->parent) || !slot_or_none(rec->prev) ||
+        n_features > T.kfStride)
+        return ORBFE_ERR_INVALID_ARG;
+    k = CovisKf{};
+    k.mnId = rec->mn_id;
+    k.bad = rec->bad != 0;
+    k.parent = rec->parent;
+    k.prev = rec->prev;
+    k.nFeatures = n_features;
+    return ORBFE_OK;
+}
+
+int orbfe_covis_add_keyframe(orbfe_handle* h, orbfe_covis* g, const orbfe_covis_keyframe* rec, int* added, int* status)
+{
+    if (!rec || !status || (rec->n_features > 0 && (!rec->point_ids || !added))) return ORBFE_ERR_INVALID_ARG;
+    CovisKf k{};
+    const int crc = covis_add_refuse(h, g, rec, rec->n_features, k);
+    if (crc != ORBFE_OK) return crc;
+    const int n = rec->n_features;
+    Staging st;
+    const auto bIds = st.in<int>(std::max(n, 1));
+    const auto bAdded = st.out<int>(std::max(n, 1));
+    const auto bStatus = st.out<int>(1);
+    return match_call(h, nullptr, [&](hipStream_t s, std::string& e) -> int {
+        int rc = reserve(h->match, st, e);
+        if (rc != ORBFE_OK) return rc;
+        if ((rc = covis_scratch(h, g, 1, s, e)) != ORBFE_OK) return rc;
+        st.put(bIds, rec->point_ids, n);
+        if ((rc = upload(st, s, e)) != ORBFE_OK) return rc;
+        rc = covis_add_keyframe_launch(s, g->T, g->C.connStride ? &g->C : nullptr, g->map->dPts, k, rec->slot, st.dev(bIds), st.dev(bAdded),
+                                       st.dev(bStatus), g->dStamps, e);
+        if (rc != ORBFE_OK) return rc;
+        if ((rc = download(st, s, e)) != ORBFE_OK) return rc;
+        st.get(bAdded, added, n);
+        *status = st.res(bStatus)[0];
+        if (*status == ORBFE_COVIS_STATUS_REFUSED) {
+            e = "orbfe_covis_add_keyframe: an observation list is full; the graph was left as it was";
+            return ORBFE_ERR_OUT_OF_MEMORY;
+        }
+        return ORBFE_OK;
+    });
+}
+
+int orbfe_covis_add_keyframe_device(orbfe_handle* h, orbfe_covis* g, const orbfe_covis_keyframe* rec, const int* d_point_ids, int n_features,
+                                    int* d_added, int* d_status, void* stream_)
+{
+    if (!d_point_ids || !d_added || !d_status) return ORBFE_ERR_INVALID_ARG;
+    CovisKf k{};
+    const int crc = covis_add_refuse(h, g, rec, n_features, k);
+    if (crc != ORBFE_OK) return crc;
+    const CovisTables& T = g->T;
+    return match_call(h, (hipStream_t)stream_, [&](hipStream_t s, std::string& e) -> int {
+        const int rc = covis_scratch(h, g, 1, s, e);
+        if (rc != ORBFE_OK) return rc;
+        return covis_add_keyframe_launch(s, T, g->C.connStride ? &g->C : nullptr, g->map->dPts, k, rec->slot, d_point_ids, d_added, d_status,
+                                         g->dStamps, e);
     });
 }
 

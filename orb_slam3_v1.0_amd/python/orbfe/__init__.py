@@ -482,6 +482,31 @@ class LocalMapIO(C.Structure):
         self.struct_size = C.sizeof(LocalMapIO)
 
 
+# SPEC DECISION S25 (include/orbfe.h), checked against the header by tests/test_covis_update_abi.py
+COVIS_MAX_CONN_STRIDE = 4096
+COVIS_STATUS_OK, COVIS_STATUS_NO_COUNTS, COVIS_STATUS_REFUSED = 0, 1, 2
+
+
+class CovisUpdateParams(C.Structure):
+    """orbfe_covis_update_params: `th` of KeyFrame::UpdateConnections (KeyFrame.cc:500), 50 in this fork."""
+    _fields_ = [("struct_size", C.c_int), ("min_weight", C.c_int)]
+
+    def __init__(self, min_weight=50):
+        super().__init__(C.sizeof(CovisUpdateParams), int(min_weight))
+
+
+COVIS_UPDATE_IO_FIELDS = ("d_slots", "d_weights", "d_count", "d_status")
+
+
+class CovisUpdateIO(C.Structure):
+    """orbfe_covis_update_io: the device pointers of orbfe_covis_update_connections_device (as ints)."""
+    _fields_ = [("struct_size", C.c_int), ("reserved", C.c_int)] + [(k, C.c_void_p) for k in COVIS_UPDATE_IO_FIELDS]
+
+    def __init__(self, **k):
+        super().__init__(**k)
+        self.struct_size = C.sizeof(CovisUpdateIO)
+
+
 class FrameView(C.Structure):
     _fields_ = [("n", C.c_int), ("kp", C.c_void_p), ("desc", C.c_void_p), ("grid_cols", C.c_int),
                 ("grid_rows", C.c_int), ("min_x", C.c_float), ("min_y", C.c_float),
@@ -515,6 +540,8 @@ SYMBOLS = [
     "orbfe_track_inertial_batch_device", "orbfe_track_frame_inertial",
     "orbfe_covis_create", "orbfe_covis_destroy", "orbfe_covis_set_keyframes", "orbfe_covis_set_observations",
     "orbfe_update_local_map_batch_device", "orbfe_update_local_map", "orbfe_frame_points_batch_device",
+    "orbfe_covis_enable_connections", "orbfe_covis_set_connections", "orbfe_covis_get_keyframe",
+    "orbfe_covis_update_connections_device", "orbfe_covis_update_connections", "orbfe_covis_add_keyframe_device", "orbfe_covis_add_keyframe",
     "orbfe_shard_range", "orbfe_pool_create", "orbfe_pool_destroy", "orbfe_pool_size", "orbfe_pool_member",
     "orbfe_pool_member_frames", "orbfe_pool_last_error", "orbfe_pool_extract", "orbfe_pool_enable_track",
     "orbfe_pool_map_update", "orbfe_pool_track",
@@ -677,6 +704,14 @@ def lib():
         L.orbfe_update_local_map_batch_device.argtypes = [vp, C.POINTER(LocalMapParams), ci, ci, vp, ci, C.POINTER(LocalMapIO), vp]
         L.orbfe_update_local_map.argtypes = [vp, C.POINTER(LocalMapParams), ci, vp, ci, vp, ci, vp, C.POINTER(ci), vp, C.POINTER(ci), vp]
         L.orbfe_frame_points_batch_device.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "orbfe_covis_update_connections_device"):  # (as above)
+        L.orbfe_covis_enable_connections.argtypes = [vp, vp, ci]
+        L.orbfe_covis_set_connections.argtypes = [vp, vp, ci, vp, vp, vp, vp]
+        L.orbfe_covis_get_keyframe.argtypes = [vp, vp, ci, C.POINTER(CovisKeyframe), vp, vp, vp, vp, C.POINTER(ci)]
+        L.orbfe_covis_update_connections_device.argtypes = [vp, C.POINTER(CovisUpdateParams), vp, ci, vp, vp, C.POINTER(CovisUpdateIO), vp]
+        L.orbfe_covis_update_connections.argtypes = [vp, C.POINTER(CovisUpdateParams), vp, ci, ci, vp, vp, C.POINTER(ci), C.POINTER(ci)]
+        L.orbfe_covis_add_keyframe_device.argtypes = [vp, vp, C.POINTER(CovisKeyframe), vp, ci, vp, vp, vp]
+        L.orbfe_covis_add_keyframe.argtypes = [vp, vp, C.POINTER(CovisKeyframe), vp, C.POINTER(ci)]
     if hasattr(L, "orbfe_initial_bundle_adjustment"):  # (as above)
         L.orbfe_initial_bundle_adjustment.argtypes = [vp, C.POINTER(InitialBAParams), ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                                       C.POINTER(InitialBAInfo)]
@@ -931,6 +966,68 @@ class Covisibility:
         assert len(off) == len(ids) + 1
         self.e._chk(self.L.orbfe_covis_set_observations(self.e.h, self.h, len(ids), _p(ids), _p(off), _p(kf_slots) if len(kf_slots) else None),
                     "orbfe_covis_set_observations")
+
+    # ---- SPEC DECISION S25: the graph maintained on the device ----
+    conn_stride = 0
+
+    def enable_connections(self, conn_stride):
+        """orbfe_covis_enable_connections: the full mConnectedKeyFrameWeights per key frame, up to conn_stride pairs"""
+        self.e._chk(self.L.orbfe_covis_enable_connections(self.e.h, self.h, int(conn_stride)), "orbfe_covis_enable_connections")
+        self.conn_stride = int(conn_stride)
+
+    def set_connections(self, slots, off, conn_slots, weights):
+        slots, off, conn_slots, weights = (np.ascontiguousarray(a, np.int32) for a in (slots, off, conn_slots, weights))
+        assert len(off) == len(slots) + 1 and len(conn_slots) == len(weights)
+        self.e._chk(self.L.orbfe_covis_set_connections(self.e.h, self.h, len(slots), _p(slots), _p(off), _p(conn_slots) if len(conn_slots) else None,
+                                                       _p(weights) if len(weights) else None), "orbfe_covis_set_connections")
+
+    def get_keyframe(self, slot):
+        """orbfe_covis_get_keyframe -> dict(mn_id, bad, parent, prev, n_features, covisible, children, conn {slot: weight}); the row's
+        order is not observable, so it comes back as a dict (None when connections are not enabled)"""
+        rec = CovisKeyframe()
+        cov, kids = np.zeros(COVIS_MAX_COVISIBLE, np.int32), np.zeros(self.child_stride, np.int32)
+        cs, cw, nc = np.zeros(max(self.conn_stride, 1), np.int32), np.zeros(max(self.conn_stride, 1), np.int32), C.c_int(0)
+        on = self.conn_stride > 0
+        self.e._chk(self.L.orbfe_covis_get_keyframe(self.e.h, self.h, int(slot), C.byref(rec), _p(cov), _p(kids), _p(cs) if on else None,
+                                                    _p(cw) if on else None, C.byref(nc) if on else None), "orbfe_covis_get_keyframe")
+        conn = None
+        if on:
+            assert len(set(cs[:nc.value].tolist())) == nc.value, "a key frame is named twice in a connection row"
+            conn = dict(zip(cs[:nc.value].tolist(), cw[:nc.value].tolist()))
+        return dict(mn_id=rec.mn_id, bad=rec.bad, parent=rec.parent, prev=rec.prev, n_features=rec.n_features,
+                    covisible=cov[:rec.n_covisible].tolist(), children=kids[:rec.n_children].tolist(), conn=conn)
+
+    def update_connections(self, slot, flag=0, params=None):
+        """orbfe_covis_update_connections: one key frame -> dict(slots, weights, count, status); raises on status 2 (OrbfeError)"""
+        S = self.conn_stride
+        sl, w, n, st = np.zeros(max(S, 1), np.int32), np.zeros(max(S, 1), np.int32), C.c_int(0), C.c_int(0)
+        params = params or CovisUpdateParams()
+        self.e._chk(self.L.orbfe_covis_update_connections(self.e.h, C.byref(params), self.h, int(slot), int(flag), _p(sl), _p(w), C.byref(n),
+                                                          C.byref(st)), "orbfe_covis_update_connections")
+        return dict(slots=sl, weights=w, count=n.value, status=st.value)
+
+    def update_connections_device(self, slots, flags, io, params=None, stream=None):
+        """orbfe_covis_update_connections_device: slots / flags are HOST arrays, io a CovisUpdateIO of raw device pointers"""
+        slots, flags = np.ascontiguousarray(slots, np.int32), np.ascontiguousarray(flags, np.int32)
+        assert len(slots) == len(flags)
+        params = params or CovisUpdateParams()
+        self.e._chk(self.L.orbfe_covis_update_connections_device(self.e.h, C.byref(params), self.h, len(slots), _p(slots), _p(flags), C.byref(io),
+                                                                 stream), "orbfe_covis_update_connections_device")
+
+    def add_keyframe_device(self, slot, mn_id, d_point_ids_ptr, n_features, d_added_ptr, d_status_ptr, bad=0, parent=-1, prev=-1, stream=None):
+        """orbfe_covis_add_keyframe_device: the graph part of LocalMapping::ProcessNewKeyFrame; raw device pointers"""
+        rec = CovisKeyframe(slot=int(slot), mn_id=int(mn_id), bad=int(bad), parent=int(parent), prev=int(prev))
+        self.e._chk(self.L.orbfe_covis_add_keyframe_device(self.e.h, self.h, C.byref(rec), d_point_ids_ptr, int(n_features), d_added_ptr,
+                                                           d_status_ptr, stream), "orbfe_covis_add_keyframe_device")
+
+    def add_keyframe(self, slot, mn_id, point_ids, bad=0, parent=-1, prev=-1):
+        """orbfe_covis_add_keyframe: the same from a host array -> dict(added, status); raises on status 2 (OrbfeError)"""
+        ids = np.ascontiguousarray(point_ids, np.int32)
+        added, st = np.zeros(max(len(ids), 1), np.int32), C.c_int(0)
+        rec = CovisKeyframe(slot=int(slot), mn_id=int(mn_id), bad=int(bad), parent=int(parent), prev=int(prev), n_features=len(ids),
+                            point_ids=ids.ctypes.data if len(ids) else None)
+        self.e._chk(self.L.orbfe_covis_add_keyframe(self.e.h, self.h, C.byref(rec), _p(added), C.byref(st)), "orbfe_covis_add_keyframe")
+        return dict(added=added[:len(ids)], status=st.value)
 
     def close(self):
         if getattr(self, "h", None):
