@@ -1673,6 +1673,101 @@ int orbfe_covis_add_keyframe_device(orbfe_handle *h, orbfe_covis *g, const orbfe
 int orbfe_covis_add_keyframe(orbfe_handle *h, orbfe_covis *g, const orbfe_covis_keyframe *rec, int *added, int *status);
 
 /* -------------------------------------------------------------------------------------------
+ * Refreshing map points from the resident graph: MapPoint::UpdateDepth (src/MapPoint.cc:440-474) and
+ * MapPoint::ComputeDistinctiveDescriptors (:343-417), the two functions the mapping thread runs on every point a key frame adds or
+ * touches (src/LocalMapping.cc:350-351, :718-720, :866-867) and every Optimizer entry point ends in.  They write the records every
+ * per-frame chain reads: min_distance / max_distance (the frustum gate, PredictScale) and the 32-byte descriptor (SearchByProjection).
+ * SPEC DECISION S26; tests/point_refresh_ref.py is the normative restatement.  Monocular key frames: one
+ * observation per (point, key frame), no rightIndex.  Opt-in: a graph on which orbfe_covis_enable_refresh was never called holds and
+ * does exactly what it did before.
+ * ---------------------------------------------------------------------------------------- */
+#define ORBFE_REFRESH_MAX_LEVELS 32
+#define ORBFE_REFRESH_DEPTH 1            /* `what` bit 0: UpdateDepth; status bit 0: the distances were written */
+#define ORBFE_REFRESH_DESCRIPTOR 2       /* `what` bit 1: ComputeDistinctiveDescriptors; status bit 1: the descriptor was written */
+
+/* Allocates, all rows empty: per key-frame slot kf_stride descriptors of 32 bytes, kf_stride octaves of one byte, a feature count and
+ * the camera centre GetTranslationInverse() (3 floats); per point of the map obs_stride feature indices parallel to the observation
+ * list (all -1, the reference's leftIndex == -1) and mpRefKF as a slot (-1: none); per graph mvScaleFactors[0 .. n_levels) from
+ * scale_factors (HOST).  Device memory: kf_capacity * (33 * kf_stride + 16) + 4 * capacity * (obs_stride + 1) + 128 bytes, released
+ * with the graph (10 000 key frames x 3000 slots: 0.99 GB, 0.96 GB of it descriptors; a map of 200 000 points x 64 observations adds
+ * 51 MB), plus 4 bytes per entry of the longest list a refresh call was given.  n_levels in [1, 32]; kf_capacity * kf_stride must
+ * stay below 2^31.  ORBFE_ERR_INVALID_ARG: a NULL, a graph of another handle or whose map is gone, n_levels or the product outside
+ * their range, a second call on the same graph.  Waits for the handle's stream. */
+int orbfe_covis_enable_refresh(orbfe_handle *h, orbfe_covis *g, int n_levels, const float *scale_factors);
+/* The setters: ordering and validation as orbfe_covis_set_observations (one staged block, one upload, on the handle's stream, return
+ * when the tables are updated; everything validated on the host first, nothing written on a refusal).  All of them refuse a graph
+ * without refresh state with ORBFE_ERR_INVALID_ARG.
+ * set_features: the n keypoints (only `octave` is read) and n x 32 descriptor bytes of key frame `slot`, HOST pointers; n in
+ *   [0, kf_stride], every octave in [0, n_levels), slot in [0, kf_capacity).  The count is stored: an index at or beyond it names no
+ *   feature. */
+int orbfe_covis_set_features(orbfe_handle *h, orbfe_covis *g, int slot, int n, const orbfe_keypoint *kp, const uint8_t *desc);
+/* The same from the DEVICE arrays an extraction left in HBM, asynchronous on `stream` (NULL == the handle's stream): a tracked frame
+ * promoted to key frame never leaves the device.  Octaves are clamped to [0, n_levels) on the device, not trusted. */
+int orbfe_covis_set_features_device(orbfe_handle *h, orbfe_covis *g, int slot, const orbfe_keypoint *d_kp, const uint8_t *d_desc, int n,
+                                    void *stream);
+/* Camera centres (GetTranslationInverse(), 3 floats each, finite) of n key frames, HOST pointers; the mapping thread calls it after a
+ * bundle adjustment.  ORBFE_ERR_INVALID_ARG: a slot outside [0, kf_capacity) or named twice, a non-finite value. */
+int orbfe_covis_set_centres(orbfe_handle *h, orbfe_covis *g, int n, const int *slots, const float *twc);
+/* orbfe_covis_set_observations plus the feature index of each observation, feat_idx[k] in [-1, kf_stride) parallel to kf_slots.  On a
+ * graph with refresh state orbfe_covis_set_observations itself keeps working and writes -1 for every index of the points it names. */
+int orbfe_covis_set_observations_indexed(orbfe_handle *h, orbfe_covis *g, int n, const int *ids, const int *off, const int *kf_slots,
+                                         const int *feat_idx);
+/* mpRefKF of n points as slots in [-1, kf_capacity); ids inside the map, none named twice. */
+int orbfe_covis_set_ref_keyframes(orbfe_handle *h, orbfe_covis *g, int n, const int *ids, const int *ref_slots);
+/* On a graph with refresh state orbfe_covis_add_keyframe_device / orbfe_covis_add_keyframe run one more launch behind their own: every
+ * feature slot i with d_added[i] == 1 stores i as the index of the observation that was just appended.  The key frame's features are
+ * set with set_features* before the refresh call; the order relative to add_keyframe does not matter.
+ *
+ * Reads one point back to HOST memory, waiting for the handle's stream: *n_obs, kf_slots / feat_idx (obs_stride ints each, the first
+ * *n_obs are the list), *ref_slot, and the record and the 32 descriptor bytes of the graph's map (point / desc, either may be NULL).
+ * ORBFE_ERR_INVALID_ARG: a NULL among the first four outputs, an id outside the map, a graph without refresh state. */
+int orbfe_covis_get_point(orbfe_handle *h, orbfe_covis *g, int id, int *n_obs, int *kf_slots, int *feat_idx, int *ref_slot,
+                          orbfe_world_point *point, uint8_t *desc);
+
+/* The outputs of orbfe_covis_refresh_points_device: DEVICE pointers, one element per list entry, any of them may be NULL.  Every
+ * entry of the list gets every output: one that was not processed, or whose bit is clear, reads status 0, distances 0.0f, slot /
+ * index / median -1.  Versioned by struct_size. */
+typedef struct orbfe_refresh_io {
+    int struct_size;          /* sizeof(orbfe_refresh_io) at the caller's compile time */
+    int reserved;             /* 0 */
+    int *d_status;            /* bit 0: the distances were written; bit 1: the descriptor was written; 0: nothing happened */
+    float *d_min_distance;    /* mfMinDistance as written */
+    float *d_max_distance;    /* mfMaxDistance as written */
+    int *d_best_slot;         /* the observer the descriptor came from */
+    int *d_best_index;        /* its feature */
+    int *d_best_median;       /* BestMedian (:408) */
+} orbfe_refresh_io;
+
+/* UpdateDepth (what & 1) and / or ComputeDistinctiveDescriptors (what & 2) for the points d_ids[0 .. n), a DEVICE list; an id outside
+ * the map is no point.  d_select (DEVICE, may be NULL): entry i is processed only if d_select[i] == select_value -- the point row
+ * given to orbfe_covis_add_keyframe_device with its d_added and 1 is LocalMapping::ProcessNewKeyFrame's :350-351 with no host in
+ * between.  The call WRITES min_distance / max_distance and the descriptor of the graph's own orbfe_map records; bad, observations,
+ * skip and the position are not touched.  The caller orders it against the chains that read the map exactly as it orders
+ * orbfe_map_update: on the stream of those chains, or behind an event.  Asynchronous on `stream`, no host synchronisation, two
+ * launches, no allocation beyond a list of n ints kept with the graph that grows to the largest n seen.
+ *   both        a point whose map record is bad or whose observation list is empty is left alone (:352, :357, :448, :455).
+ *   descriptor  collected: the observers that are not bad (:366) and whose index is not -1 (:370) and names a feature of the key frame
+ *               (below the count of its set_features); none collected: nothing written.  With N collected, row i is the N Hamming
+ *               distances from i, its own 0 included; its median is the element at position (size_t)(0.5 * (N - 1)) of the sorted
+ *               row; the descriptor with the least median is copied to the map.  Among equal medians the observer with the lowest
+ *               mn_id wins (S26: mn_id stands for the address the reference's map iterates by), then the earlier in the list.
+ *   depth       r = the point's reference slot; dist = sqrt((x x + y y) + z z) of Pos - centre[r] in binary32, every operation
+ *               rounded once; max = dist * sf[level], min = max / sf[n_levels - 1]; level = the octave of r's feature at the index
+ *               of r's observation.  r not among the observers: index 0, as written (:461 default-constructs).  r is not tested for
+ *               bad.  Undefined in the reference, here nothing written and bit 0 clear: r outside [0, kf_capacity), an index of -1,
+ *               an index at or beyond r's feature count.
+ * An id named twice gets the same values written twice.  Results do not depend on n, on the order of the list or on the arrival
+ * order of any atomic.  Points with at most 64 observers take one wave each; the others a block each in the second launch.
+ * ORBFE_ERR_INVALID_ARG: a NULL (h, g, d_ids, io), a wrong struct_size, n < 1, what outside 1..3, a graph of another handle, whose map
+ * is gone or without refresh state; all decided before the device is touched. */
+int orbfe_covis_refresh_points_device(orbfe_handle *h, orbfe_covis *g, int n, const int *d_ids, const int *d_select, int select_value,
+                                      int what, const orbfe_refresh_io *io, void *stream);
+/* The same from a HOST list with HOST outputs (n elements each, any may be NULL): one upload, the same launches, one download, one
+ * synchronisation.  Results equal the device call's. */
+int orbfe_covis_refresh_points(orbfe_handle *h, orbfe_covis *g, int n, const int *ids, int what, int *status, float *min_distance,
+                               float *max_distance, int *best_slot, int *best_index, int *best_median);
+
+/* -------------------------------------------------------------------------------------------
  * Bundle adjustment of the initial map: the line behind orbfe_two_view_reconstruct (src/Tracking.cc:698)
  * ---------------------------------------------------------------------------------------- */
 /* the camera and the constants of Optimizer::GlobalBundleAdjustemnt(map, 20) (src/Optimizer.cc:60-369); versioned by struct_size */

@@ -769,6 +769,90 @@ public:
         return status == ORBFE_COVIS_STATUS_OK;
     }
 
+    // ---- map points refreshed from the graph (SPEC DECISION S26): MapPoint::UpdateDepth and ComputeDistinctiveDescriptors run where the
+    // map records live, so min_distance / max_distance and the descriptor every per-frame chain reads no longer wait for a host push.
+    // EraseObservation, Replace, SetBadFlag and a changed mpRefKF still reach the graph through the setters below. ----
+
+    // descriptors, octaves and centre per key frame, feature index per observation, mpRefKF per point; scaleFactors = mvScaleFactors
+    void EnableRefresh(const std::vector<float>& scaleFactors)
+    {
+        orbfe_detail::check(orbfe_covis_enable_refresh(h_, g_, (int)scaleFactors.size(), scaleFactors.data()), h_, "orbfe_covis_enable_refresh");
+    }
+
+    // mvKeysUn[i].octave and mDescriptors.row(i) of the key frame at `slot`: octaves.size() features, 32 descriptor bytes each
+    void SetFeatures(int slot, const std::vector<int>& octaves, const std::vector<uint8_t>& descriptors)
+    {
+        std::vector<orbfe_keypoint> kp(octaves.size() > 0 ? octaves.size() : 1, orbfe_keypoint{});
+        for (size_t i = 0; i < octaves.size(); i++) kp[i].octave = octaves[i];
+        if (descriptors.size() != octaves.size() * ORBFE_DESC_BYTES) orbfe_detail::check(ORBFE_ERR_INVALID_ARG, h_, "SetFeatures");
+        orbfe_detail::check(orbfe_covis_set_features(h_, g_, slot, (int)octaves.size(), kp.data(), descriptors.data()),
+                            h_, "orbfe_covis_set_features");
+    }
+
+    // GetTranslationInverse() of the key frames at `slots`, 3 floats each: after every bundle adjustment that moved them
+    void SetCentres(const std::vector<int>& slots, const std::vector<float>& twc)
+    {
+        if (twc.size() != slots.size() * 3) orbfe_detail::check(ORBFE_ERR_INVALID_ARG, h_, "SetCentres");
+        orbfe_detail::check(orbfe_covis_set_centres(h_, g_, (int)slots.size(), slots.data(), twc.data()), h_, "orbfe_covis_set_centres");
+    }
+
+    // GetObservations() of every point of the list with get<0> of each tuple, the leftIndex; an observing key frame that is not
+    // resident is left out.  On a graph with refresh state this replaces UpdateObservations, which writes indices of -1.
+    template <class MPPtr, class IdOf, class SlotOf>
+    void SetObservations(const std::vector<MPPtr>& vpMPs, IdOf idOf, SlotOf slotOf)
+    {
+        std::vector<int> ids, off(1, 0), slots, idx;
+        for (const auto& pMP : vpMPs) {
+            ids.push_back(idOf(pMP));
+            for (const auto& ob : pMP->GetObservations()) {
+                const int s = ob.first ? slotOf(ob.first) : -1;
+                if (s < 0) continue;
+                slots.push_back(s);
+                idx.push_back(std::get<0>(ob.second));
+            }
+            off.push_back((int)slots.size());
+        }
+        orbfe_detail::check(orbfe_covis_set_observations_indexed(h_, g_, (int)ids.size(), ids.data(), off.data(), slots.data(), idx.data()), h_,
+                            "orbfe_covis_set_observations_indexed");
+    }
+
+    // GetReferenceKeyFrame() of every point of the list; none, or one that is not resident: -1
+    template <class MPPtr, class IdOf, class SlotOf>
+    void SetReferenceKeyFrames(const std::vector<MPPtr>& vpMPs, IdOf idOf, SlotOf slotOf)
+    {
+        std::vector<int> ids, refs;
+        for (const auto& pMP : vpMPs) {
+            ids.push_back(idOf(pMP));
+            const auto pRef = pMP->GetReferenceKeyFrame();
+            refs.push_back(pRef ? slotOf(pRef) : -1);
+        }
+        orbfe_detail::check(orbfe_covis_set_ref_keyframes(h_, g_, (int)ids.size(), ids.data(), refs.data()), h_, "orbfe_covis_set_ref_keyframes");
+    }
+
+    struct Refreshed {
+        std::vector<int> status;                     // bit 0: the distances were written, bit 1: the descriptor
+        std::vector<float> minDistance, maxDistance; // mfMinDistance / mfMaxDistance as written
+        std::vector<int> bestSlot, bestIndex, bestMedian;
+    };
+    // UpdateDepth (what & 1) and ComputeDistinctiveDescriptors (what & 2) of the points `ids`, written into the resident map's records;
+    // the caller orders it against the chains that read the map as it orders ResidentMap::Update
+    Refreshed RefreshPoints(const std::vector<int>& ids, int what = ORBFE_REFRESH_DEPTH | ORBFE_REFRESH_DESCRIPTOR)
+    {
+        Refreshed r;
+        const size_t n = ids.size();
+        r.status.assign(n, 0);
+        r.minDistance.assign(n, 0.0f);
+        r.maxDistance.assign(n, 0.0f);
+        r.bestSlot.assign(n, -1);
+        r.bestIndex.assign(n, -1);
+        r.bestMedian.assign(n, -1);
+        if (n == 0) return r;
+        orbfe_detail::check(orbfe_covis_refresh_points(h_, g_, (int)n, ids.data(), what, r.status.data(), r.minDistance.data(), r.maxDistance.data(),
+                                                       r.bestSlot.data(), r.bestIndex.data(), r.bestMedian.data()),
+                            h_, "orbfe_covis_refresh_points");
+        return r;
+    }
+
     orbfe_covis* get() const { return g_; }
 
 private:

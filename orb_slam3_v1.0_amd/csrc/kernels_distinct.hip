@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "distinct_select.h"
 #include "match_common.h"
 
 namespace orbfe {
@@ -24,22 +25,19 @@ __global__ __launch_bounds__(256) void distinct_kernel(int nRows, const int* __r
     const int s = rowSet[r];
     const int lo = setOff[s], hi = setOff[s + 1];
     const int N = hi - lo, i = r - lo;
-    const int k = (int)(size_t)(0.5 * (double)(N - 1));
+    const int k = distinct_median_position(N);
     unsigned long long d4[4];
     const unsigned long long* dp = reinterpret_cast<const unsigned long long*>(desc + (size_t)r * 32);
     d4[0] = dp[0]; d4[1] = dp[1]; d4[2] = dp[2]; d4[3] = dp[3];
-    int vlo = 0, vhi = 256;  // smallest v with #{j : dist(i, j) <= v} >= k + 1
-    while (vlo < vhi) {
-        const int mid = (vlo + vhi) >> 1;
+    const int median = distinct_kth_distance(k, [&](int v) {   // recomputing the popcounts from L2-resident descriptors
         int c = 0;
         for (int j = lo; j < hi; j++) {
             const int dist = j == r ? 0 : hamming256(reinterpret_cast<const uint2*>(desc + (size_t)j * 32), d4);
-            c += dist <= mid;
+            c += dist <= v;
         }
-        if (c >= k + 1) vhi = mid;
-        else vlo = mid + 1;
-    }
-    atomicMin(&best[s], ((unsigned int)vlo << 20) | (unsigned int)i);
+        return c;
+    });
+    atomicMin(&best[s], distinct_pack(median, i));
 }
 
 }  // namespace
@@ -51,7 +49,7 @@ int distinctive_run(MatchScratch& m, hipStream_t s, int nSets, const int* setOff
     const int nRows = setOff[nSets];
     for (int q = 0; q < nSets; q++) {
         const int n = setOff[q + 1] - setOff[q];
-        if (n < 0 || n >= (1 << 20)) return ORBFE_ERR_INVALID_ARG;
+        if (n < 0 || n >= (1 << kDistinctIndexBits)) return ORBFE_ERR_INVALID_ARG;
         bestIdx[q] = -1;
         if (bestMedian) bestMedian[q] = 0;
     }
@@ -76,8 +74,8 @@ int distinctive_run(MatchScratch& m, hipStream_t s, int nSets, const int* setOff
     const unsigned int* hBest = st.res(bBest);
     for (int q = 0; q < nSets; q++)
         if (setOff[q + 1] > setOff[q]) {
-            bestIdx[q] = (int)(hBest[q] & 0xFFFFFu);
-            if (bestMedian) bestMedian[q] = (int)(hBest[q] >> 20);
+            bestIdx[q] = (int)(hBest[q] & ((1u << kDistinctIndexBits) - 1));
+            if (bestMedian) bestMedian[q] = (int)(hBest[q] >> kDistinctIndexBits);
         }
     return ORBFE_OK;
 }

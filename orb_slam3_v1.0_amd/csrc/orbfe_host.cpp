@@ -27,6 +27,8 @@
 #include "keyframe.h"
 #include "local_map.h"
 #include "covis_update.h"
+#include "covis_refresh.h"
+#include "covis_refresh_check.h"
 #include "marginalize.h"
 #include "poseimu_math.h"
 #include "prep.h"
@@ -1114,16 +1116,19 @@ struct orbfe_covis {  // the covisibility graph resident in HBM (orbfe_covis_*, 
     int* dCounters = nullptr;
     int scratchBatch = 0;
     CovisConn C{};  // the connection rows (SPEC DECISION S25): connStride == 0 until orbfe_covis_enable_connections
+    CovisRefresh R{};  // the refresh state (SPEC DECISION S26): nLevels == 0 until orbfe_covis_enable_refresh
 };
 
 // the caller holds h->mu (or is the handle's destruction); the handle's stream is idle
 static void covis_free(orbfe_covis* g)
 {
     void* ptrs[] = {g->T.kf, g->T.covisible, g->T.children, g->T.kfPoints, g->T.obsCount, g->T.obs, g->dStamps, g->dCounters,
-                    g->C.slots, g->C.weights, g->C.count, g->C.work};
+                    g->C.slots, g->C.weights, g->C.count, g->C.work,
+                    g->R.desc, g->R.octave, g->R.nFeat, g->R.centre, g->R.obsIdx, g->R.refKf, g->R.sf, g->R.rest};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     g->C = CovisConn{};
+    g->R = CovisRefresh{};
     g->T.kf = nullptr;
     g->T.covisible = g->T.children = g->T.kfPoints = g->T.obsCount = g->T.obs = nullptr;
     g->dStamps = nullptr;
@@ -2939,37 +2944,35 @@ int orbfe_covis_set_keyframes(orbfe_handle* h, orbfe_covis* g, int n, const orbf
         [&](std::string& err) { return covis_scatter_keyframes_launch(h->stream, T, n, stg.dev(bBlk), err); });
 }
 
-int orbfe_covis_set_observations(orbfe_handle* h, orbfe_covis* g, int n, const int* ids, const int* off, const int* kf_slots)
+}  // extern "C"
+
+// both observation setters; feat_idx: null for the form without indices, which on a graph with refresh state writes -1 (S26)
+static int covis_set_observations(orbfe_handle* h, orbfe_covis* g, int n, const int* ids, const int* off, const int* kf_slots,
+                                  const int* feat_idx, bool indexed)
 {
     if (!h || !g || g->h != h || !g->map || n < 0 || (n > 0 && (!ids || !off))) return ORBFE_ERR_INVALID_ARG;
-    if (n == 0) return ORBFE_OK;
+    if (indexed && g->R.nLevels == 0) return ORBFE_ERR_INVALID_ARG;
     const CovisTables& T = g->T;
-    if (off[0] < 0) return ORBFE_ERR_INVALID_ARG;
-    for (int i = 0; i < n; i++)
-        if (ids[i] < 0 || ids[i] >= T.cap || off[i + 1] < off[i] || off[i + 1] - off[i] > T.obsStride) return ORBFE_ERR_INVALID_ARG;
-    {
-        std::vector<int> sorted(ids, ids + n);
-        std::sort(sorted.begin(), sorted.end());
-        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return ORBFE_ERR_INVALID_ARG;
-    }
-    const int total = off[n];
-    if (total > off[0] && !kf_slots) return ORBFE_ERR_INVALID_ARG;
-    for (int k = off[0]; k < total; k++)
-        if (kf_slots[k] < 0 || kf_slots[k] >= T.kfCap) return ORBFE_ERR_INVALID_ARG;
+    if (!refresh_observations_ok(RefreshDims{T.kfCap, T.kfStride, T.obsStride, T.cap, g->R.nLevels}, n, ids, off, kf_slots, feat_idx, indexed))
+        return ORBFE_ERR_INVALID_ARG;
+    if (n == 0) return ORBFE_OK;
     Staging st;
-    const auto bIds = st.in<int>(n);
-    const auto bOff = st.in<int>((size_t)n + 1);
-    const auto bSlots = st.in<int>(std::max(total, 1));
+    const ObservationsStage B(st, n, off, indexed);
+    const auto bIds = B.ids, bOff = B.off, bSlots = B.slots, bIdx = B.idx;
     return covis_staged_call(
-        h, st, st.inBytes,
-        [&]() {
-            st.put(bIds, ids);
-            st.put(bOff, off);
-            st.put(bSlots, kf_slots, total);
-        },
+        h, st, st.inBytes, [&]() { B.fill(st, ids, off, kf_slots, feat_idx); },
         [&](std::string& err) {
-            return covis_scatter_observations_launch(h->stream, T, n, st.dev(bIds), st.dev(bOff), st.dev(bSlots), err);
+            const int rc = covis_scatter_observations_launch(h->stream, T, n, st.dev(bIds), st.dev(bOff), st.dev(bSlots), err);
+            if (rc != ORBFE_OK || g->R.nLevels == 0) return rc;
+            return covis_scatter_indices_launch(h->stream, T, g->R, n, st.dev(bIds), st.dev(bOff), indexed ? st.dev(bIdx) : nullptr, err);
         });
+}
+
+extern "C" {
+
+int orbfe_covis_set_observations(orbfe_handle* h, orbfe_covis* g, int n, const int* ids, const int* off, const int* kf_slots)
+{
+    return covis_set_observations(h, g, n, ids, off, kf_slots, nullptr, false);
 }
 
 // what the arguments alone decide, for both per-frame calls: no handle is looked at
@@ -3314,6 +3317,7 @@ int orbfe_covis_add_keyframe(orbfe_handle* h, orbfe_covis* g, const orbfe_covis_
         rc = covis_add_keyframe_launch(s, g->T, g->C.connStride ? &g->C : nullptr, g->map->dPts, k, rec->slot, st.dev(bIds), st.dev(bAdded),
                                        st.dev(bStatus), g->dStamps, e);
         if (rc != ORBFE_OK) return rc;
+        if (g->R.nLevels && (rc = covis_index_added_launch(s, g->T, g->R, rec->slot, n, st.dev(bIds), st.dev(bAdded), e)) != ORBFE_OK) return rc;
         if ((rc = download(st, s, e)) != ORBFE_OK) return rc;
         st.get(bAdded, added, n);
         *status = st.res(bStatus)[0];
@@ -3334,10 +3338,226 @@ int orbfe_covis_add_keyframe_device(orbfe_handle* h, orbfe_covis* g, const orbfe
     if (crc != ORBFE_OK) return crc;
     const CovisTables& T = g->T;
     return match_call(h, (hipStream_t)stream_, [&](hipStream_t s, std::string& e) -> int {
-        const int rc = covis_scratch(h, g, 1, s, e);
+        int rc = covis_scratch(h, g, 1, s, e);
         if (rc != ORBFE_OK) return rc;
-        return covis_add_keyframe_launch(s, T, g->C.connStride ? &g->C : nullptr, g->map->dPts, k, rec->slot, d_point_ids, d_added, d_status,
-                                         g->dStamps, e);
+        rc = covis_add_keyframe_launch(s, T, g->C.connStride ? &g->C : nullptr, g->map->dPts, k, rec->slot, d_point_ids, d_added, d_status,
+                                       g->dStamps, e);
+        if (rc != ORBFE_OK || g->R.nLevels == 0) return rc;
+        return covis_index_added_launch(s, T, g->R, rec->slot, n_features, d_point_ids, d_added, e);
+    });
+}
+
+// ---- refreshing map points from the resident graph: UpdateDepth and ComputeDistinctiveDescriptors (SPEC DECISION S26) ----
+
+int orbfe_covis_enable_refresh(orbfe_handle* h, orbfe_covis* g, int n_levels, const float* scale_factors)
+{
+    if (!h || !g || g->h != h || !g->map || !scale_factors || n_levels < 1 || n_levels > kRefreshMaxLevels) return ORBFE_ERR_INVALID_ARG;
+    const CovisTables& T = g->T;
+    const size_t rowsKf = (size_t)T.kfCap * T.kfStride;
+    if (rowsKf >= ((size_t)1 << 31)) return ORBFE_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (g->R.nLevels != 0) {
+        h->err = "orbfe_covis_enable_refresh: the graph has its refresh state already";
+        return ORBFE_ERR_INVALID_ARG;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    CovisRefresh R{};
+    R.nLevels = n_levels;
+    const size_t rowsObs = (size_t)T.cap * T.obsStride;
+    float sf[kRefreshMaxLevels] = {};
+    memcpy(sf, scale_factors, (size_t)n_levels * sizeof(float));
+    std::string err;
+    int rc = ORBFE_OK;
+    hipStream_t s = h->stream;
+    if (hipMalloc(&R.desc, rowsKf * ORBFE_DESC_BYTES) != hipSuccess || hipMalloc(&R.octave, rowsKf) != hipSuccess ||
+        hipMalloc(&R.nFeat, (size_t)T.kfCap * sizeof(int)) != hipSuccess || hipMalloc(&R.centre, (size_t)T.kfCap * 3 * sizeof(float)) != hipSuccess ||
+        hipMalloc(&R.obsIdx, rowsObs * sizeof(int)) != hipSuccess || hipMalloc(&R.refKf, (size_t)T.cap * sizeof(int)) != hipSuccess ||
+        hipMalloc(&R.sf, sizeof sf) != hipSuccess) {
+        err = "orbfe_covis_enable_refresh: allocation failed";
+        rc = ORBFE_ERR_OUT_OF_MEMORY;
+    }
+    // all rows empty: no features, indices and reference slots -1 (every byte 0xff)
+    if (rc == ORBFE_OK &&
+        (hipMemsetAsync(R.desc, 0, rowsKf * ORBFE_DESC_BYTES, s) != hipSuccess || hipMemsetAsync(R.octave, 0, rowsKf, s) != hipSuccess ||
+         hipMemsetAsync(R.nFeat, 0, (size_t)T.kfCap * sizeof(int), s) != hipSuccess ||
+         hipMemsetAsync(R.centre, 0, (size_t)T.kfCap * 3 * sizeof(float), s) != hipSuccess ||
+         hipMemsetAsync(R.obsIdx, 0xff, rowsObs * sizeof(int), s) != hipSuccess ||
+         hipMemsetAsync(R.refKf, 0xff, (size_t)T.cap * sizeof(int), s) != hipSuccess ||
+         copy_sync(R.sf, sf, sizeof sf, hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)) {
+        err = "orbfe_covis_enable_refresh: initialising the rows failed";
+        rc = ORBFE_ERR_HIP;
+    }
+    if (rc != ORBFE_OK) {
+        (void)hipGetLastError();
+        void* ptrs[] = {R.desc, R.octave, R.nFeat, R.centre, R.obsIdx, R.refKf, R.sf};
+        for (void* p : ptrs)
+            if (p) (void)hipFree(p);
+        h->err = err;
+        return rc;
+    }
+    g->R = R;
+    return ORBFE_OK;
+}
+
+// what every refresh setter refuses first
+static bool covis_no_refresh(const orbfe_handle* h, const orbfe_covis* g) { return !h || !g || g->h != h || !g->map || g->R.nLevels == 0; }
+static RefreshDims covis_dims(const orbfe_covis* g) { return RefreshDims{g->T.kfCap, g->T.kfStride, g->T.obsStride, g->T.cap, g->R.nLevels}; }
+
+int orbfe_covis_set_features(orbfe_handle* h, orbfe_covis* g, int slot, int n, const orbfe_keypoint* kp, const uint8_t* desc)
+{
+    if (covis_no_refresh(h, g) || !refresh_features_ok(covis_dims(g), slot, n, kp, desc, true)) return ORBFE_ERR_INVALID_ARG;
+    Staging st;
+    const FeaturesStage B(st, n);
+    return covis_staged_call(
+        h, st, st.inBytes, [&]() { B.fill(st, n, kp, desc); },
+        [&](std::string& err) { return covis_set_features_launch(h->stream, g->T, g->R, slot, n, st.dev(B.kp), st.dev(B.desc), err); });
+}
+
+int orbfe_covis_set_features_device(orbfe_handle* h, orbfe_covis* g, int slot, const orbfe_keypoint* d_kp, const uint8_t* d_desc, int n,
+                                    void* stream_)
+{
+    if (covis_no_refresh(h, g) || !refresh_features_ok(covis_dims(g), slot, n, d_kp, d_desc, false)) return ORBFE_ERR_INVALID_ARG;
+    return match_call(h, (hipStream_t)stream_, [&](hipStream_t s, std::string& e) -> int {
+        return covis_set_features_launch(s, g->T, g->R, slot, n, d_kp, d_desc, e);
+    });
+}
+
+int orbfe_covis_set_centres(orbfe_handle* h, orbfe_covis* g, int n, const int* slots, const float* twc)
+{
+    if (covis_no_refresh(h, g) || !refresh_centres_ok(covis_dims(g), n, slots, twc)) return ORBFE_ERR_INVALID_ARG;
+    if (n == 0) return ORBFE_OK;
+    Staging st;
+    const auto bSlots = st.in<int>(n);
+    const auto bTwc = st.in<float>((size_t)n * 3);
+    return covis_staged_call(
+        h, st, st.inBytes,
+        [&]() {
+            st.put(bSlots, slots);
+            st.put(bTwc, twc);
+        },
+        [&](std::string& err) { return covis_scatter_centres_launch(h->stream, g->T, g->R, n, st.dev(bSlots), st.dev(bTwc), err); });
+}
+
+int orbfe_covis_set_observations_indexed(orbfe_handle* h, orbfe_covis* g, int n, const int* ids, const int* off, const int* kf_slots,
+                                         const int* feat_idx)
+{
+    return covis_set_observations(h, g, n, ids, off, kf_slots, feat_idx, true);
+}
+
+int orbfe_covis_set_ref_keyframes(orbfe_handle* h, orbfe_covis* g, int n, const int* ids, const int* ref_slots)
+{
+    if (covis_no_refresh(h, g) || !refresh_refs_ok(covis_dims(g), n, ids, ref_slots)) return ORBFE_ERR_INVALID_ARG;
+    if (n == 0) return ORBFE_OK;
+    Staging st;
+    const auto bIds = st.in<int>(n);
+    const auto bRef = st.in<int>(n);
+    return covis_staged_call(
+        h, st, st.inBytes,
+        [&]() {
+            st.put(bIds, ids);
+            st.put(bRef, ref_slots);
+        },
+        [&](std::string& err) { return covis_scatter_ref_launch(h->stream, g->T, g->R, n, st.dev(bIds), st.dev(bRef), err); });
+}
+
+int orbfe_covis_get_point(orbfe_handle* h, orbfe_covis* g, int id, int* n_obs, int* kf_slots, int* feat_idx, int* ref_slot,
+                          orbfe_world_point* point, uint8_t* desc)
+{
+    if (covis_no_refresh(h, g) || !n_obs || !kf_slots || !feat_idx || !ref_slot || id < 0 || id >= g->T.cap) return ORBFE_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIPCHK(h, hipSetDevice(h->device));
+    const CovisTables& T = g->T;
+    hipStream_t s = h->stream;
+    const size_t S = (size_t)T.obsStride;
+    HIPCHK(h, hipMemcpyAsync(n_obs, T.obsCount + id, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(kf_slots, T.obs + (size_t)id * S, S * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(feat_idx, g->R.obsIdx + (size_t)id * S, S * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(ref_slot, g->R.refKf + id, sizeof(int), hipMemcpyDeviceToHost, s));
+    if (point) HIPCHK(h, hipMemcpyAsync(point, g->map->dPts + id, sizeof *point, hipMemcpyDeviceToHost, s));
+    if (desc) HIPCHK(h, hipMemcpyAsync(desc, g->map->dDesc + (size_t)id * ORBFE_DESC_BYTES, ORBFE_DESC_BYTES, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    return ORBFE_OK;
+}
+
+// the rest list for a call of n entries; the caller holds h->mu.  Grows only, both counters at zero when it does.
+static int covis_refresh_scratch(orbfe_covis* g, int n, hipStream_t s, std::string& err)
+{
+    CovisRefresh& R = g->R;
+    if (n > R.restCap) {
+        // the block in use may still be read by a call in flight on another stream: hipFree waits for the device
+        if (R.rest) (void)hipFree(R.rest);
+        R.rest = nullptr;
+        R.restCap = 0;
+        if (hipMalloc(&R.rest, ((size_t)n + 2) * sizeof(int)) != hipSuccess) {
+            (void)hipGetLastError();
+            R.rest = nullptr;
+            err = "orbfe_covis_refresh_points: allocation of the rest list failed";
+            return ORBFE_ERR_OUT_OF_MEMORY;
+        }
+        MCHK(hipMemsetAsync(R.rest, 0, 2 * sizeof(int), s));
+        R.restCap = n;
+        R.parity = 0;
+    }
+    return ORBFE_OK;
+}
+
+// what the arguments alone decide, for both forms
+static int covis_refresh_refuse(const orbfe_handle* h, const orbfe_covis* g, int n, const void* ids, int what)
+{
+    if (covis_no_refresh(h, g) || !ids || n < 1 || what < 1 || what > 3) return ORBFE_ERR_INVALID_ARG;
+    return ORBFE_OK;
+}
+
+// the two launches of one call; the caller holds h->mu inside a call scope
+static int covis_refresh_run(orbfe_covis* g, hipStream_t s, int n, const int* dIds, const int* dSelect, int selectValue, int what,
+                             const RefreshOut& out, std::string& e)
+{
+    int rc = covis_refresh_scratch(g, n, s, e);
+    if (rc != ORBFE_OK) return rc;
+    rc = covis_refresh_launch(s, g->T, g->R, g->map->dPts, g->map->dDesc, n, dIds, dSelect, selectValue, what, out, e);
+    g->R.parity ^= 1;
+    return rc;
+}
+
+int orbfe_covis_refresh_points_device(orbfe_handle* h, orbfe_covis* g, int n, const int* d_ids, const int* d_select, int select_value,
+                                      int what, const orbfe_refresh_io* io, void* stream_)
+{
+    if (!io) return ORBFE_ERR_INVALID_ARG;
+    if (io->struct_size != (int)sizeof(orbfe_refresh_io))
+        return refuse(h, ORBFE_ERR_INVALID_ARG,
+                      "orbfe_refresh_io.struct_size does not match this library (rebuild the caller against include/orbfe.h)", kKeep);
+    const int crc = covis_refresh_refuse(h, g, n, d_ids, what);
+    if (crc != ORBFE_OK) return crc;
+    const RefreshOut out{io->d_status, io->d_min_distance, io->d_max_distance, io->d_best_slot, io->d_best_index, io->d_best_median};
+    return match_call(h, (hipStream_t)stream_, [&](hipStream_t s, std::string& e) -> int {
+        return covis_refresh_run(g, s, n, d_ids, d_select, select_value, what, out, e);
+    });
+}
+
+int orbfe_covis_refresh_points(orbfe_handle* h, orbfe_covis* g, int n, const int* ids, int what, int* status, float* min_distance,
+                               float* max_distance, int* best_slot, int* best_index, int* best_median)
+{
+    const int crc = covis_refresh_refuse(h, g, n, ids, what);
+    if (crc != ORBFE_OK) return crc;
+    Staging st;
+    const RefreshStage B(st, n);
+    const auto bIds = B.ids, bStatus = B.status, bSlot = B.slot, bIndex = B.index, bMedian = B.median;
+    const auto bMin = B.minD, bMax = B.maxD;
+    return match_call(h, nullptr, [&](hipStream_t s, std::string& e) -> int {
+        int rc = reserve(h->match, st, e);
+        if (rc != ORBFE_OK) return rc;
+        st.put(bIds, ids);
+        if ((rc = upload(st, s, e)) != ORBFE_OK) return rc;
+        const RefreshOut out{st.dev(bStatus), st.dev(bMin), st.dev(bMax), st.dev(bSlot), st.dev(bIndex), st.dev(bMedian)};
+        if ((rc = covis_refresh_run(g, s, n, st.dev(bIds), nullptr, 0, what, out, e)) != ORBFE_OK) return rc;
+        if ((rc = download(st, s, e)) != ORBFE_OK) return rc;
+        st.get(bStatus, status);
+        st.get(bMin, min_distance);
+        st.get(bMax, max_distance);
+        st.get(bSlot, best_slot);
+        st.get(bIndex, best_index);
+        st.get(bMedian, best_median);
+        return ORBFE_OK;
     });
 }
 

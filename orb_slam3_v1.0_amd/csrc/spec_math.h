@@ -175,4 +175,20 @@ ORBFE_HD inline double spec_cbrt64(double x)
     return ldexp(y, q - 1000);
 }
 
+// ---- SPEC DECISION S26: MapPoint::UpdateDepth (src/MapPoint.cc:458-472) in binary32 ----
+// dist = |Pos - centre| as sqrt((x x + y y) + z z), every operation rounded once (sqrtf and the division are correctly rounded on both
+// sides); max = dist * sf[level], min = max / sf[nLevels - 1]
+ORBFE_HD inline float spec_point_distance(float px, float py, float pz, float cx, float cy, float cz)
+{
+    const float x = px - cx, y = py - cy, z = pz - cz;
+    const float xx = x * x, yy = y * y, zz = z * z;
+    const float s = xx + yy;
+    return sqrtf(s + zz);
+}
+ORBFE_HD inline void spec_update_depth(float dist, float levelScale, float lastScale, float& minDistance, float& maxDistance)
+{
+    maxDistance = dist * levelScale;
+    minDistance = maxDistance / lastScale;
+}
+
 }  // namespace orbfe

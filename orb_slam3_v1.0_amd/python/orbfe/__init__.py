@@ -507,6 +507,21 @@ class CovisUpdateIO(C.Structure):
         self.struct_size = C.sizeof(CovisUpdateIO)
 
 
+# SPEC DECISION S26 (include/orbfe.h), checked against the header by tests/test_point_refresh_abi.py
+REFRESH_MAX_LEVELS = 32
+REFRESH_DEPTH, REFRESH_DESCRIPTOR = 1, 2
+REFRESH_IO_FIELDS = ("d_status", "d_min_distance", "d_max_distance", "d_best_slot", "d_best_index", "d_best_median")
+
+
+class RefreshIO(C.Structure):
+    """orbfe_refresh_io: the device pointers of orbfe_covis_refresh_points_device (as ints), any may be None."""
+    _fields_ = [("struct_size", C.c_int), ("reserved", C.c_int)] + [(k, C.c_void_p) for k in REFRESH_IO_FIELDS]
+
+    def __init__(self, **k):
+        super().__init__(**k)
+        self.struct_size = C.sizeof(RefreshIO)
+
+
 class FrameView(C.Structure):
     _fields_ = [("n", C.c_int), ("kp", C.c_void_p), ("desc", C.c_void_p), ("grid_cols", C.c_int),
                 ("grid_rows", C.c_int), ("min_x", C.c_float), ("min_y", C.c_float),
@@ -542,6 +557,9 @@ SYMBOLS = [
     "orbfe_update_local_map_batch_device", "orbfe_update_local_map", "orbfe_frame_points_batch_device",
     "orbfe_covis_enable_connections", "orbfe_covis_set_connections", "orbfe_covis_get_keyframe",
     "orbfe_covis_update_connections_device", "orbfe_covis_update_connections", "orbfe_covis_add_keyframe_device", "orbfe_covis_add_keyframe",
+    "orbfe_covis_enable_refresh", "orbfe_covis_set_features", "orbfe_covis_set_features_device", "orbfe_covis_set_centres",
+    "orbfe_covis_set_observations_indexed", "orbfe_covis_set_ref_keyframes", "orbfe_covis_get_point",
+    "orbfe_covis_refresh_points_device", "orbfe_covis_refresh_points",
     "orbfe_shard_range", "orbfe_pool_create", "orbfe_pool_destroy", "orbfe_pool_size", "orbfe_pool_member",
     "orbfe_pool_member_frames", "orbfe_pool_last_error", "orbfe_pool_extract", "orbfe_pool_enable_track",
     "orbfe_pool_map_update", "orbfe_pool_track",
@@ -712,6 +730,16 @@ def lib():
         L.orbfe_covis_update_connections.argtypes = [vp, C.POINTER(CovisUpdateParams), vp, ci, ci, vp, vp, C.POINTER(ci), C.POINTER(ci)]
         L.orbfe_covis_add_keyframe_device.argtypes = [vp, vp, C.POINTER(CovisKeyframe), vp, ci, vp, vp, vp]
         L.orbfe_covis_add_keyframe.argtypes = [vp, vp, C.POINTER(CovisKeyframe), vp, C.POINTER(ci)]
+    if hasattr(L, "orbfe_covis_refresh_points_device"):  # (as above)
+        L.orbfe_covis_enable_refresh.argtypes = [vp, vp, ci, vp]
+        L.orbfe_covis_set_features.argtypes = [vp, vp, ci, ci, vp, vp]
+        L.orbfe_covis_set_features_device.argtypes = [vp, vp, ci, vp, vp, ci, vp]
+        L.orbfe_covis_set_centres.argtypes = [vp, vp, ci, vp, vp]
+        L.orbfe_covis_set_observations_indexed.argtypes = [vp, vp, ci, vp, vp, vp, vp]
+        L.orbfe_covis_set_ref_keyframes.argtypes = [vp, vp, ci, vp, vp]
+        L.orbfe_covis_get_point.argtypes = [vp, vp, ci, C.POINTER(ci), vp, vp, C.POINTER(ci), vp, vp]
+        L.orbfe_covis_refresh_points_device.argtypes = [vp, vp, ci, vp, vp, ci, ci, C.POINTER(RefreshIO), vp]
+        L.orbfe_covis_refresh_points.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "orbfe_initial_bundle_adjustment"):  # (as above)
         L.orbfe_initial_bundle_adjustment.argtypes = [vp, C.POINTER(InitialBAParams), ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                                       C.POINTER(InitialBAInfo)]
@@ -1028,6 +1056,66 @@ class Covisibility:
                             point_ids=ids.ctypes.data if len(ids) else None)
         self.e._chk(self.L.orbfe_covis_add_keyframe(self.e.h, self.h, C.byref(rec), _p(added), C.byref(st)), "orbfe_covis_add_keyframe")
         return dict(added=added[:len(ids)], status=st.value)
+
+    # ---- SPEC DECISION S26: map points refreshed from the graph ----
+    n_levels = 0
+
+    def enable_refresh(self, scale_factors):
+        """orbfe_covis_enable_refresh: descriptors, octaves and centres per key frame, feature indices and mpRefKF per point"""
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        self.e._chk(self.L.orbfe_covis_enable_refresh(self.e.h, self.h, len(sf), _p(sf)), "orbfe_covis_enable_refresh")
+        self.n_levels = len(sf)
+
+    def set_features(self, slot, kp, desc):
+        kp, desc = np.ascontiguousarray(kp, KP_DTYPE), np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        assert len(kp) == len(desc)
+        self.e._chk(self.L.orbfe_covis_set_features(self.e.h, self.h, int(slot), len(kp), _p(kp) if len(kp) else None,
+                                                    _p(desc) if len(kp) else None), "orbfe_covis_set_features")
+
+    def set_features_device(self, slot, d_kp_ptr, d_desc_ptr, n, stream=None):
+        """orbfe_covis_set_features_device: the arrays an extraction left in HBM; raw device pointers"""
+        self.e._chk(self.L.orbfe_covis_set_features_device(self.e.h, self.h, int(slot), d_kp_ptr, d_desc_ptr, int(n), stream),
+                    "orbfe_covis_set_features_device")
+
+    def set_centres(self, slots, twc):
+        slots, twc = np.ascontiguousarray(slots, np.int32), np.ascontiguousarray(twc, np.float32).reshape(-1, 3)
+        assert len(slots) == len(twc)
+        self.e._chk(self.L.orbfe_covis_set_centres(self.e.h, self.h, len(slots), _p(slots), _p(twc)), "orbfe_covis_set_centres")
+
+    def set_observations_indexed(self, ids, off, kf_slots, feat_idx):
+        ids, off, kf_slots, feat_idx = (np.ascontiguousarray(a, np.int32) for a in (ids, off, kf_slots, feat_idx))
+        assert len(off) == len(ids) + 1 and len(kf_slots) == len(feat_idx)
+        self.e._chk(self.L.orbfe_covis_set_observations_indexed(self.e.h, self.h, len(ids), _p(ids), _p(off), _p(kf_slots) if len(kf_slots) else None,
+                                                                _p(feat_idx) if len(feat_idx) else None), "orbfe_covis_set_observations_indexed")
+
+    def set_ref_keyframes(self, ids, ref_slots):
+        ids, ref_slots = np.ascontiguousarray(ids, np.int32), np.ascontiguousarray(ref_slots, np.int32)
+        assert len(ids) == len(ref_slots)
+        self.e._chk(self.L.orbfe_covis_set_ref_keyframes(self.e.h, self.h, len(ids), _p(ids), _p(ref_slots)), "orbfe_covis_set_ref_keyframes")
+
+    def get_point(self, id_):
+        """orbfe_covis_get_point -> dict(obs [(slot, index)], ref, record (WP_DTYPE scalar), desc (32 bytes))"""
+        n, ref = C.c_int(0), C.c_int(0)
+        sl, ix = np.zeros(self.obs_stride, np.int32), np.zeros(self.obs_stride, np.int32)
+        rec, desc = np.zeros(1, WP_DTYPE), np.zeros(32, np.uint8)
+        self.e._chk(self.L.orbfe_covis_get_point(self.e.h, self.h, int(id_), C.byref(n), _p(sl), _p(ix), C.byref(ref), _p(rec), _p(desc)),
+                    "orbfe_covis_get_point")
+        return dict(obs=list(zip(sl[:n.value].tolist(), ix[:n.value].tolist())), ref=ref.value, record=rec[0], desc=desc)
+
+    def refresh_points_device(self, n, d_ids_ptr, what, io, d_select_ptr=None, select_value=0, stream=None):
+        """orbfe_covis_refresh_points_device: raw device pointers, io a RefreshIO"""
+        self.e._chk(self.L.orbfe_covis_refresh_points_device(self.e.h, self.h, int(n), d_ids_ptr, d_select_ptr, int(select_value), int(what),
+                                                             C.byref(io), stream), "orbfe_covis_refresh_points_device")
+
+    def refresh_points(self, ids, what=3):
+        """orbfe_covis_refresh_points: a host list -> dict(status, min_distance, max_distance, best_slot, best_index, best_median)"""
+        ids = np.ascontiguousarray(ids, np.int32)
+        n = max(len(ids), 1)
+        out = dict(status=np.zeros(n, np.int32), min_distance=np.zeros(n, np.float32), max_distance=np.zeros(n, np.float32),
+                   best_slot=np.zeros(n, np.int32), best_index=np.zeros(n, np.int32), best_median=np.zeros(n, np.int32))
+        self.e._chk(self.L.orbfe_covis_refresh_points(self.e.h, self.h, len(ids), _p(ids), int(what), *(_p(out[k]) for k in (
+            "status", "min_distance", "max_distance", "best_slot", "best_index", "best_median"))), "orbfe_covis_refresh_points")
+        return {k: v[:len(ids)] for k, v in out.items()}
 
     def close(self):
         if getattr(self, "h", None):
